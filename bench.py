@@ -1,12 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/s of the per-buoy advection hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one model record applied to every buoy of the batch.  `sitrk_run` advances 32 resident records per launch
-(advect_run_kernel: loop interchange, every buoy still takes every step -- the form the command line runs too); the same
-K steps with one launch of advect_step_kernel per record and with 8 records per launch are timed in the same run and
-reported under `per_record_launch` / `eight_records_per_launch`.
+(advect_run_kernel: loop interchange, every buoy still takes every step -- the form the command line runs too).
+
+A plain run sets up the workload, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line:
+`value`, `ms_per_step` and the fused kernel's `roofline` (priced from the timed steps themselves).  Everything else it can
+measure runs only with --full, after the headline leg: the same K steps with one launch of advect_step_kernel per record and
+with 8 records per launch (`per_record_launch` / `eight_records_per_launch`), `fresh_records`, `cpu_baseline`, `c2`,
+`c4_shard`, `e2e_upload` and, at N > 1, `solo_same_shard` and `e2e_broadcast`.
+
+--dump-outputs DIR: right after the timed steps, the state they leave a caller with (sitrk_fetch, in the caller's buoy
+order) is written as DIR/yx.npy (fp64 positions), DIR/jiT.npy (host cells), DIR/alive.npy and DIR/kill_rec.npy (float64 /
+float32, every value exact) for a fixed, seeded sample of at most DUMP_SAMPLE buoys of rank 0 (all of them when there are
+fewer).  Grid, buoys and records are seeded: the same arguments give the same inputs in every run.
 
 Workload: N = 1 -> BASELINE.json configs[2] (C3, the one the metric is quoted on): synthetic regular 4096x4096 C-grid
 (4 km), 1e7 random buoys in the central 60 %, 32 device-resident fp32 records (solid-body rotation + per-record drift,
@@ -18,21 +27,22 @@ seeds kept by the product's own SeedInit under a synthetic land / ice mask (BASE
 
 Prints ONE JSON line (rank 0).
  * `value`: the K resident records are cycled, so each record's Survive bytes (tracking.py:62-93 once per cell) are derived
-   once and reused K/records_resident times OUTSIDE the clock.  `fresh_records.value` = the same steps with every record
+   once and reused K/records_resident times OUTSIDE the clock.  `fresh_records.value` (--full) = the same steps with every record
    committed afresh (Survive re-derived over the box the buoys can touch, one launch per batch of records) INSIDE the clock.
  * `roofline` of the fused kernel: bound "valu_issue+wave_chain"; achieved = VALU instructions per second (instructions per
    wave and record from the committed rocprofv3 counters in profiles/traffic.json x waves x records really advanced, counted
    by the library: sitrk_launch_stats) against a class-weighted issue ceiling (a model) and the uniform 4-cycle ceiling;
-   `lane_utilisation` = share of the issued lanes that do work; `stale` = the profiled binary is not the one that ran
+   `lane_utilisation` = share of the issued lanes that do work (crossing rate counted by --full's cpu_baseline, else the
+   profile's); `stale` = the profiled binary is not the one that ran
    (kernel fingerprints, tools/kernel_fingerprint.py) -- `frac` is dropped then.  `traffic` = measured fabric bytes per launch
    (FETCH_SIZE x 2 + WRITE_SIZE of the same command, profiles/); `hbm` = the algorithmic-byte view.  Algorithmic bytes follow
    SURVEY.md 8(d) -- 50 B of state per buoy + 56 B (48 B geometry + u,v) per grid cell a step needs.
- * `per_record_launch.roofline`: bound "hbm", algorithmic bytes of one record over the measured launch time.
- * `cpu_baseline`: the CPU oracle (oracle/sitrk_oracle.c, a port of the reference loop, OpenMP over buoys) timed on this
-   box's host cores on a bounded sample of the same workload.
- * N = 1: `c4_shard` = C4's per-rank shard (1.25e7 buoys) on this one GPU -- the N = 1 point of the weak-scaling curve --
+ * `per_record_launch.roofline` (--full): bound "hbm", algorithmic bytes of one record over the measured launch time.
+ * `cpu_baseline` (--full): the CPU oracle (oracle/sitrk_oracle.c, a port of the reference loop, OpenMP over buoys) timed on
+   this box's host cores on a bounded sample of the same workload.
+ * N = 1 (--full): `c4_shard` = C4's per-rank shard (1.25e7 buoys) on this one GPU -- the N = 1 point of the weak-scaling curve --
    and `e2e_upload` = one record per step from host memory through the library's pinned staging (whole records and boxes).
- * N > 1: `solo_same_shard` (rank 0 alone, the others idle) and `efficiency_vs_n1_same_shard`; `e2e_broadcast` = a short
+ * N > 1 (--full): `solo_same_shard` (rank 0 alone, the others idle) and `efficiency_vs_n1_same_shard`; `e2e_broadcast` = a short
    segment with ONE broadcast of every record's slab per step overlapped with the stepping (RCCL broadcast and scatter +
    all-gather), next to the resident `value`.
 """
@@ -210,7 +220,31 @@ def parse():
     ap.add_argument("--regime", default="resident", choices=["resident", "e2e"],
                     help="resident: records live in HBM (the metric). e2e: every step's record is uploaded from pinned host "
                          "memory on rank 0 (+ RCCL broadcast), double-buffered against the stepping; reported for context only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, measure everything else too (per-record and 8-per-launch legs, fresh records, "
+                         "CPU baseline, C2, C4 shard, end-to-end segments, N > 1 solo leg); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the state the timed steps leave (a fixed, seeded sample of rank 0's buoys) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20              # buoys --dump-outputs writes at most: 46 MB
+
+
+def dump_outputs(ctx, outdir, seed=2024):
+    """--dump-outputs: what a caller of the timed path receives after its last step (sitrk_fetch, caller's buoy order) for
+    a fixed, seeded sample of the buoys; integers as float64 / float32, where every value they take is exact"""
+    st = ctx.fetch()
+    nP = ctx.nP
+    if nP <= DUMP_SAMPLE:
+        idx = np.arange(nP)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(nP, DUMP_SAMPLE, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    out = {"yx": st["yx"][idx], "jiT": st["jiT"][idx].astype(np.float64), "alive": st["alive"][idx].astype(np.float32),
+           "kill_rec": st["kill_rec"][idx].astype(np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr))
 
 
 # The reference's OWN Python loop cannot run on the GPU box (no /root/reference there): it was timed in the build container
@@ -743,7 +777,8 @@ def main():
     slabs_host = None
     if rank == 0:
         u, v, sic = make_records(syn, w, K)
-        slabs_host = [sd.pack_slab(u[k], v[k], sic[k], np.float32) for k in range(K)]
+        if dist is not None or a.regime == "e2e":        # (one GPU, resident: the records are pushed from u, v, sic)
+            slabs_host = [sd.pack_slab(u[k], v[k], sic[k], np.float32) for k in range(K)]
     records_via = "host upload" if dist is None else ("RCCL broadcast from rank 0" if backend == "nccl" else backend + " broadcast from rank 0")
     _STATE["base"]["config"] = {"workload": label, "grid": [Nj, Ni], "buoys_per_gpu": nP, "buoys_total": nP * world, "regime": a.regime,
                                 "partition": "buoy-range x%d" % world, "records_via": records_via}
@@ -827,7 +862,7 @@ def main():
         ctx.set_tuning(fuse=fuse)
         ctx.run(0, 0, a.warmup)
         nrun = a.warmup
-        if dist is not None and not a.only_fused:
+        if dist is not None and a.full and not a.only_fused:
             # the same-shard N = 1 point, measured in THIS job: rank 0 steps alone while every other rank idles at the barrier
             # (what follows is then the ratio of two runs of one binary on one node, not of two workloads)
             _phase("solo leg (rank 0 alone)")
@@ -840,17 +875,20 @@ def main():
             nrun += a.steps
         dt, ev_ms, stats = timed_run(nrun, a.steps, fuse)
         nrun += a.steps
-        if fuse > 1 and not a.only_fused and not a.no_fresh:
+        if a.dump_outputs and rank == 0:
+            dump_outputs(ctx, a.dump_outputs)
+        extras = a.full and not a.only_fused
+        if fuse > 1 and extras and not a.no_fresh:
             # right behind the headline leg (the box the buoys can touch grows as the cloud rotates: same state, same launches)
             _phase("fresh-records leg")
             fresh = fresh_records_leg(ctx, K, fuse, nrun, a.steps, barrier, overlap=a.fresh_overlap)
             nrun += a.steps
-        if fuse > 1 and not a.only_fused:
+        if fuse > 1 and extras:
             # for reference: the same K steps with one launch per record (the HBM-bound form of the kernel)
             dt1, ev1_ms, st1 = timed_run(nrun, a.steps, 1)
             per_record = (dt1, ev1_ms, st1)
             nrun += a.steps
-        if fuse > 8 and not a.only_fused:
+        if fuse > 8 and extras:
             # for reference: 8 records per launch (the K = 8 of SURVEY 8d's synthetic set-up allows no more)
             eight = timed_run(nrun, a.steps, 8)[0]
             nrun += a.steps
@@ -947,6 +985,8 @@ def main():
             ctx.buoy_box_end()
         if not a.e2e_library:
             ctx.set_stream(None)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(ctx, a.dump_outputs)
         e2e_bytes_per_step = st["bytes"] / float(a.steps)
         nrun = a.warmup + a.steps
     value_per_rank = None
@@ -981,13 +1021,13 @@ def main():
     # ---- N = 1 extras on the same context, after everything `value` and the check need (they move the buoys on)
     e2e_upload = None
     c4_shard = None
-    plain = world == 1 and dist is None and a.regime == "resident" and not a.only_fused
-    if plain and not a.no_e2e_upload and K >= 2:
+    n1_extras = a.full and world == 1 and dist is None and a.regime == "resident" and not a.only_fused
+    if n1_extras and not a.no_e2e_upload and K >= 2:
         _phase("e2e upload segment")
         e2e_upload, nrun = e2e_upload_segment(ctx, w, u, v, sic, K, nrun)
         for k in (0, 1):
             ctx.push_record(k, u[k], v[k], sic[k])           # the two slots the segment used hold whole records again
-    if plain and a.config == "c3" and a.buoys == 0 and not a.no_c4_shard:
+    if n1_extras and a.config == "c3" and a.buoys == 0 and not a.no_c4_shard:
         _phase("c4 shard sub-run")
         c4_shard = c4_shard_subrun(a, syn, ctx, w, K, fuse, nrun, barrier)
 
@@ -1010,7 +1050,7 @@ def main():
 
     e2e_bcast = None
     e2e_hung = False
-    if dist is not None and a.regime == "resident" and backend == "nccl" and not a.no_e2e_broadcast:
+    if a.full and dist is not None and a.regime == "resident" and backend == "nccl" and not a.no_e2e_broadcast:
         # Everything `value` needs is measured and reduced by now.  The extra segment runs under a watchdog: if a collective
         # in it never completes on some rank, every rank gives up after the same wait, rank 0 still prints the line (with
         # the segment marked as timed out) and the processes leave without touching the stuck communicator.
@@ -1163,7 +1203,7 @@ def main():
         # crossing rate of THIS workload (share of the buoy-records that leave their cell): counted by the CPU oracle on its
         # baseline sample when that leg runs, else the figure stored with the profile
         cpu_base = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             _phase("cpu baseline")
             cpu_base = cpu_baseline(grid, u, v, sic, yx, ji, a.cpu_seconds, a.uv_strategy)
         p_cross, p_cross_src = prof_fused.get("crossing_rate"), "profiles/traffic.json"
@@ -1191,8 +1231,8 @@ def main():
         }
         if a.regime == "resident":
             line["note"] = ("the %d resident records are cycled: each record's Survive bytes (sitrack/tracking.py:62-93 once per cell) were "
-                            "derived once at ingest and reused ~%.1f times OUTSIDE the timed region; fresh_records.value has every record "
-                            "committed once, inside the clock" % (K, amort))
+                            "derived once at ingest and reused ~%.1f times OUTSIDE the timed region; fresh_records.value (--full) has "
+                            "every record committed once, inside the clock" % (K, amort))
         if fresh is not None:
             fs = fresh["stats"]
             line["fresh_records"] = {
@@ -1236,7 +1276,7 @@ def main():
         if e2e_bcast is not None:
             line["e2e_broadcast"] = e2e_bcast
         # (nothing below touches the GPU when the segment's thread is stuck inside a collective)
-        if world == 1 and not e2e_hung and a.regime == "resident" and a.config == "c3" and a.buoys == 0 and not a.no_c2 and not a.warp:
+        if a.full and world == 1 and not e2e_hung and a.regime == "resident" and a.config == "c3" and a.buoys == 0 and not a.no_c2 and not a.warp:
             _phase("c2 sub-run")
             line["c2"] = c2_subrun(sit, syn, dev, a)
         if cpu_base is not None:

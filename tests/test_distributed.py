@@ -587,7 +587,7 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     env = dict(os.environ, SITRK_DIST_BACKEND="gloo", SITRK_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "8", "--config", "c2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -627,7 +627,8 @@ def test_bench_multi_gpu_code_path_with_one_rccl_rank():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SITRK_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "bench.py", "--config", "c2", "--steps", "96", "--warmup", "8", "--no-cpu-baseline", "--check"],
+    r = subprocess.run([sys.executable, "bench.py", "--config", "c2", "--steps", "96", "--warmup", "8", "--no-cpu-baseline", "--check",
+                        "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "check OK" in r.stderr
@@ -655,7 +656,7 @@ def test_bench_line_survives_a_stuck_end_to_end_segment():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SITRK_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), SITRK_E2E_SEGMENT_TIMEOUT="0.001")
-    r = subprocess.run([sys.executable, "bench.py", "--config", "c2", "--steps", "64", "--warmup", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--config", "c2", "--steps", "64", "--warmup", "8", "--no-cpu-baseline", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 3, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -44,7 +44,7 @@ def test_c2_full_1000_steps_checked_by_the_oracle():
 def test_c3_full_1000_steps_checked_by_the_oracle():
     """the headline workload at the length BASELINE quotes it: 1e7 buoys x 1000 records (+ the fresh-records leg and the two
     reference legs of the same run), first 20 000 buoys bit-exact against the oracle at the end"""
-    d, err = _bench(["--steps", "1000", "--warmup", "50", "--check", "--no-cpu-baseline", "--no-c2"])
+    d, err = _bench(["--steps", "1000", "--warmup", "50", "--full", "--check", "--no-cpu-baseline", "--no-c2"])
     assert "check OK" in err and "after 4050 steps" in err, err[-2000:]          # warm-up + headline + fresh + per-record + 8-per-launch legs
     assert d["config"]["grid"] == [4096, 4096] and d["config"]["buoys_per_gpu"] == 10_000_000 and d["value"] > 1e9
     r = d["roofline"]

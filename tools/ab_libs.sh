@@ -2,7 +2,7 @@
 # Runs on the GPU box: bench.py once per variant library in build_ab/ (tools/build_variant.sh), interleaved over ROUNDS rounds.
 #   tools/ab_libs.sh <tag> "<variant names>" [bench args...]
 TAG=$1; VARS=$2; shift 2
-ARGS=${@:---steps 640 --warmup 64 --no-cpu-baseline --no-c2}
+ARGS=${@:---steps 640 --warmup 64 --no-cpu-baseline --no-c2 --full}
 mkdir -p gpurun_out
 for r in 1 2; do
   for v in $VARS; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box: bench.py once per --tune setting (product library), two rounds.   tools/ab_tune_bench.sh <tag> "<tune1>;<tune2>;..." [bench args]
 TAG=$1; IFS=';' read -ra SETS <<< "$2"; shift 2
-ARGS=${@:---steps 640 --warmup 64 --no-cpu-baseline --no-c2}
+ARGS=${@:---steps 640 --warmup 64 --no-cpu-baseline --no-c2 --full}
 mkdir -p gpurun_out
 for r in 1 2; do
   n=0
