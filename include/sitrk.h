@@ -99,7 +99,8 @@ int sitrk_set_params(sitrk_t *h, double rdt, int uv_strategy, double rmin_conc);
  * cells it takes around their bounding box; "xcd_group" (0..4096, default 16): runs of that many consecutive workgroups of the
  * fused kernel share an XCD (its L2); "step_block" (256/512/1024): workgroup size of the one-record kernel; "fuse" (1..32):
  * consecutive resident records advanced per launch by sitrk_run (loop interchange: the buoys are independent, each lane keeps
- * its buoy in registers across the records). */
+ * its buoy in registers across the records); "subsample_block" (256..4096, powers of two, default 1024): points per workgroup of
+ * sitrk_subsample_cloud's resolve kernel. */
 int sitrk_set_tuning(sitrk_t *h, const char *knob, int value);
 
 /* ---- model records (u_ice, v_ice, siconc) -------------------------------
@@ -272,6 +273,22 @@ int sitrk_nearest_point(sitrk_t *h, int64_t nP, const double *latlon, const doub
 int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t *tmask, const int8_t *rmask,
                     const double *latT, const double *lonT, const double *sic, const double *latF, const double *lonF,
                     double lat0, double lon0, int64_t capacity, double *latlon, double *yx, int64_t *nT, int64_t *nF);
+
+/* ---- seed-cloud coarsening -------------------------------------------------
+ * SubSampCloud (sitrack/util.py:345-370), i.e. gudhi.subsampling.sparsify_point_set(yx, min_squared_dist=rd_km**2) on the
+ * seeds' polar-stereographic [y,x] km: n points yx (n,2) in the given order, keep[k] 1/0, *nkeep = number kept.
+ * Contract: d2(i,j) = (y_i-y_j)*(y_i-y_j) + (x_i-x_j)*(x_i-x_j), two rounded fp64 products and one rounded sum, no FMA,
+ * compared with r2 = rd_km*rd_km (rounded fp64).  Point i is kept iff no kept j < i has d2(i,j) < r2: pairs at exactly
+ * d2 == r2 are both kept, duplicates collapse to the first.  This is the lexicographically-first maximal independent set
+ * of the graph with edges d2 < r2 -- the greedy loop of gudhi's sparsify_point_set, whose documented guarantee is
+ * "squared distance between any two output points >= min_squared_dist".  The boundary rule and the rounding are taken
+ * from that documented behaviour and loop; gudhi itself is not available to this project, so bit parity with gudhi is
+ * UNPINNED.  Result independent of the knob "subsample_block" (points per workgroup, 256..4096, powers of two).
+ * Host arrays, synchronous on the handle's stream like sitrk_nemo_seed; n == 0 is valid.  *launches (may be NULL) =
+ * launches of the resolve kernel.  Uses the context's transient scratch only (never read by the stepping): the grid,
+ * buoys and records of a tracker on the same handle are left as they were.  SITRK_EINVAL when rd_km is not finite or
+ * <= 0, when a coordinate is not finite (the first such index is named in sitrk_last_error) or a pointer is missing. */
+int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, double rd_km, int8_t *keep, int64_t *nkeep, int32_t *launches);
 
 /* ---- predicate probes ------------------------------------------------------
  * The device-side predicates of the hot path evaluated on plain arrays, so that each one can be held

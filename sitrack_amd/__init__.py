@@ -11,4 +11,5 @@ from .predicates import (_ccw_, intersect2Seg, IsInsideQuadrangle, CrossedEdge, 
                          Survive, Haversine, NearestPoint)
 from .ncio import (GetModelGrid, GetModelUVGrid, LoadNCtime, LoadNCdata, SeedFileTimeInfo, ModelFileTimeInfo,  # noqa: F401
                    ncSaveCloudBuoys, chck4f)
+from .seeding import SubSampCloud                                            # noqa: F401
 from . import synthetic                                                      # noqa: F401

@@ -67,6 +67,7 @@ _SIGNATURES = {
     "sitrk_find_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "sitrk_seed_init": (_int, [_vp, _i64] + [_vp] * 9),
     "sitrk_nemo_seed": (_int, [_vp, _int, _int, _int] + [_vp] * 7 + [_dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_subsample_cloud": (_int, [_vp, _i64, _vp, _dbl, _vp, C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "sitrk_nearest_point": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp]),
     "sitrk_eval_haversine": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sitrk_eval_inside": (_int, [_vp, _i64, _vp, _vp, _vp]),
@@ -492,6 +493,18 @@ class Context:
         if n:
             self._chk(self._L.sitrk_nemo_seed(*args, n, _ptr(ll), _ptr(yx), C.byref(nT), C.byref(nF)))
         return ll, yx, nT.value, nF.value
+
+    def subsample_cloud(self, yx, rd_km):
+        """sitrk_subsample_cloud: (keep (n,) bool, launches) -- point i kept iff no kept j < i lies closer than rd_km
+        (squared distance < rd_km**2 in fp64, no FMA): gudhi's sparsify_point_set on yx (n,2) km in the given order."""
+        yx = as_c(yx, np.float64)
+        if yx.ndim != 2 or yx.shape[1] != 2:
+            raise ValueError("subsample_cloud: yx must be (n,2)")
+        n = yx.shape[0]
+        keep = np.zeros(n, dtype=np.int8)
+        nk, nl = _i64(0), C.c_int32(0)
+        self._chk(self._L.sitrk_subsample_cloud(self._h, n, _ptr(yx), float(rd_km), _ptr(keep), C.byref(nk), C.byref(nl)))
+        return keep.astype(bool), nl.value
 
     def nearest_point(self, latlon, latT, lonT, resolkm=None, rd_found_km=10., max_itr=5):
         """NearestPoint of the reference for an array of points: (ji (n,2) int32 with -1,-1 = not found, dmin km)."""

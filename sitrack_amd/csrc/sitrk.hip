@@ -278,6 +278,12 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
         h->patch_margin = value;
         return SITRK_OK;
     }
+    else if (!strcmp(knob, "subsample_block")) {     // points per workgroup of sitrk_subsample_cloud's resolve kernel
+        if (value < 256 || value > 256 * kSubMaxPpt || (value & (value - 1)))
+            return fail(h, SITRK_EINVAL, "sitrk_set_tuning: subsample_block must be a power of two in 256..%d", 256 * kSubMaxPpt);
+        h->subsample_block = value;
+        return SITRK_OK;
+    }
     else if (!strcmp(knob, "locate_bruteforce")) bit = TUNE_LOCATE_BRUTEFORCE;
 #ifdef SITRK_DIAG
     else if (!strcmp(knob, "stamps")) { h->stamps_on = value != 0; return SITRK_OK; }
@@ -1730,6 +1736,130 @@ SITRK_API int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t
     HIPCHK(hipMemcpyAsync(latlon, d_ll, nout * 16, hipMemcpyDeviceToHost, h->stream));
     if (yx) HIPCHK(hipMemcpyAsync(yx, d_yx, nout * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return SITRK_OK;
+}
+
+// --------------------------------------------------------------------------- seed-cloud coarsening
+// Kernels in sitrk_subsample.hip (algorithm and rules there).  Everything lives in h->scratch, which the stepping never reads.
+SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, double rd_km, int8_t *keep, int64_t *nkeep,
+                                    int32_t *launches)
+{
+    NEED(h, "null handle");
+    NEED(n >= 0 && n < ((int64_t)1 << 31) - 1, "sitrk_subsample_cloud: n must be in 0..2^31-2");
+    NEED(nkeep, "sitrk_subsample_cloud: null nkeep");
+    NEED(n == 0 || (yx && keep), "sitrk_subsample_cloud: null array");
+    if (!std::isfinite(rd_km) || !(rd_km > 0.0))
+        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: rd_km must be finite and > 0 (got %g)", rd_km);
+    *nkeep = 0;
+    if (launches) *launches = 0;
+    if (n == 0) return SITRK_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t un = (size_t)n;
+    const size_t b_pt = align256(un * sizeof(pt)), b_4 = align256(un * 4), b_1 = align256(un);
+    // the cell grid is known after the bounding box; size the scratch for the largest grid allowed (cells <= n + 1024)
+    const int64_t max_cells = n + 1024;
+    const size_t b_c = align256((size_t)max_cells * 4);
+    size_t b_sort = 0;
+    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, h->stream));
+    b_sort = align256(b_sort);
+    const int ppt = h->subsample_block / 256;
+    const int64_t nwg = (n + h->subsample_block - 1) / h->subsample_block;
+    const size_t b_red = 256, b_done = align256((size_t)nwg);
+    int rc = ensure_scratch(h, 2 * b_pt + 5 * b_4 + 3 * b_1 + 2 * b_c + b_sort + b_red + b_done);
+    if (rc) return rc;
+    char *w = (char *)h->scratch;
+    pt *d_yx = (pt *)w;                             w += b_pt;
+    pt *d_yxs = (pt *)w;                            w += b_pt;
+    uint32_t *k0 = (uint32_t *)w;                   w += b_4;
+    uint32_t *k1 = (uint32_t *)w;                   w += b_4;
+    int32_t *v0 = (int32_t *)w;                     w += b_4;
+    int32_t *perm = (int32_t *)w;                   w += b_4;
+    int32_t *cur_q = (int32_t *)w;                  w += b_4;
+    uint8_t *state = (uint8_t *)w;                  w += b_1;
+    uint8_t *cur_k = (uint8_t *)w;                  w += b_1;
+    int8_t *d_keep = (int8_t *)w;                   w += b_1;
+    int32_t *cstart = (int32_t *)w;                 w += b_c;
+    int32_t *cend = (int32_t *)w;                   w += b_c;
+    void *sort_tmp = w;                             w += b_sort;
+    unsigned long long *red = (unsigned long long *)w; w += b_red;     // [0..4] bbox + first non-finite, [5] undecided, [6] kept
+    uint8_t *done = (uint8_t *)w;
+
+    HIPCHK(hipMemcpyAsync(d_yx, yx, un * sizeof(pt), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(subsample_bbox(n, d_yx, red, h->stream));
+    unsigned long long bb[5];
+    HIPCHK(hipMemcpyAsync(bb, red, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bb[4] != ~0ull)
+        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: non-finite coordinate at index %llu", bb[4]);
+    SubGrid g;
+    g.ymin = subsample_key_to_double(bb[0]); g.xmin = subsample_key_to_double(bb[1]);
+    const double ymax = subsample_key_to_double(bb[2]), xmax = subsample_key_to_double(bb[3]);
+    // side h >= rd, padded so that the rounding of a cell coordinate ((v - v0) * inv_h, <= 2^20) can never put a pair with
+    // d2 < r2 two cells apart; doubled while the grid exceeds n + 1024 cells or 2^20 cells a side (a coarser grid is only slower)
+    double side = rd_km * (1.0 + 1.0 / 1024.0);
+    int64_t ny = 1, nx = 1;
+    for (int it = 0; it < 2100; it++) {
+        g.inv_h = 1.0 / side;
+        const double ty = (ymax - g.ymin) * g.inv_h, tx = (xmax - g.xmin) * g.inv_h;
+        if (ty < 1048576.0 && tx < 1048576.0) {
+            ny = (int64_t)std::floor(ty) + 1; nx = (int64_t)std::floor(tx) + 1;
+            if (ny * nx <= max_cells) break;
+        }
+        side *= 2.0;
+    }
+    if (ny * nx > max_cells || !(g.inv_h > 0.0)) return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: no cell grid fits the cloud's extent");
+    g.ny = (int)ny; g.nx = (int)nx;
+    const int64_t ncells = ny * nx;
+    unsigned end_bit = 1;
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)ncells) end_bit++;
+
+    // bin: key = cell, stable radix sort (index order inside a cell), sorted coordinates, cell ranges
+    HIPCHK(subsample_bin_keys(g, n, d_yx, k0, v0, h->stream));
+    size_t tb = b_sort;
+    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, h->stream));
+    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * 4, h->stream));
+    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * 4, h->stream));
+    HIPCHK(subsample_bin_gather(n, d_yx, k1, perm, d_yxs, cstart, cend, h->stream));
+    HIPCHK(hipMemsetAsync(state, 0, un, h->stream));
+    HIPCHK(hipMemsetAsync(cur_k, 0, un, h->stream));
+    HIPCHK(hipMemsetAsync(cur_q, 0xff, un * 4, h->stream));
+    HIPCHK(hipMemsetAsync(done, 0, (size_t)nwg, h->stream));
+
+    SubResolveArgs a;
+    a.g = g; a.n = n; a.r2 = rd_km * rd_km; a.ppt = ppt;
+    a.yx = d_yxs; a.perm = perm; a.cstart = cstart; a.cend = cend;
+    a.state = state; a.cur_q = cur_q; a.cur_k = cur_k; a.done = done;
+    // launches in batches; the last launch of a batch counts what it leaves undecided (an over-count at worst, and always
+    // below the previous batch's count, since every launch decides the lowest undecided point): stop at 0, give up if it stalls
+    unsigned long long prev = (unsigned long long)n + 1, und = 0;
+    int64_t nl = 0;
+    int batch = 4;
+    for (;;) {
+        for (int b = 0; b < batch; b++) {
+            a.undecided = nullptr;
+            if (b == batch - 1) {
+                HIPCHK(hipMemsetAsync(red + 5, 0, sizeof(unsigned long long), h->stream));
+                a.undecided = red + 5;
+            }
+            HIPCHK(subsample_resolve(a, h->stream));
+        }
+        nl += batch;
+        HIPCHK(hipMemcpyAsync(&und, red + 5, sizeof(und), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (und == 0) break;
+        if (und >= prev || nl > n + 64)
+            return fail(h, SITRK_EHIP, "sitrk_subsample_cloud: undecided count stalled at %llu after %lld launches", und, (long long)nl);
+        prev = und;
+        batch = std::min(2 * batch, 64);
+    }
+    HIPCHK(hipMemsetAsync(red + 6, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(subsample_emit(n, perm, state, d_keep, red + 6, h->stream));
+    unsigned long long nk = 0;
+    HIPCHK(hipMemcpyAsync(keep, d_keep, un, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&nk, red + 6, sizeof(nk), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *nkeep = (int64_t)nk;
+    if (launches) *launches = (int32_t)std::min<int64_t>(nl, INT32_MAX);
     return SITRK_OK;
 }
 

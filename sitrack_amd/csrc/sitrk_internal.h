@@ -11,6 +11,34 @@ namespace sitrk {
 hipError_t sort_pairs_u32(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uint32_t *kout,
                           const int32_t *vin, int32_t *vout, size_t n, unsigned end_bit, hipStream_t s);
 
+// Seed-cloud coarsening (sitrk_subsample.hip): cells of side 1/inv_h, ny x nx of them, from (ymin, xmin)
+struct SubGrid {
+    double ymin = 0.0, xmin = 0.0, inv_h = 0.0;
+    int ny = 1, nx = 1;
+};
+constexpr int kSubMaxPpt = 16;          // points per thread of resolve_kernel: knob subsample_block = 256 * ppt, 256..4096
+struct SubResolveArgs {
+    SubGrid g;
+    int64_t n = 0;
+    double r2 = 0.0;
+    int ppt = 4;
+    const pt *yx = nullptr;             // sorted by cell, index order inside a cell
+    const int32_t *perm = nullptr;      // perm[s] = input index of sorted point s
+    const int32_t *cstart = nullptr, *cend = nullptr;
+    uint8_t *state = nullptr;           // 0 undecided, 1 kept, 2 dropped (sorted order)
+    int32_t *cur_q = nullptr;           // pull cursor: sorted position (-1: start of the cell) ...
+    uint8_t *cur_k = nullptr;           // ... inside neighbour cell cur_k (0..8)
+    uint8_t *done = nullptr;            // per workgroup: all its points decided
+    unsigned long long *undecided = nullptr;   // optional: += points still undecided at each workgroup's exit
+};
+hipError_t subsample_bbox(int64_t n, const pt *yx, unsigned long long *red, hipStream_t s);
+double subsample_key_to_double(unsigned long long k);
+hipError_t subsample_bin_keys(const SubGrid &g, int64_t n, const pt *yx, uint32_t *key, int32_t *val, hipStream_t s);
+hipError_t subsample_bin_gather(int64_t n, const pt *yx, const uint32_t *key_sorted, const int32_t *perm, pt *yx_s, int32_t *cstart,
+                                int32_t *cend, hipStream_t s);
+hipError_t subsample_resolve(const SubResolveArgs &a, hipStream_t s);
+hipError_t subsample_emit(int64_t n, const int32_t *perm, const uint8_t *state, int8_t *keep, unsigned long long *nkeep, hipStream_t s);
+
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
 // perm[s] = index of slot s in the caller's order.
 struct BuoyState {
@@ -68,6 +96,7 @@ struct sitrk_ctx {
     int patch_kb = 16;                  // fused kernel: LDS bytes per workgroup for its geometry patch (0 = none, all reads global)
     int xcd_group = 16;                 // fused kernel: runs of that many consecutive workgroups on one XCD (0/1 = hardware order)
     int patch_margin = 8;               // ... and the widest margin of cells around the buoys' bounding box it may take
+    int subsample_block = 1024;         // sitrk_subsample_cloud: points per workgroup of its resolve kernel (never changes results)
     int fill_threads = 8;               // host threads copying a pushed record (>= 8 MB) into the pinned staging (2 / 4 / 8: 26 / 36 / 47 GB/s on the box rows of C3)
 
     // records

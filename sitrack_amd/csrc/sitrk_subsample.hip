@@ -1,0 +1,286 @@
+// sitrk_subsample.hip -- seed-cloud coarsening (sitrk_subsample_cloud): the greedy sparsification of the reference's
+// util.SubSampCloud (gudhi.subsampling.sparsify_point_set).  Point i is kept iff no kept j < i has d2(i,j) < r2, i.e.
+// the lexicographically-first maximal independent set of the graph with edges where d2 < r2.  Kept in its own
+// translation unit so that the device code of sitrk.hip stays as it is.
+//
+// Steps (driven by sitrk.hip):
+//   1. bbox_kernel      bounding box of the cloud and the first non-finite coordinate
+//   2. bin_key_kernel   square cells of side h >= rd (padded); key = cell, value = index; the rocPRIM radix sort of
+//                       sitrk_sort.hip orders the points by cell, stably, so each cell holds its points in index order
+//   3. bin_gather_kernel sorted coordinates and the [start,end) range of every cell
+//   4. resolve_kernel   the greedy result in rounds over a state array (undecided -> kept | dropped), see below
+//   5. emit_kernel      keep mask in input order and the kept count
+//
+// All state lives in sorted position order.  Every decision is final and correct on its own:
+//   - a point is dropped only when it sees a KEPT earlier neighbour (kept states are correct by induction);
+//   - a point is kept only when it has seen every earlier neighbour DROPPED;
+//   - a point that becomes kept marks its later neighbours dropped at once ("push"), cooperatively by its workgroup.
+// So the result is the unique greedy set whatever the dispatch order, timing or placement.  A workgroup re-sweeps its
+// own undecided points while it makes progress (at most kMaxSweeps times); what it reads of other workgroups' states
+// is a hint (a stale "undecided" only delays a decision).  No workgroup ever waits for another.  The lowest-index
+// undecided point at a launch's start has all its earlier neighbours decided and visible (kernel boundary), so its
+// workgroup decides it in its first sweep: every launch decides at least one point.
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sitrk_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace sitrk {
+
+namespace {
+
+constexpr int kSubThreads = 256;      // threads per workgroup of every kernel here
+constexpr int kMaxSweeps = 256;       // bound of the in-launch re-sweeps of one workgroup
+constexpr uint8_t kUndecided = 0, kKept = 1, kDropped = 2;
+
+// order-preserving map of a double to an unsigned 64-bit key (min/max by integer atomics)
+__device__ __forceinline__ unsigned long long dkey(double d)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ uint8_t state_load(const uint8_t *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void state_store(uint8_t *p, uint8_t v)
+{
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the contract's distance: two rounded products, one rounded sum, no FMA (contract(off) above and -ffp-contract=off)
+__device__ __forceinline__ double d2of(pt a, pt b)
+{
+    const double dy = a.y - b.y, dx = a.x - b.x;
+    const double yy = dy * dy, xx = dx * dx;
+    return yy + xx;
+}
+
+__device__ __forceinline__ int cell_coord(double v, double v0, double inv_h, int nc)
+{
+    const double t = (v - v0) * inv_h;               // same expression as the host's cell count: t <= nc - 1 by monotonicity
+    int c = (int)floor(t);
+    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
+}
+
+__global__ void bbox_init_kernel(unsigned long long *red)
+{
+    if (threadIdx.x < 5) red[threadIdx.x] = threadIdx.x < 2 || threadIdx.x == 4 ? ~0ull : 0ull;
+}
+
+// red[0..3] = keys of ymin, xmin, ymax, xmax (finite points); red[4] = first non-finite index (all-ones: none)
+__global__ __launch_bounds__(kSubThreads) void bbox_kernel(int64_t n, const pt *__restrict__ yx, unsigned long long *red)
+{
+    unsigned long long lo_y = ~0ull, lo_x = ~0ull, hi_y = 0, hi_x = 0, bad = ~0ull;
+    for (int64_t i = (int64_t)blockIdx.x * kSubThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kSubThreads) {
+        const pt p = yx[i];
+        if (!isfinite(p.y) || !isfinite(p.x)) {
+            bad = min(bad, (unsigned long long)i);
+            continue;
+        }
+        const unsigned long long ky = dkey(p.y), kx = dkey(p.x);
+        lo_y = min(lo_y, ky); hi_y = max(hi_y, ky);
+        lo_x = min(lo_x, kx); hi_x = max(hi_x, kx);
+    }
+    __shared__ unsigned long long sm[5][kSubThreads];
+    sm[0][threadIdx.x] = lo_y; sm[1][threadIdx.x] = lo_x; sm[2][threadIdx.x] = hi_y; sm[3][threadIdx.x] = hi_x;
+    sm[4][threadIdx.x] = bad;
+    __syncthreads();
+    for (int s = kSubThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sm[0][threadIdx.x] = min(sm[0][threadIdx.x], sm[0][threadIdx.x + s]);
+            sm[1][threadIdx.x] = min(sm[1][threadIdx.x], sm[1][threadIdx.x + s]);
+            sm[2][threadIdx.x] = max(sm[2][threadIdx.x], sm[2][threadIdx.x + s]);
+            sm[3][threadIdx.x] = max(sm[3][threadIdx.x], sm[3][threadIdx.x + s]);
+            sm[4][threadIdx.x] = min(sm[4][threadIdx.x], sm[4][threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        atomicMin(&red[0], sm[0][0]); atomicMin(&red[1], sm[1][0]);
+        atomicMax(&red[2], sm[2][0]); atomicMax(&red[3], sm[3][0]);
+        atomicMin(&red[4], sm[4][0]);
+    }
+}
+
+__global__ __launch_bounds__(kSubThreads) void bin_key_kernel(SubGrid g, int64_t n, const pt *__restrict__ yx, uint32_t *key,
+                                                             int32_t *val)
+{
+    const int64_t i = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
+    if (i >= n) return;
+    const pt p = yx[i];
+    const int cy = cell_coord(p.y, g.ymin, g.inv_h, g.ny), cx = cell_coord(p.x, g.xmin, g.inv_h, g.nx);
+    key[i] = (uint32_t)cy * (uint32_t)g.nx + (uint32_t)cx;
+    val[i] = (int32_t)i;
+}
+
+// cstart/cend zeroed by the caller: empty cells keep [0,0)
+__global__ __launch_bounds__(kSubThreads) void bin_gather_kernel(int64_t n, const pt *__restrict__ yx, const uint32_t *__restrict__ key,
+                                                                const int32_t *__restrict__ perm, pt *yx_s, int32_t *cstart,
+                                                                int32_t *cend)
+{
+    const int64_t s = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
+    if (s >= n) return;
+    yx_s[s] = yx[perm[s]];
+    const uint32_t k = key[s];
+    if (s == 0 || key[s - 1] != k) cstart[k] = (int32_t)s;
+    if (s == n - 1 || key[s + 1] != k) cend[k] = (int32_t)(s + 1);
+}
+
+// Pull: walk the earlier neighbours of sorted point p from its cursor (cell slot 0..8 of the 3x3 neighbourhood, sorted
+// position inside that cell).  The cursor only ever moves past non-neighbours and DROPPED neighbours, which are final,
+// so a point blocked behind an undecided neighbour costs one re-check per sweep.  Returns the decision (or kUndecided).
+__device__ uint8_t pull(const SubResolveArgs &a, int32_t p)
+{
+    const pt P = a.yx[p];
+    const int32_t me = a.perm[p];
+    const int cy = cell_coord(P.y, a.g.ymin, a.g.inv_h, a.g.ny), cx = cell_coord(P.x, a.g.xmin, a.g.inv_h, a.g.nx);
+    int k = a.cur_k[p];
+    int32_t q = a.cur_q[p];
+    for (; k < 9; k++, q = -1) {
+        const int yy = cy + k / 3 - 1, xx = cx + k % 3 - 1;
+        if (yy < 0 || yy >= a.g.ny || xx < 0 || xx >= a.g.nx) continue;
+        const int64_t c = (int64_t)yy * a.g.nx + xx;
+        const int32_t e = a.cend[c];
+        if (q < 0) q = a.cstart[c];
+        for (; q < e; q++) {
+            if (a.perm[q] >= me) break;              // a cell holds its points in index order: the rest are later
+            if (d2of(P, a.yx[q]) < a.r2) {
+                const uint8_t st = state_load(a.state + q);
+                if (st == kKept) return kDropped;
+                if (st == kUndecided) {
+                    a.cur_k[p] = (uint8_t)k;
+                    a.cur_q[p] = q;
+                    return kUndecided;
+                }
+            }
+        }
+    }
+    return kKept;
+}
+
+__global__ __launch_bounds__(kSubThreads) void resolve_kernel(SubResolveArgs a)
+{
+    const int wg = blockIdx.x;
+    if (a.done[wg]) return;                          // every point of this workgroup decided in an earlier launch
+    const int64_t base = (int64_t)wg * kSubThreads * a.ppt;
+    __shared__ int32_t klist[kSubThreads * kSubMaxPpt];
+    __shared__ int nk, progress, nund;
+    for (int sweep = 0; sweep < kMaxSweeps; sweep++) {
+        if (threadIdx.x == 0) { nk = 0; progress = 0; }
+        __syncthreads();
+        for (int t = 0; t < a.ppt; t++) {
+            const int64_t p = base + (int64_t)t * kSubThreads + threadIdx.x;
+            if (p >= a.n || state_load(a.state + p) != kUndecided) continue;
+            const uint8_t d = pull(a, (int32_t)p);
+            if (d == kUndecided) continue;
+            state_store(a.state + p, d);
+            if (d == kKept) klist[atomicAdd(&nk, 1)] = (int32_t)p;
+            progress = 1;
+        }
+        __syncthreads();
+        // both flags are read into registers here, between the two barriers: thread 0 resets them at the top of the next
+        // sweep with no barrier in between, so a read after the second barrier could see the reset and leave the loop alone
+        const int nkept = nk, prog = progress;
+        // push: the whole workgroup drops the later neighbours of each point it has just kept
+        for (int e = 0; e < nkept; e++) {
+            const int32_t p = klist[e];
+            const pt P = a.yx[p];
+            const int32_t me = a.perm[p];
+            const int cy = cell_coord(P.y, a.g.ymin, a.g.inv_h, a.g.ny), cx = cell_coord(P.x, a.g.xmin, a.g.inv_h, a.g.nx);
+            for (int k = 0; k < 9; k++) {
+                const int yy = cy + k / 3 - 1, xx = cx + k % 3 - 1;
+                if (yy < 0 || yy >= a.g.ny || xx < 0 || xx >= a.g.nx) continue;
+                const int64_t c = (int64_t)yy * a.g.nx + xx;
+                const int32_t e1 = a.cend[c];
+                for (int32_t q = a.cstart[c] + (int32_t)threadIdx.x; q < e1; q += kSubThreads)
+                    if (a.perm[q] > me && d2of(P, a.yx[q]) < a.r2 && state_load(a.state + q) == kUndecided)
+                        state_store(a.state + q, kDropped);
+            }
+        }
+        __syncthreads();
+        if (!prog) break;                            // uniform: every thread read the same value before the barrier
+    }
+    // what is left undecided here (an over-count at worst: another workgroup may have dropped some of these meanwhile)
+    if (threadIdx.x == 0) nund = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int t = 0; t < a.ppt; t++) {
+        const int64_t p = base + (int64_t)t * kSubThreads + threadIdx.x;
+        if (p < a.n && state_load(a.state + p) == kUndecided) mine++;
+    }
+    if (mine) atomicAdd(&nund, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (nund == 0) a.done[wg] = 1;
+        if (a.undecided && nund) atomicAdd(a.undecided, (unsigned long long)nund);
+    }
+}
+
+__global__ __launch_bounds__(kSubThreads) void emit_kernel(int64_t n, const int32_t *__restrict__ perm, const uint8_t *__restrict__ state,
+                                                          int8_t *keep, unsigned long long *nkeep)
+{
+    const int64_t s = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
+    const int kept = s < n && state[s] == kKept;
+    if (s < n) keep[perm[s]] = (int8_t)kept;
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    if (kept) atomicAdd(&cnt, 1);
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt) atomicAdd(nkeep, (unsigned long long)cnt);
+}
+
+inline unsigned nblk(int64_t n) { return (unsigned)((n + kSubThreads - 1) / kSubThreads); }
+
+}  // namespace
+
+hipError_t subsample_bbox(int64_t n, const pt *yx, unsigned long long *red, hipStream_t s)
+{
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, s, red);
+    const unsigned g = nblk(n) < 2048u ? nblk(n) : 2048u;
+    hipLaunchKernelGGL(bbox_kernel, dim3(g), dim3(kSubThreads), 0, s, n, yx, red);
+    return hipGetLastError();
+}
+
+double subsample_key_to_double(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double d;
+    memcpy(&d, &b, sizeof(d));
+    return d;
+}
+
+hipError_t subsample_bin_keys(const SubGrid &g, int64_t n, const pt *yx, uint32_t *key, int32_t *val, hipStream_t s)
+{
+    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, g, n, yx, key, val);
+    return hipGetLastError();
+}
+
+hipError_t subsample_bin_gather(int64_t n, const pt *yx, const uint32_t *key_sorted, const int32_t *perm, pt *yx_s, int32_t *cstart,
+                                int32_t *cend, hipStream_t s)
+{
+    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, n, yx, key_sorted, perm, yx_s, cstart, cend);
+    return hipGetLastError();
+}
+
+hipError_t subsample_resolve(const SubResolveArgs &a, hipStream_t s)
+{
+    const int64_t per_wg = (int64_t)kSubThreads * a.ppt;
+    const unsigned g = (unsigned)((a.n + per_wg - 1) / per_wg);
+    hipLaunchKernelGGL(resolve_kernel, dim3(g), dim3(kSubThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t subsample_emit(int64_t n, const int32_t *perm, const uint8_t *state, int8_t *keep, unsigned long long *nkeep, hipStream_t s)
+{
+    hipLaunchKernelGGL(emit_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, n, perm, state, keep, nkeep);
+    return hipGetLastError();
+}
+
+}  // namespace sitrk

@@ -1,5 +1,6 @@
 """Idealised seeding on the model grid -- the surface of the reference's seeding generators (`nemoSeed`, `SidfexSeeding`,
-`ReadFromSidfexDatFile`; sitrack/tracking.py:331-442) as used by tools/generate_idealized_seeding.py.
+`ReadFromSidfexDatFile`; sitrack/tracking.py:331-442) and of the coarsening it applies (`SubSampCloud`, util.py:345-370) as
+used by tools/generate_idealized_seeding.py.
 
 `nemoSeed` runs on the GPU (`sitrk_nemo_seed`, sitrack_amd/csrc/sitrk_seed.h): the decision which points of the sub-sampled
 mesh carry a seed, their compaction in the reference's output order and their projection to the polar-stereographic plane
@@ -40,3 +41,23 @@ def SidfexSeeding(filepath='./sidfexloc.dat'):
     """Reference sitrack/tracking.py:331-341 -> (n,2) [lat,lon] and the buoy IDs (int)."""
     dat = ReadFromSidfexDatFile(filepath)
     return dat[:, [2, 1]], dat[:, 0].astype(int)
+
+
+def SubSampCloud(rd_km, pCoor, *, ctx=None):
+    """Reference sitrack/util.py:345-370, same positional parameters and return tuple (Nb, zCoor, idxleft): the points of
+    `pCoor` (n,2) -- the seeds' polar-stereographic [y,x] km -- kept by the greedy sparsification of
+    gudhi.subsampling.sparsify_point_set(pCoor, min_squared_dist=rd_km**2), in input order.  Runs on the GPU
+    (`sitrk_subsample_cloud`, sitrack_amd/csrc/sitrk_subsample.hip).  Raises ValueError where the reference prints and
+    exits.  One deliberate deviation: the reference recovers `idxleft` with np.where(pCoor == zCoor[i]), which matches a
+    row where EITHER coordinate is equal and can return an earlier, dropped point; here `idxleft` is the true index of
+    each kept point, so zCoor == pCoor[idxleft] row by row."""
+    from .tracking import default_context
+    cerr = 'ERROR [SubSampCloud()]: '
+    if not rd_km > 0. or rd_km > 2000:
+        raise ValueError(cerr + 'silly value for `rd_km`: %r' % (rd_km,))
+    pCoor = np.asarray(pCoor, dtype=np.float64)
+    if pCoor.ndim != 2 or pCoor.shape[1] != 2:
+        raise ValueError(cerr + 'second dimension of `pCoor` must be 2 !')
+    keep, _ = (ctx or default_context()).subsample_cloud(pCoor, rd_km)
+    idxleft = np.flatnonzero(keep)
+    return len(idxleft), pCoor[idxleft, :].copy(), idxleft

@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Seeding file on the model grid -- the flags of the reference tools generate_idealized_seeding.py /
-generate_sidfex_seeding.py (-d -m -i -v -k -S -f -N, --lsidfex) minus the coarsening path (-C needs
-`gudhi`/`mojito`).  Writes ./nc/sitrack_seeding_<nemoTsi3|nemoTmm|sidfex>_<YYYYMMDD_hh>[_HSS<S>].nc with the schema
-of reference ncio.py:131-197.  `--lsidfex 1` seeds from a text file `id lon lat` (reference tools/sidfexloc.dat)."""
+generate_sidfex_seeding.py (-d -m -i -v -k -S -f -C -N, --lsidfex).  Writes
+./nc/sitrack_seeding_<nemoTsi3|nemoTmm|sidfex>_<YYYYMMDD_hh>[_HSS<S>|_<C>km].nc with the schema of reference
+ncio.py:131-197.  `--lsidfex 1` seeds from a text file `id lon lat` (reference tools/sidfexloc.dat).
+
+`-C <C>` coarsens the seed cloud to a spacing of about C km (reference :158-186, :323-360): the seeds' [y,x] km go through
+`SubSampCloud` (greedy sparsification at radius rd_ss, on the GPU) and the kept rows keep their IDs, lat/lon and y/x;
+C = 10 and 20 add the mesh's F-points to the T-seeds first.  rd_ss = 6.0 / 14.6 / 34.5 / 74.75 / 156. / 315.6 km for
+C = 10 / 20 / 40 / 80 / 160 / 320.  C = 640 also needs the reference's dist-to-coast file and mojito's `MaskCoastal`, and is
+refused; so is any other value.  A SIDFEx cloud is coarsened the same way, without F-points."""
 import argparse
 import os
 import sys
@@ -28,22 +34,25 @@ def main(argv=None):
     ap.add_argument('-k', '--krec', type=int, default=0, help='use sea-ice concentration at this record')
     ap.add_argument('-S', '--ihss', type=int, default=1, help='horizontal subsampling factor to apply')
     ap.add_argument('-f', '--fmsk', default=None, help='mask (on SI3 model domain) to control seeding region')
-    ap.add_argument('-C', '--crsn', type=int, default=0, help='coarsening in km (not supported here)')
+    ap.add_argument('-C', '--crsn', type=int, default=0, help='coarsening in km: 10, 20, 40, 80, 160 or 320')
     ap.add_argument('-N', '--ncnf', default='NANUK4', help='name of the horizontak NEMO config used')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
-    if a.crsn >= 1:
-        raise SystemExit('-C/--crsn needs the gudhi-based SubSampCloud of `mojito`: out of scope of this build')
+    rd_ss, add_f = coarsening(a.crsn)
     if a.ihss < 1 or a.ihss > 20:
         raise SystemExit('ERROR: chosen horizontal subsampling makes no sense iHSS=%d' % a.ihss)
     seeding_type = 'sidfex' if a.lsidfex == 1 else ('nemoTsi3' if a.fsi3 else 'nemoTmm')
     ctx = sit.Context(a.device)
     if seeding_type == 'sidfex':
         XseedGC, zIDs = SidfexSeeding(a.sidfex_file)
-        return write_seeding(ctx, a, seeding_type, XseedGC, zIDs)
+        return write_seeding(ctx, a, seeding_type, XseedGC, zIDs, rd_ss=rd_ss)
     if not a.fmmm:
         raise SystemExit('ERROR: you have to specify a MeshMask file with `-m`')
-    imaskt, xlatT, xlonT, xYt, xXt, xYf, xXf, xResKM = ncio.GetModelGrid(a.fmmm, ctx=ctx)
+    if add_f:
+        imaskt, xlatT, xlonT, xYt, xXt, xYf, xXf, xResKM, _, xlatF, xlonF = ncio.GetModelGrid(a.fmmm, alsoF=True, ctx=ctx)
+    else:
+        imaskt, xlatT, xlonT, xYt, xXt, xYf, xXf, xResKM = ncio.GetModelGrid(a.fmmm, ctx=ctx)
+        xlatF, xlonF = [], []
     if a.fsi3:
         rec = ncio.ModelRecords(a.fsi3)
         (xIC,) = rec.fields(a.krec, (a.nsic,))
@@ -59,18 +68,44 @@ def main(argv=None):
         if np.shape(FSmask) != np.shape(imaskt):
             raise SystemExit('ERROR: `shape(FSmask) != shape(imaskt)`')
     # which points carry a seed, their order and their projection: one call into the library (sitrk_nemo_seed)
-    XseedGC, XseedYX = nemoSeed(imaskt, xlatT, xlonT, xIC, khss=a.ihss, fmsk_rstrct=FSmask, ctx=ctx, return_yx=True)
+    XseedGC, XseedYX = nemoSeed(imaskt, xlatT, xlonT, xIC, khss=a.ihss, fmsk_rstrct=FSmask, platF=xlatF, plonF=xlonF,
+                                ctx=ctx, return_yx=True)
     zIDs = np.arange(1, XseedGC.shape[0] + 1, dtype=int)
-    return write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX)
+    return write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX, rd_ss)
 
 
-def write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX=None):
-    nP = XseedGC.shape[0]
+# -C <km> -> (rd_ss km, add F-points): reference :158-186
+RD_SS = {10: (6.0, True), 20: (14.6, True), 40: (34.5, False), 80: (74.75, False), 160: (156., False), 320: (315.6, False)}
+
+
+def coarsening(icrsn):
+    """(rd_ss, add F-points) for `-C icrsn`, (None, False) without coarsening; SystemExit for what cannot be done."""
+    if icrsn < 1:
+        return None, False
+    if icrsn == 640:
+        raise SystemExit('ERROR: -C 640 also removes seeds near the coast: it needs the dist-to-coast file '
+                         '$DATA_DIR/data/dist2coast/dist2coast_4deg_North.nc and mojito\'s `MaskCoastal`, which this build does not have')
+    if icrsn not in RD_SS:
+        raise SystemExit('ERROR: we do not know what `rd_ss` to pick for `icrsn` = %d (known: %s)' %
+                         (icrsn, ', '.join(str(k) for k in sorted(RD_SS))))
+    return RD_SS[icrsn]
+
+
+def write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX=None, rd_ss=None):
     t0 = driver.clock2epoch(a.dat0)
     if XseedYX is None:
         XseedYX = sit.Geo2CartNPSkm1D(XseedGC, ctx=ctx)
     cdate = datetime.fromtimestamp(t0, timezone.utc).strftime("%Y%m%d_%H")
     cextra = '_HSS' + str(a.ihss) if a.ihss > 1 else ''
+    if rd_ss is not None:
+        nP0 = XseedGC.shape[0]
+        print(' *** Applying spatial sub-sampling with radius: %.2fkm' % rd_ss)
+        _, XseedYX, idxKeep = sit.SubSampCloud(rd_ss, XseedYX, ctx=ctx)
+        XseedGC = XseedGC[idxKeep, :]
+        zIDs = np.asarray(zIDs)[idxKeep]
+        print('    ==> nP, nPss = %d %d' % (nP0, len(idxKeep)))
+        cextra = '_%dkm' % a.crsn
+    nP = XseedGC.shape[0]
     foutnc = './nc/sitrack_seeding_' + seeding_type + '_' + cdate + cextra + '.nc'
     ncio.ncSaveCloudBuoys(foutnc, np.array([t0], dtype='i4'), zIDs, XseedYX[None, :, 0], XseedYX[None, :, 1],
                           XseedGC[None, :, 0], XseedGC[None, :, 1], corigin='idealized_seeding', cauthor='generate_idealized_seeding.py')
