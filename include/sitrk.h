@@ -290,6 +290,33 @@ int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t *tmask, c
  * <= 0, when a coordinate is not finite (the first such index is named in sitrk_last_error) or a pointer is missing. */
 int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, double rd_km, int8_t *keep, int64_t *nkeep, int32_t *launches);
 
+/* ---- overlap cleaning of a tracked cloud ---------------------------------------
+ * CancelTooClose (sitrack/util.py:520-565) at one record krec: n buoys at lat/lon (degrees, the record's positions), valid[b]
+ * = pmsk[krec,b] != 0 (NULL: every buoy valid), nrec_all[b] = sum_t pmsk[t,b], nrec_before[b] = sum_{t<krec} pmsk[t,b].
+ * Contract: d(j,k) = the reference Haversine(lat[j], lon[j], lat[k], lon[k]) (util.py:85-103, R = 6360 km, its operation
+ * order); nn[j] = the valid k != j of smallest d(j,k), lowest index on ties, dmin[j] = that distance.  The reference's scan
+ * (util.py:536-556) then runs over j in index order: if j is still alive and dmin[j] < rd_km, the one of j and nn[j] with
+ * the smaller count goes (on equal counts nn[j]), where the count of a buoy already dropped is nrec_before (its records >= krec
+ * were zeroed) and that of a live one nrec_all.  Distances are measured to dropped buoys too.  Every pass of the reference
+ * starts afresh, so NbPass >= 1 does not change the result and this runs it once.  keep[b] = 1 for the buoys kept (valid and
+ * not dropped), *nkeep their number, *nclose (may be NULL) the number of valid buoys with dmin < rd_km.
+ * Extension (the reference raises IndexError there): a buoy with valid[b] == 0 takes no part -- never examined, nobody's
+ * neighbour, not kept; with every buoy valid the result is the reference's.  The device sin/cos/asin may differ from numpy's
+ * in the last ulp (the convention of sitrk_eval_haversine), so a dmin within ~1e-12 relative of rd_km, or two distinct
+ * distances within ~1e-12 of each other, are unpinned; exact duplicates (distance 0) are exact.
+ * Host arrays, synchronous on the handle's stream; n == 0 is valid.  Uses the context's transient scratch only (never read by
+ * the stepping): the grid, buoys and records of a tracker on the same handle are left as they were.  SITRK_EINVAL when rd_km is
+ * not finite or outside (0, 9999] (above 9999 the reference's self-mask would win), when a coordinate of a valid buoy is not
+ * finite (the first such index is named in sitrk_last_error) or a pointer is missing. */
+int sitrk_cancel_too_close(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid, const int32_t *nrec_all,
+                           const int32_t *nrec_before, double rd_km, int8_t *keep, int64_t *nkeep, int64_t *nclose);
+
+/* Probe of the first stage of sitrk_cancel_too_close: for every valid buoy j, nn[j] and dmin[j] as defined there when
+ * dmin[j] < rd_km, else nn[j] = -1 and dmin[j] = +inf (also for the buoys with valid[j] == 0).  Same arguments, limits and
+ * errors as sitrk_cancel_too_close. */
+int sitrk_nearest_buoy(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid, double rd_km, int32_t *nn,
+                       double *dmin);
+
 /* ---- predicate probes ------------------------------------------------------
  * The device-side predicates of the hot path evaluated on plain arrays, so that each one can be held
  * against the reference function it restates (parity tests):

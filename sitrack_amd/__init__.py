@@ -12,4 +12,5 @@ from .predicates import (_ccw_, intersect2Seg, IsInsideQuadrangle, CrossedEdge, 
 from .ncio import (GetModelGrid, GetModelUVGrid, LoadNCtime, LoadNCdata, SeedFileTimeInfo, ModelFileTimeInfo,  # noqa: F401
                    ncSaveCloudBuoys, chck4f)
 from .seeding import SubSampCloud                                            # noqa: F401
+from .overlap import CancelTooClose                                          # noqa: F401
 from . import synthetic                                                      # noqa: F401

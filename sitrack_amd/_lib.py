@@ -68,6 +68,8 @@ _SIGNATURES = {
     "sitrk_seed_init": (_int, [_vp, _i64] + [_vp] * 9),
     "sitrk_nemo_seed": (_int, [_vp, _int, _int, _int] + [_vp] * 7 + [_dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_subsample_cloud": (_int, [_vp, _i64, _vp, _dbl, _vp, C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    "sitrk_cancel_too_close": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_nearest_buoy": (_int, [_vp, _i64, _vp, _vp, _vp, _dbl, _vp, _vp]),
     "sitrk_nearest_point": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp]),
     "sitrk_eval_haversine": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sitrk_eval_inside": (_int, [_vp, _i64, _vp, _vp, _vp]),
@@ -505,6 +507,38 @@ class Context:
         nk, nl = _i64(0), C.c_int32(0)
         self._chk(self._L.sitrk_subsample_cloud(self._h, n, _ptr(yx), float(rd_km), _ptr(keep), C.byref(nk), C.byref(nl)))
         return keep.astype(bool), nl.value
+
+    def _cloud_args(self, lat, lon, valid, name):
+        lat = as_c(lat, np.float64)
+        lon = as_c(lon, np.float64)
+        if lat.ndim != 1 or lon.shape != lat.shape:
+            raise ValueError("%s: lat and lon must be 1-D of one length" % name)
+        if valid is not None:
+            valid = as_c(np.asarray(valid) != 0, np.int8, lat.shape, name + ": valid")
+        return lat, lon, valid
+
+    def nearest_buoy(self, lat, lon, valid=None, rd_km=1.0):
+        """sitrk_nearest_buoy: (nn (n,) int64, dmin (n,) km) -- the nearest other valid buoy by the reference Haversine
+        (lowest index on ties) when it lies closer than rd_km, else -1 and +inf."""
+        lat, lon, valid = self._cloud_args(lat, lon, valid, "nearest_buoy")
+        n = lat.shape[0]
+        nn = np.empty(n, dtype=np.int32)
+        dmin = np.empty(n, dtype=np.float64)
+        self._chk(self._L.sitrk_nearest_buoy(self._h, n, _ptr(lat), _ptr(lon), _ptr(valid), float(rd_km), _ptr(nn), _ptr(dmin)))
+        return nn.astype(np.int64), dmin
+
+    def cancel_too_close(self, lat, lon, valid, nrec_all, nrec_before, rd_km):
+        """sitrk_cancel_too_close: (keep (n,) bool, nclose) -- the buoys CancelTooClose keeps at one record, given its
+        positions, validity (None: all valid) and the per-buoy counts of valid records in all / before that record."""
+        lat, lon, valid = self._cloud_args(lat, lon, valid, "cancel_too_close")
+        n = lat.shape[0]
+        nall = as_c(nrec_all, np.int32, (n,), "cancel_too_close: nrec_all")
+        nbef = as_c(nrec_before, np.int32, (n,), "cancel_too_close: nrec_before")
+        keep = np.zeros(n, dtype=np.int8)
+        nk, nc = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_cancel_too_close(self._h, n, _ptr(lat), _ptr(lon), _ptr(valid), _ptr(nall), _ptr(nbef),
+                                                 float(rd_km), _ptr(keep), C.byref(nk), C.byref(nc)))
+        return keep.astype(bool), nc.value
 
     def nearest_point(self, latlon, latT, lonT, resolkm=None, rd_found_km=10., max_itr=5):
         """NearestPoint of the reference for an array of points: (ji (n,2) int32 with -1,-1 = not found, dmin km)."""

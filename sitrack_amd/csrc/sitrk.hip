@@ -1863,6 +1863,188 @@ SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, dou
     return SITRK_OK;
 }
 
+// --------------------------------------------------------------------------- overlap cleaning of a tracked cloud
+// Kernels in sitrk_overlap.hip (algorithm there, bounds in DESIGN.md section 3.6).  Everything lives in h->scratch, which the
+// stepping never reads.  Stage 1 leaves, in input order, nn (nearest other valid buoy with Haversine < rd_km, else -1) and dmin.
+struct OverlapScratch {
+    int32_t *nn = nullptr, *flag = nullptr, *pos = nullptr, *cidx = nullptr, *cnn = nullptr;
+    double *dmin = nullptr;
+    void *scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    unsigned long long *red = nullptr;
+};
+
+static int overlap_stage1(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, const int8_t *valid,
+                          double rd_km, OverlapScratch &o)
+{
+    HIPCHK(hipSetDevice(h->device));
+    const size_t un = (size_t)n;
+    const size_t b_8 = align256(un * 8), b_4 = align256(un * 4), b_1 = align256(un);
+    const size_t b_v3 = align256(un * sizeof(V3)), b_ll = align256(un * sizeof(ll));
+    const int64_t max_cells = n + 1024;                 // the grid is known after the bounding box: size for the largest allowed
+    const size_t b_c = align256((size_t)max_cells * 4);
+    size_t b_sort = 0, b_scan = 0;
+    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, h->stream));
+    HIPCHK(overlap_compact(nullptr, &b_scan, n, nullptr, nullptr, nullptr, nullptr, nullptr, h->stream));
+    b_sort = align256(b_sort);
+    b_scan = align256(b_scan);
+    const size_t b_red = 256;
+    int rc = ensure_scratch(h, 3 * b_8 + b_1 + 9 * b_4 + b_v3 + b_ll + 2 * b_c + b_sort + b_scan + b_red);
+    if (rc) return rc;
+    char *w = (char *)h->scratch;
+    double *d_lat = (double *)w;                    w += b_8;
+    double *d_lon = (double *)w;                    w += b_8;
+    o.dmin = (double *)w;                           w += b_8;
+    int8_t *d_valid = (int8_t *)w;                  w += b_1;
+    uint32_t *k0 = (uint32_t *)w;                   w += b_4;
+    uint32_t *k1 = (uint32_t *)w;                   w += b_4;
+    int32_t *v0 = (int32_t *)w;                     w += b_4;
+    int32_t *perm = (int32_t *)w;                   w += b_4;
+    o.nn = (int32_t *)w;                            w += b_4;
+    o.flag = (int32_t *)w;                          w += b_4;
+    o.pos = (int32_t *)w;                           w += b_4;
+    o.cidx = (int32_t *)w;                          w += b_4;
+    o.cnn = (int32_t *)w;                           w += b_4;
+    V3 *uv_s = (V3 *)w;                             w += b_v3;
+    ll *ll_s = (ll *)w;                             w += b_ll;
+    int32_t *cstart = (int32_t *)w;                 w += b_c;
+    int32_t *cend = (int32_t *)w;                   w += b_c;
+    void *sort_tmp = w;                             w += b_sort;
+    o.scan_tmp = w;                                 w += b_scan;
+    o.scan_bytes = b_scan;
+    o.red = (unsigned long long *)w;                // [0..5] bbox keys, [6] first non-finite valid index, [7] valid count
+
+    HIPCHK(hipMemcpyAsync(d_lat, lat, un * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_lon, lon, un * 8, hipMemcpyHostToDevice, h->stream));
+    if (valid) HIPCHK(hipMemcpyAsync(d_valid, valid, un, hipMemcpyHostToDevice, h->stream));
+    const int8_t *dv = valid ? d_valid : nullptr;
+    HIPCHK(overlap_bbox(n, d_lat, d_lon, dv, o.red, h->stream));
+    unsigned long long bb[8];
+    HIPCHK(hipMemcpyAsync(bb, o.red, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bb[6] != ~0ull) return fail(h, SITRK_EINVAL, "%s: non-finite coordinate of valid buoy at index %llu", fn, bb[6]);
+    OvGrid g;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    if (bb[7]) {
+        for (int c = 0; c < 3; c++) { lo[c] = subsample_key_to_double(bb[c]); hi[c] = subsample_key_to_double(bb[3 + c]); }
+    }
+    g.x0 = lo[0]; g.y0 = lo[1]; g.z0 = lo[2];
+    // chord of rd (rd <= 9999 km: half-angle <= 0.79 rad, sin increasing); side h >= that chord, padded so that neither the
+    // rounding of the Haversine (~1e-15 relative) nor that of the unit vectors (~1e-16) nor that of a cell coordinate
+    // ((v - v0) * inv_h, < 2^20) can put a pair with Haversine < rd two cells apart; doubled while the grid exceeds n + 1024
+    // cells or 2^20 cells a side (a coarser grid is only slower)
+    const double chord = 2.0 * std::sin(rd_km / (2.0 * 6360.0));
+    const double cut = chord * (1.0 + 1.0 / 1024.0) + 1e-12;
+    double side = cut;
+    int64_t ncell[3] = {1, 1, 1};
+    bool ok = false;
+    for (int it = 0; it < 2100 && !ok; it++) {
+        g.inv_h = 1.0 / side;
+        ok = true;
+        for (int c = 0; c < 3 && ok; c++) {
+            const double t = (hi[c] - lo[c]) * g.inv_h;
+            if (!(t < 1048576.0)) ok = false;
+            else ncell[c] = (int64_t)std::floor(t) + 1;
+        }
+        if (ok && ncell[0] * ncell[1] * ncell[2] > max_cells) ok = false;
+        if (!ok) side *= 2.0;
+    }
+    if (!ok || !(g.inv_h > 0.0)) return fail(h, SITRK_EINVAL, "%s: no cell grid fits the cloud's extent", fn);
+    g.nx = (int)ncell[0]; g.ny = (int)ncell[1]; g.nz = (int)ncell[2];
+    const int64_t ncells = ncell[0] * ncell[1] * ncell[2];
+    g.ncells = (uint32_t)ncells;
+    unsigned end_bit = 1;                               // keys 0..ncells (ncells: invalid buoys)
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)ncells) end_bit++;
+
+    HIPCHK(overlap_bin_keys(g, n, d_lat, d_lon, dv, k0, v0, h->stream));
+    size_t tb = b_sort;
+    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, h->stream));
+    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * 4, h->stream));
+    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * 4, h->stream));
+    HIPCHK(overlap_bin_gather(g, n, d_lat, d_lon, k1, perm, uv_s, ll_s, cstart, cend, h->stream));
+    HIPCHK(overlap_nearest(g, n, rd_km, cut * cut, k1, perm, uv_s, ll_s, cstart, cend, o.nn, o.dmin, h->stream));
+    return SITRK_OK;
+}
+
+static int overlap_check(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, double rd_km)
+{
+    NEED(h, "null handle");
+    if (!(n >= 0 && n < ((int64_t)1 << 31) - 1)) return fail(h, SITRK_EINVAL, "%s: n must be in 0..2^31-2", fn);
+    if (n > 0 && !(lat && lon)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    if (!std::isfinite(rd_km) || !(rd_km > 0.0) || rd_km > 9999.0)
+        return fail(h, SITRK_EINVAL, "%s: rd_km must be finite and in (0, 9999] (got %g)", fn, rd_km);
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_nearest_buoy(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid, double rd_km,
+                                 int32_t *nn, double *dmin)
+{
+    const char *fn = "sitrk_nearest_buoy";
+    int rc = overlap_check(h, fn, n, lat, lon, rd_km);
+    if (rc) return rc;
+    if (n > 0 && !(nn && dmin)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    if (n == 0) return SITRK_OK;
+    OverlapScratch o;
+    rc = overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(nn, o.nn, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(dmin, o.dmin, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_cancel_too_close(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid,
+                                     const int32_t *nrec_all, const int32_t *nrec_before, double rd_km, int8_t *keep, int64_t *nkeep,
+                                     int64_t *nclose)
+{
+    const char *fn = "sitrk_cancel_too_close";
+    int rc = overlap_check(h, fn, n, lat, lon, rd_km);
+    if (rc) return rc;
+    if (!nkeep) return fail(h, SITRK_EINVAL, "%s: null nkeep", fn);
+    if (n > 0 && !(nrec_all && nrec_before && keep)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    *nkeep = 0;
+    if (nclose) *nclose = 0;
+    if (n == 0) return SITRK_OK;
+    OverlapScratch o;
+    rc = overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o);
+    if (rc) return rc;
+    // stage 2: the close set (dmin < rd) in index order, neighbours as positions in it
+    size_t tb = o.scan_bytes;
+    HIPCHK(overlap_compact(o.scan_tmp, &tb, n, o.nn, o.flag, o.pos, o.cidx, o.cnn, h->stream));
+    int32_t last[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&last[0], o.pos + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&last[1], o.flag + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t m = (int64_t)last[0] + last[1];
+    std::vector<int32_t> cidx((size_t)m), cnn((size_t)m);
+    if (m) {
+        HIPCHK(hipMemcpyAsync(cidx.data(), o.cidx, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(cnn.data(), o.cnn, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    // stage 3: the reference's scan (util.py:536-556) over the close set in index order; a buoy dropped at krec loses its
+    // records >= krec (zmsk[krec:,j2c] = 0), so its count becomes nrec_before; on equal counts the neighbour goes
+    std::vector<uint8_t> dead((size_t)m, 0);
+    for (int64_t p = 0; p < m; p++) {
+        if (dead[p]) continue;
+        const int32_t q = cnn[p];
+        if (q < 0 || q >= m) return fail(h, SITRK_EHIP, "%s: nearest neighbour of buoy %d outside the close set", fn, cidx[p]);
+        const int32_t i = cidx[p], k = cidx[q];
+        const int64_t ci = nrec_all[i], ck = dead[q] ? nrec_before[k] : nrec_all[k];
+        dead[ci < ck ? p : q] = 1;
+    }
+    int64_t nk = 0;
+    for (int64_t i = 0; i < n; i++) {
+        keep[i] = (valid == nullptr || valid[i] != 0) ? 1 : 0;
+    }
+    for (int64_t p = 0; p < m; p++)
+        if (dead[p]) keep[cidx[p]] = 0;
+    for (int64_t i = 0; i < n; i++) nk += keep[i];
+    *nkeep = nk;
+    if (nclose) *nclose = m;
+    return SITRK_OK;
+}
+
 // --------------------------------------------------------------------------- measurement
 SITRK_API int sitrk_timer_start(sitrk_t *h)
 {

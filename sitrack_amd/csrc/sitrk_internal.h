@@ -39,6 +39,25 @@ hipError_t subsample_bin_gather(int64_t n, const pt *yx, const uint32_t *key_sor
 hipError_t subsample_resolve(const SubResolveArgs &a, hipStream_t s);
 hipError_t subsample_emit(int64_t n, const int32_t *perm, const uint8_t *state, int8_t *keep, unsigned long long *nkeep, hipStream_t s);
 
+// Overlap cleaning of a tracked cloud (sitrk_overlap.hip): cubic cells of side 1/inv_h over the unit vectors' bounding box,
+// nx x ny x nz of them from (x0, y0, z0); key = (cz * ny + cy) * nx + cx, ncells = nx * ny * nz (the key of an invalid buoy)
+struct __attribute__((aligned(16))) V3 { double x, y, z, w; };
+struct OvGrid {
+    double x0 = 0.0, y0 = 0.0, z0 = 0.0, inv_h = 0.0;
+    int nx = 1, ny = 1, nz = 1;
+    uint32_t ncells = 1;
+};
+hipError_t overlap_bbox(int64_t n, const double *lat, const double *lon, const int8_t *valid, unsigned long long *red, hipStream_t s);
+hipError_t overlap_bin_keys(const OvGrid &g, int64_t n, const double *lat, const double *lon, const int8_t *valid, uint32_t *key,
+                            int32_t *val, hipStream_t s);
+hipError_t overlap_bin_gather(const OvGrid &g, int64_t n, const double *lat, const double *lon, const uint32_t *key_sorted,
+                              const int32_t *perm, V3 *uv_s, ll *ll_s, int32_t *cstart, int32_t *cend, hipStream_t s);
+hipError_t overlap_nearest(const OvGrid &g, int64_t n, double rd_km, double cut2, const uint32_t *key_sorted, const int32_t *perm,
+                           const V3 *uv_s, const ll *ll_s, const int32_t *cstart, const int32_t *cend, int32_t *nn, double *dmin,
+                           hipStream_t s);
+hipError_t overlap_compact(void *tmp, size_t *tmp_bytes, int64_t n, const int32_t *nn, int32_t *flag, int32_t *pos, int32_t *cidx,
+                           int32_t *cnn, hipStream_t s);
+
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
 // perm[s] = index of slot s in the caller's order.
 struct BuoyState {

@@ -1,0 +1,281 @@
+// sitrk_overlap.hip -- overlap cleaning of a tracked cloud (sitrk_cancel_too_close, sitrk_nearest_buoy): the reference's
+// util.CancelTooClose (sitrack/util.py:520-565).  Kept in its own translation unit so that the device code of sitrk.hip
+// stays as it is.
+//
+// Stage 1 (nearest other valid buoy within rd, per valid buoy), driven by sitrk.hip:
+//   1. unit_bbox_kernel  bounding box of the valid buoys' unit vectors and the first valid index with a non-finite coordinate
+//   2. bin_key_kernel    cubic cells of side h >= chord(rd) (padded) over that box; key = cell (invalid buoys: ncells, sorted
+//                        last); the rocPRIM radix sort of sitrk_sort.hip orders the buoys by cell
+//   3. bin_gather_kernel sorted unit vectors and [lat,lon], and the [start,end) range of every cell
+//   4. nearest_kernel    one thread per sorted buoy over the 27 neighbouring cells: pass 1 takes the minimum chord^2, pass 2
+//                        evaluates the reference Haversine only on the candidates within the margin of that minimum and keeps
+//                        the smallest distance, lowest index on ties (the bound is in DESIGN.md section 3.6)
+// Stage 2 (close set, dmin < rd, in index order): flag_kernel, the rocPRIM exclusive scan below, close_scatter_kernel, with the
+// neighbour remapped to its position in the compact list.  Stage 3, the sequential scan of the reference, runs on the host.
+#include <cmath>
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <stdint.h>
+
+#include "sitrk_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace sitrk {
+
+namespace {
+
+constexpr int kOvThreads = 256;
+
+__device__ __forceinline__ unsigned long long dkey(double d)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ V3 unit_vec(double lat, double lon)
+{
+    const double to_rad = 3.141592653589793 / 180.;
+    double sl, cl, sp, cp;
+    sincos(lon * to_rad, &sl, &cl);
+    sincos(lat * to_rad, &sp, &cp);
+    V3 v;
+    v.x = cp * cl; v.y = cp * sl; v.z = sp; v.w = 0.0;
+    return v;
+}
+
+// squared chord between two unit vectors: three rounded products, two rounded sums, no FMA
+__device__ __forceinline__ double chord2(V3 a, V3 b)
+{
+    const double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return (xx + yy) + zz;
+}
+
+// Haversine   reference sitrack/util.py:85-103 (R = 6360 km), the operation order of sitrk_kernels.h's haversine: plat is the
+// buoy the distances are measured from (the reference's Haversine(zlat[jb], zlon[jb], zlat, zlon)), cos_plat = cos(plat*to_rad)
+__device__ __forceinline__ double haversine(double plat, double plon, double cos_plat, double xlat, double xlon)
+{
+    const double to_rad = 3.141592653589793 / 180.;
+    const double R = 6360.;
+    double a1 = sin(0.5 * ((xlat - plat) * to_rad));
+    double a2 = sin(0.5 * ((xlon - plon) * to_rad));
+    double a3 = cos(xlat * to_rad) * cos_plat;
+    return 2. * R * asin(sqrt(a1 * a1 + a3 * a2 * a2));
+}
+
+__device__ __forceinline__ int cell_coord(double v, double v0, double inv_h, int nc)
+{
+    const double t = (v - v0) * inv_h;               // same expression as the host's cell count: t <= nc - 1 by monotonicity
+    int c = (int)floor(t);
+    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
+}
+
+__device__ __forceinline__ bool is_valid(const int8_t *valid, int64_t i) { return valid == nullptr || valid[i] != 0; }
+
+__global__ void bbox_init_kernel(unsigned long long *red)
+{
+    if (threadIdx.x < 8) red[threadIdx.x] = (threadIdx.x < 3 || threadIdx.x == 6) ? ~0ull : 0ull;
+}
+
+// red[0..2] = keys of xmin, ymin, zmin; red[3..5] = keys of xmax, ymax, zmax (valid finite buoys); red[6] = first valid index with
+// a non-finite coordinate (all-ones: none); red[7] = number of valid buoys
+__global__ __launch_bounds__(kOvThreads) void unit_bbox_kernel(int64_t n, const double *__restrict__ lat, const double *__restrict__ lon,
+                                                              const int8_t *__restrict__ valid, unsigned long long *red)
+{
+    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0}, bad = ~0ull, cnt = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kOvThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kOvThreads) {
+        if (!is_valid(valid, i)) continue;
+        const double la = lat[i], lo_ = lon[i];
+        if (!isfinite(la) || !isfinite(lo_)) {
+            bad = min(bad, (unsigned long long)i);
+            continue;
+        }
+        cnt++;
+        const V3 v = unit_vec(la, lo_);
+        const unsigned long long k[3] = {dkey(v.x), dkey(v.y), dkey(v.z)};
+        for (int c = 0; c < 3; c++) { lo[c] = min(lo[c], k[c]); hi[c] = max(hi[c], k[c]); }
+    }
+    __shared__ unsigned long long sm[8][kOvThreads];
+    for (int c = 0; c < 3; c++) { sm[c][threadIdx.x] = lo[c]; sm[3 + c][threadIdx.x] = hi[c]; }
+    sm[6][threadIdx.x] = bad;
+    sm[7][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = kOvThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            for (int c = 0; c < 3; c++) {
+                sm[c][threadIdx.x] = min(sm[c][threadIdx.x], sm[c][threadIdx.x + s]);
+                sm[3 + c][threadIdx.x] = max(sm[3 + c][threadIdx.x], sm[3 + c][threadIdx.x + s]);
+            }
+            sm[6][threadIdx.x] = min(sm[6][threadIdx.x], sm[6][threadIdx.x + s]);
+            sm[7][threadIdx.x] += sm[7][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        for (int c = 0; c < 3; c++) { atomicMin(&red[c], sm[c][0]); atomicMax(&red[3 + c], sm[3 + c][0]); }
+        atomicMin(&red[6], sm[6][0]);
+        if (sm[7][0]) atomicAdd(&red[7], sm[7][0]);
+    }
+}
+
+__device__ __forceinline__ uint32_t cell_of(const OvGrid &g, V3 v)
+{
+    const int cx = cell_coord(v.x, g.x0, g.inv_h, g.nx), cy = cell_coord(v.y, g.y0, g.inv_h, g.ny);
+    const int cz = cell_coord(v.z, g.z0, g.inv_h, g.nz);
+    return ((uint32_t)cz * (uint32_t)g.ny + (uint32_t)cy) * (uint32_t)g.nx + (uint32_t)cx;
+}
+
+// invalid buoys get key ncells: they sort after every cell and belong to none
+__global__ __launch_bounds__(kOvThreads) void bin_key_kernel(OvGrid g, int64_t n, const double *__restrict__ lat,
+                                                            const double *__restrict__ lon, const int8_t *__restrict__ valid,
+                                                            uint32_t *key, int32_t *val)
+{
+    const int64_t i = (int64_t)blockIdx.x * kOvThreads + threadIdx.x;
+    if (i >= n) return;
+    key[i] = is_valid(valid, i) ? cell_of(g, unit_vec(lat[i], lon[i])) : g.ncells;
+    val[i] = (int32_t)i;
+}
+
+// cstart/cend zeroed by the caller: empty cells keep [0,0)
+__global__ __launch_bounds__(kOvThreads) void bin_gather_kernel(OvGrid g, int64_t n, const double *__restrict__ lat,
+                                                               const double *__restrict__ lon, const uint32_t *__restrict__ key,
+                                                               const int32_t *__restrict__ perm, V3 *uv_s, ll *ll_s, int32_t *cstart,
+                                                               int32_t *cend)
+{
+    const int64_t s = (int64_t)blockIdx.x * kOvThreads + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t k = key[s];
+    if (k >= g.ncells) return;
+    const int32_t i = perm[s];
+    const double la = lat[i], lo = lon[i];
+    uv_s[s] = unit_vec(la, lo);
+    ll p; p.lat = la; p.lon = lo;
+    ll_s[s] = p;
+    if (s == 0 || key[s - 1] != k) cstart[k] = (int32_t)s;
+    if (s == n - 1 || key[s + 1] != k) cend[k] = (int32_t)(s + 1);
+}
+
+// Results in input order: nn = input index of the nearest other valid buoy when its distance is < rd, else -1 (dmin +inf).
+__global__ __launch_bounds__(kOvThreads) void nearest_kernel(OvGrid g, int64_t n, double rd_km, double cut2,
+                                                            const uint32_t *__restrict__ key, const int32_t *__restrict__ perm,
+                                                            const V3 *__restrict__ uv, const ll *__restrict__ lls,
+                                                            const int32_t *__restrict__ cstart, const int32_t *__restrict__ cend,
+                                                            int32_t *nn, double *dmin)
+{
+    const int64_t s = (int64_t)blockIdx.x * kOvThreads + threadIdx.x;
+    if (s >= n) return;
+    const int32_t me = perm[s];
+    const uint32_t k = key[s];
+    int32_t best_i = -1;
+    double best = INFINITY;
+    if (k < g.ncells) {
+        const int cx = (int)(k % (uint32_t)g.nx), cy = (int)((k / (uint32_t)g.nx) % (uint32_t)g.ny);
+        const int cz = (int)(k / ((uint32_t)g.nx * (uint32_t)g.ny));
+        const V3 P = uv[s];
+        // pass 1: minimum chord^2 to any other valid buoy of the 27 cells
+        double cmin = INFINITY;
+        for (int c = 0; c < 27; c++) {
+            const int zz = cz + c / 9 - 1, yy = cy + (c / 3) % 3 - 1, xx = cx + c % 3 - 1;
+            if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny || xx < 0 || xx >= g.nx) continue;
+            const int64_t cc = ((int64_t)zz * g.ny + yy) * g.nx + xx;
+            const int32_t e = cend[cc];
+            for (int32_t q = cstart[cc]; q < e; q++)
+                if (q != s) cmin = fmin(cmin, chord2(P, uv[q]));
+        }
+        // nothing within the chord of rd (with its slack) can be closer than rd: skip pass 2
+        if (cmin <= cut2) {
+            const double t = sqrt(cmin) * (1.0 + 1e-9) + 1e-13;
+            const double thr = t * t;
+            const ll L = lls[s];
+            const double cos_plat = cos(L.lat * (3.141592653589793 / 180.));
+            for (int c = 0; c < 27; c++) {
+                const int zz = cz + c / 9 - 1, yy = cy + (c / 3) % 3 - 1, xx = cx + c % 3 - 1;
+                if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny || xx < 0 || xx >= g.nx) continue;
+                const int64_t cc = ((int64_t)zz * g.ny + yy) * g.nx + xx;
+                const int32_t e = cend[cc];
+                for (int32_t q = cstart[cc]; q < e; q++) {
+                    if (q == s || !(chord2(P, uv[q]) <= thr)) continue;
+                    const ll Q = lls[q];
+                    const double d = haversine(L.lat, L.lon, cos_plat, Q.lat, Q.lon);
+                    const int32_t qi = perm[q];
+                    if (d < best || (d == best && qi < best_i)) { best = d; best_i = qi; }
+                }
+            }
+        }
+        if (!(best < rd_km)) { best = INFINITY; best_i = -1; }
+    }
+    nn[me] = best_i;
+    dmin[me] = best;
+}
+
+__global__ __launch_bounds__(kOvThreads) void flag_kernel(int64_t n, const int32_t *__restrict__ nn, int32_t *flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * kOvThreads + threadIdx.x;
+    if (i < n) flag[i] = nn[i] >= 0 ? 1 : 0;
+}
+
+// pos = exclusive scan of the flags: close buoy i goes to position pos[i]; its neighbour nn[i] is close too,
+// -1 flags a broken closure (the host reports it)
+__global__ __launch_bounds__(kOvThreads) void close_scatter_kernel(int64_t n, const int32_t *__restrict__ nn, const int32_t *__restrict__ pos,
+                                                                  int32_t *cidx, int32_t *cnn)
+{
+    const int64_t i = (int64_t)blockIdx.x * kOvThreads + threadIdx.x;
+    if (i >= n) return;
+    const int32_t j = nn[i];
+    if (j < 0) return;
+    const int32_t p = pos[i];
+    cidx[p] = (int32_t)i;
+    cnn[p] = nn[j] >= 0 ? pos[j] : -1;
+}
+
+inline unsigned nblk(int64_t n) { return (unsigned)((n + kOvThreads - 1) / kOvThreads); }
+
+}  // namespace
+
+hipError_t overlap_bbox(int64_t n, const double *lat, const double *lon, const int8_t *valid, unsigned long long *red, hipStream_t s)
+{
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, s, red);
+    const unsigned g = nblk(n) < 2048u ? nblk(n) : 2048u;
+    hipLaunchKernelGGL(unit_bbox_kernel, dim3(g), dim3(kOvThreads), 0, s, n, lat, lon, valid, red);
+    return hipGetLastError();
+}
+
+hipError_t overlap_bin_keys(const OvGrid &g, int64_t n, const double *lat, const double *lon, const int8_t *valid, uint32_t *key,
+                            int32_t *val, hipStream_t s)
+{
+    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, lat, lon, valid, key, val);
+    return hipGetLastError();
+}
+
+hipError_t overlap_bin_gather(const OvGrid &g, int64_t n, const double *lat, const double *lon, const uint32_t *key_sorted,
+                              const int32_t *perm, V3 *uv_s, ll *ll_s, int32_t *cstart, int32_t *cend, hipStream_t s)
+{
+    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, lat, lon, key_sorted, perm, uv_s, ll_s, cstart,
+                       cend);
+    return hipGetLastError();
+}
+
+hipError_t overlap_nearest(const OvGrid &g, int64_t n, double rd_km, double cut2, const uint32_t *key_sorted, const int32_t *perm,
+                           const V3 *uv_s, const ll *ll_s, const int32_t *cstart, const int32_t *cend, int32_t *nn, double *dmin,
+                           hipStream_t s)
+{
+    hipLaunchKernelGGL(nearest_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, rd_km, cut2, key_sorted, perm, uv_s, ll_s, cstart,
+                       cend, nn, dmin);
+    return hipGetLastError();
+}
+
+// two-call protocol like sort_pairs_u32: tmp == nullptr -> only *tmp_bytes is written
+hipError_t overlap_compact(void *tmp, size_t *tmp_bytes, int64_t n, const int32_t *nn, int32_t *flag, int32_t *pos, int32_t *cidx,
+                           int32_t *cnn, hipStream_t s)
+{
+    if (tmp == nullptr)
+        return rocprim::exclusive_scan(tmp, *tmp_bytes, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s);
+    hipLaunchKernelGGL(flag_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, n, nn, flag);
+    hipError_t e = rocprim::exclusive_scan(tmp, *tmp_bytes, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(close_scatter_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, n, nn, pos, cidx, cnn);
+    return hipGetLastError();
+}
+
+}  // namespace sitrk

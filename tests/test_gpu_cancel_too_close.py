@@ -1,0 +1,301 @@
+"""Overlap cleaning on the GPU (sitrk_cancel_too_close, sitrk_nearest_buoy, CancelTooClose, tools/cancel_too_close.py)
+against the test-side restatement in test_cancel_too_close.py, which is itself pinned to the reference by golden set G11."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+from scipy.spatial import cKDTree
+
+import sitrack_amd as sit
+from sitrack_amd import _lib
+from sitrack_amd import ncio
+from sitrack_amd import synthetic as syn
+
+from test_cancel_too_close import g11_cases, haversine, load_generator, nearest, random_cloud, restate
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = sit.Context(0)
+    yield c
+    c.close()
+
+
+def test_g11_bit_equal(ctx):
+    for name, krec, rdkm, nbpass, plat, plon, pmsk, nbn, idx in g11_cases():
+        n, got = sit.CancelTooClose(krec, rdkm, plat, plon, pmsk, NbPass=nbpass, ctx=ctx)
+        assert got.dtype == np.int64
+        assert n == nbn and np.array_equal(got, idx), name
+
+
+def test_g11_nearest_probe(ctx):
+    for name, krec, rdkm, _, plat, plon, pmsk, _, _ in g11_cases():
+        nn_r, d_r = nearest(plat[krec], plon[krec])
+        close = d_r < rdkm
+        nn, d = ctx.nearest_buoy(plat[krec], plon[krec], None, rdkm)
+        assert np.array_equal(nn[close], nn_r[close]), name
+        np.testing.assert_allclose(d[close], d_r[close], rtol=1e-12, atol=0)
+        assert np.all(nn[~close] == -1) and np.all(np.isinf(d[~close])), name
+        assert np.array_equal(d[close] == 0, d_r[close] == 0), name            # exact duplicates are exact
+
+
+def _random_case(seed):
+    """A ulp-safe random case (see gen_golden_g11.ulp_safe) with invalid buoys at krec holding fill or NaN."""
+    gen = load_generator()
+    rng = np.random.default_rng(500 + seed)
+    for _ in range(20):
+        n = int(rng.integers(20, 5001)) if seed % 5 else int(rng.integers(2, 40))
+        rd = float(np.exp(rng.uniform(np.log(0.5), np.log(300.))))
+        la, lo = random_cloud(rng, n, rd)
+        if seed % 4 == 1:                                       # duplicates
+            k = n // 8
+            src, dst = rng.integers(0, n, k), rng.choice(n, k, replace=False)
+            la[dst], lo[dst] = la[src], lo[src]
+        nrec = int(rng.integers(1, 7))
+        krec = int(rng.integers(0, nrec))
+        pmsk = (rng.random((nrec, n)) < 0.8).astype(np.int8)
+        pmsk[krec] = rng.random(n) < (0.9 if seed % 3 else 1.0)
+        v = pmsk[krec] != 0
+        if gen.ulp_safe(la[v], lo[v], rd):
+            plat, plon = gen.series(la, lo, pmsk, krec)
+            bad = np.flatnonzero(~v)
+            plat[krec, bad] = np.where(bad % 2, -9999., np.nan)
+            plon[krec, bad] = np.where(bad % 3, -9999., np.nan)
+            return krec, rd, plat, plon, pmsk
+    raise RuntimeError("no ulp-safe draw")
+
+
+@pytest.mark.parametrize("seed", range(50))
+def test_random_against_restatement(ctx, seed):
+    krec, rd, plat, plon, pmsk = _random_case(seed)
+    nbn_r, idx_r = restate(krec, rd, plat, plon, pmsk)
+    nbn, idx = sit.CancelTooClose(krec, rd, plat, plon, pmsk, NbPass=1 + seed % 3, ctx=ctx)
+    assert nbn == nbn_r and np.array_equal(idx, idx_r)
+    assert np.all(pmsk[krec, idx] == 1)
+
+
+def test_invalid_buoys_take_no_part(ctx):
+    # three buoys at one place; the middle one is invalid (fill, then NaN) and must be nobody's neighbour
+    la = np.array([80., 80., 80.00001, 70.])
+    lo = np.array([10., 10., 10., 10.])
+    pmsk = np.ones((2, 4), np.int8)
+    pmsk[1, 1] = 0
+    for fill in (-9999., np.nan):
+        plat, plon = np.stack([la, la]), np.stack([lo, lo])
+        plat[1, 1] = plon[1, 1] = fill
+        nbn, idx = sit.CancelTooClose(1, 5., plat, plon, pmsk, ctx=ctx)
+        # 0 and 2 are close with equal counts: the neighbour (2) goes; 1 lies on them but is invalid
+        assert nbn == 2 and list(idx) == [0, 3]
+        nn, d = ctx.nearest_buoy(plat[1], plon[1], pmsk[1], 5.)
+        assert list(nn) == [2, -1, 0, -1] and np.isinf(d[1]) and np.isinf(d[3])
+    # all invalid, none valid, n == 0
+    keep, nclose = ctx.cancel_too_close(la, lo, np.zeros(4, np.int8), np.ones(4), np.zeros(4), 5.)
+    assert not keep.any() and nclose == 0
+    keep, nclose = ctx.cancel_too_close(np.zeros(0), np.zeros(0), None, np.zeros(0), np.zeros(0), 5.)
+    assert keep.shape == (0,) and nclose == 0
+    nn, d = ctx.nearest_buoy(np.zeros(0), np.zeros(0), None, 5.)
+    assert nn.shape == (0,) and d.shape == (0,)
+    # valid == NULL: every buoy valid
+    keep, nclose = ctx.cancel_too_close(la[[0, 2, 3]], lo[[0, 2, 3]], None, [3, 3, 3], [0, 0, 0], 5.)
+    assert list(keep) == [True, False, True] and nclose == 2
+
+
+@pytest.mark.parametrize("rd", [0.0, -1.0, np.inf, -np.inf, np.nan, 9999.0001, 1e300])
+def test_einval_rd(ctx, rd):
+    with pytest.raises(_lib.SitrkError, match="rd_km"):
+        ctx.cancel_too_close([80., 81.], [0., 0.], None, [1, 1], [0, 0], rd)
+    with pytest.raises(_lib.SitrkError, match="rd_km"):
+        ctx.nearest_buoy([80., 81.], [0., 0.], None, rd)
+
+
+@pytest.mark.parametrize("where", ["lat", "lon"])
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+def test_einval_nonfinite_names_first_index(ctx, where, bad):
+    la = np.full(10, 80.)
+    lo = np.linspace(0., 1., 10)
+    (la if where == "lat" else lo)[[3, 7]] = bad
+    with pytest.raises(_lib.SitrkError, match="index 3"):
+        ctx.cancel_too_close(la, lo, None, np.ones(10), np.zeros(10), 5.)
+    with pytest.raises(_lib.SitrkError, match="index 3"):
+        ctx.nearest_buoy(la, lo, None, 5.)
+    v = np.ones(10, np.int8)
+    v[3] = 0                                    # an invalid buoy may hold anything: the next one is named
+    with pytest.raises(_lib.SitrkError, match="index 7"):
+        ctx.nearest_buoy(la, lo, v, 5.)
+    v[7] = 0
+    nn, _ = ctx.nearest_buoy(la, lo, v, 5.)
+    assert nn[3] == -1 and nn[7] == -1
+
+
+def test_einval_null_arrays(ctx):
+    L = ctx._L
+    nk, nc = _lib._i64(0), _lib._i64(0)
+    a = np.zeros(4)
+    c = np.zeros(4, np.int32)
+    k = np.zeros(4, np.int8)
+    P = _lib._ptr
+    import ctypes as C
+    assert L.sitrk_cancel_too_close(ctx._h, 4, None, P(a), None, P(c), P(c), 5., P(k), C.byref(nk), C.byref(nc)) == -1
+    assert L.sitrk_cancel_too_close(ctx._h, 4, P(a), P(a), None, None, P(c), 5., P(k), C.byref(nk), C.byref(nc)) == -1
+    assert L.sitrk_cancel_too_close(ctx._h, 4, P(a), P(a), None, P(c), P(c), 5., None, C.byref(nk), C.byref(nc)) == -1
+    assert L.sitrk_cancel_too_close(ctx._h, 4, P(a), P(a), None, P(c), P(c), 5., P(k), None, None) == -1
+    assert L.sitrk_cancel_too_close(ctx._h, -1, P(a), P(a), None, P(c), P(c), 5., P(k), C.byref(nk), None) == -1
+    assert L.sitrk_nearest_buoy(ctx._h, 4, P(a), P(a), None, 5., None, P(a)) == -1
+    assert L.sitrk_nearest_buoy(ctx._h, 4, P(a), None, None, 5., P(c), P(a)) == -1
+    assert L.sitrk_nearest_buoy(None, 4, P(a), P(a), None, 5., P(c), P(a)) == -1
+
+
+def test_nearest_buoy_at_scale_against_kdtree(ctx):
+    """~2e6 perturbed mesh points (with duplicates) against a cKDTree on the unit vectors, Haversine re-evaluated in numpy on
+    the candidates it returns."""
+    rng = np.random.default_rng(11)
+    N = 1414
+    g = syn.make_grid(N, N, dkm=3.0, warp=0.5)
+    yx = np.stack([g["Yt"].ravel(), g["Xt"].ravel()], axis=1)
+    yx += rng.normal(0., 0.6, yx.shape)
+    ll = ctx.cart2geo(yx)
+    la, lo = ll[:, 0].copy(), np.mod(ll[:, 1], 360.)
+    n = len(la)
+    dup = rng.choice(n, 2 * (n // 200), replace=False)
+    la[dup[1::2]], lo[dup[1::2]] = la[dup[0::2]], lo[dup[0::2]]          # pairs of exact copies
+    valid = rng.random(n) > 0.02
+    rd = 2.5
+    nn, d = ctx.nearest_buoy(la, lo, valid, rd)
+    # truth: the 8 chord-nearest valid points, Haversine on them, first minimum in index order
+    r = np.radians
+    uv = np.stack([np.cos(r(la)) * np.cos(r(lo)), np.cos(r(la)) * np.sin(r(lo)), np.sin(r(la))], axis=1)
+    iv = np.flatnonzero(valid)
+    tree = cKDTree(uv[iv])
+    K = 9
+    ch, kk = tree.query(uv[iv], k=K, workers=16)
+    cand = iv[kk]                                           # (nv, K) input indices, self among them
+    dh = haversine(la[iv][:, None], lo[iv][:, None], la[cand], lo[cand])
+    dh[cand == iv[:, None]] = np.inf
+    best = np.min(dh, axis=1)
+    tie = dh == best[:, None]
+    idx_best = np.where(tie, cand, np.iinfo(np.int64).max).min(axis=1)
+    # the K-th chord bounds what the tree may have missed: rows whose minimum is not clearly inside it are not judged
+    chord_best = 2. * np.sin(best / (2. * 6360.))
+    judged = ch[:, -1] > chord_best * (1. + 1e-6) + 1e-12
+    assert judged.mean() > 0.99
+    # ulp-close rows are not judged either: dmin at rd, or a distinct rival within 1e-10
+    second = np.where(dh > best[:, None], dh, np.inf).min(axis=1)
+    judged &= (np.abs(best - rd) > 1e-9 * rd) & ((second > best * (1. + 1e-10)) | (best == 0.))
+    close = best < rd
+    sel = judged & close
+    assert sel.sum() > 0.3 * n and (judged & ~close).sum() > 1000
+    assert np.array_equal(nn[iv[sel]], idx_best[sel])
+    np.testing.assert_allclose(d[iv[sel]], best[sel], rtol=1e-12, atol=0)
+    far = judged & ~close
+    assert np.all(nn[iv[far]] == -1) and np.all(np.isinf(d[iv[far]]))
+    assert np.all(nn[~valid] == -1) and np.all(np.isinf(d[~valid]))
+    # duplicates found at distance 0
+    assert np.sum(d[iv] == 0.) >= 0.8 * len(dup)
+
+
+def test_tracker_state_is_untouched_by_a_cleaning_on_the_same_handle():
+    g = syn.make_grid(64, 64, dkm=4.0, warp=1.0)
+    u, v, sic = syn.make_fields(g, K=4, seed=2024, umax=0.75, drift=0.25, ripple=0.12)
+    _, yx = syn.make_buoys(g, 2000, seed=1234, frac=0.7)
+    rng = np.random.default_rng(9)
+    la, lo = random_cloud(rng, 300_000, 5.)                 # larger than anything the tracker staged
+    runs = []
+    for with_cloud in (False, True):
+        trk = sit.IceTracker(g["Yf"], g["Xf"], g["Yu"], g["Xu"], g["Yv"], g["Xv"], g["tmask"], nslots=4)
+        found, ji, _ = sit.FindContainingCell(yx, syn.nearest_t_plane(g, yx), ctx=trk.ctx)
+        trk.set_buoys(yx[found], ji[found])
+        for k in range(4):
+            trk.load_record(k, u[k], v[k], sic[k])
+        trk.run(0, 0, 4)
+        if with_cloud:
+            keep, nclose = trk.ctx.cancel_too_close(la, lo, None, np.full(len(la), 3), np.zeros(len(la)), 5.)
+            assert nclose > 0 and 0 < keep.sum() < len(la)
+            trk.ctx.nearest_buoy(la, lo, None, 5.)
+        trk.run(4, 0, 4)
+        st = trk.state()
+        rec = trk.record(7)
+        runs.append((st, rec))
+        trk.ctx.close()
+    (a, ra), (b, rb) = runs
+    for k in ("yx", "vJIt", "iAlive"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("ctc_tool", os.path.join(ROOT, "tools", "cancel_too_close.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _traj(rng, nrec, n, krec):
+    la, lo = random_cloud(rng, n, 8.)
+    lat = np.stack([la + 0.01 * t for t in range(nrec)])
+    lon = np.stack([np.mod(lo + 0.01 * t, 360.) for t in range(nrec)])
+    msk = (rng.random((nrec, n)) < 0.85).astype(np.int8)
+    msk[0] = 1
+    lat[msk == 0] = -9999.
+    lon[msk == 0] = -9999.
+    y, x = lat * 10., lon * 10.
+    y[msk == 0] = -9999.
+    x[msk == 0] = -9999.
+    return lat, lon, y, x, msk
+
+
+def _read_all(path):
+    with ncio._Reader(path) as f:
+        out = {v: np.asarray(f.var(v)) for v in ('time', 'id_buoy', 'latitude', 'longitude', 'y_pos', 'x_pos')}
+        for v in ('mask', 'time_pos'):
+            if f.has_var(v):
+                out[v] = np.asarray(f.var(v))
+    return out
+
+
+def _check_tool(tmp_path, src, krec, rd, has_mask):
+    tool = _tool()
+    out = str(tmp_path / "out.nc")
+    assert tool.main(["-i", src, "-k", str(krec), "-r", str(rd), "-o", out]) == 0
+    a, b = _read_all(src), _read_all(out)
+    _, _, zLL, _ = ncio.LoadNCdata(src)
+    plat, plon = zLL[..., 0], zLL[..., 1]
+    if has_mask:
+        pmsk = a['mask']
+    else:
+        pmsk = (a['latitude'] != np.float32(-9999.)).astype(np.int8)
+    nbn, idx = sit.CancelTooClose(krec, rd, plat, plon, pmsk)
+    assert 0 < nbn < int((pmsk[krec] != 0).sum())
+    assert set(b) == set(a)
+    assert np.array_equal(b['time'], a['time'])
+    for v in b:
+        if v != 'time':
+            assert np.array_equal(b[v], a[v][..., idx]), v
+
+
+def test_tool_two_record_file(tmp_path):
+    rng = np.random.default_rng(21)
+    n = 3000
+    lat, lon, y, x, msk = _traj(rng, 2, n, 0)
+    tpos = np.stack([np.full(n, 1000), np.full(n, 4600)]).astype(np.int32)
+    src = str(tmp_path / "traj12.nc")
+    ncio.ncSaveCloudBuoys(src, np.array([1000, 4600]), np.arange(n) + 70000, y, x, lat, lon, mask=msk, xtime=tpos)
+    _check_tool(tmp_path, src, 0, 6., True)
+    src2 = str(tmp_path / "traj12_nomask.nc")                  # validity from latitude's _FillValue
+    ncio.ncSaveCloudBuoys(src2, np.array([1000, 4600]), np.arange(n) + 70000, y, x, lat, lon)
+    _check_tool(tmp_path, src2, 1, 6., False)
+
+
+def test_tool_series_file(tmp_path):
+    rng = np.random.default_rng(22)
+    n, nrec = 2500, 6
+    lat, lon, y, x, msk = _traj(rng, nrec, n, 3)
+    src = str(tmp_path / "series.nc")
+    s = ncio.CloudBuoysStream(src, np.arange(nrec) * 3600, np.arange(n) + 10, with_mask=True)
+    for t in range(nrec):
+        s.put(t, y[t], x[t], lat[t], lon[t], mask=msk[t])
+    s.close()
+    _check_tool(tmp_path, src, 3, 6., True)
