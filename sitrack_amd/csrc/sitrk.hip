@@ -137,7 +137,6 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     free_buoys(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter);
-    dev_free(h->stamps);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
     if (h->box_host) (void)hipHostFree(h->box_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -285,11 +284,6 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
         return SITRK_OK;
     }
     else if (!strcmp(knob, "locate_bruteforce")) bit = TUNE_LOCATE_BRUTEFORCE;
-#ifdef SITRK_DIAG
-    else if (!strcmp(knob, "stamps")) { h->stamps_on = value != 0; return SITRK_OK; }
-    else if (!strcmp(knob, "diag_memonly")) bit = TUNE_DIAG_MEMONLY;
-    else if (!strcmp(knob, "diag_nocross")) bit = TUNE_DIAG_NOCROSS;
-#endif
     else return fail(h, SITRK_EINVAL, "sitrk_set_tuning: unknown knob '%s'", knob);
     h->tune = value ? (h->tune | bit) : (h->tune & ~bit);
     return SITRK_OK;
@@ -1044,11 +1038,6 @@ static void launch_step_b(sitrk_ctx *h, const StepArgs &a)
 template <typename FT>
 static void launch_step(sitrk_ctx *h, const StepArgs &a)
 {
-#ifdef SITRK_DIAG
-    dim3 grid(nblocks(a.nP)), block(kBlock);
-    if (h->tune & TUNE_DIAG_MEMONLY) { hipLaunchKernelGGL((advect_memonly_kernel<FT>), grid, block, 0, h->stream, a); return; }
-    if (h->tune & TUNE_DIAG_NOCROSS) { hipLaunchKernelGGL((advect_nocross_kernel<FT>), grid, block, 0, h->stream, a); return; }
-#endif
     if (h->step_block == 1024) launch_step_b<FT, 1024>(h, a);
     else if (h->step_block == 512) launch_step_b<FT, 512>(h, a);
     else launch_step_b<FT, 256>(h, a);
@@ -1110,21 +1099,16 @@ static void launch_run(sitrk_ctx *h, const RunArgs &ra)
     // dynamic LDS: tables + the patch's F-points
     const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
     const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
-#define SITRK_LAUNCH_RUN(KERNEL)                                                                          \
-    do {                                                                                                  \
-        if (h->uv_strategy == 1) {                                                                        \
-            if (windowed) hipLaunchKernelGGL((KERNEL<FT, 1, true>), grid, block, lds, h->stream, ra);     \
-            else hipLaunchKernelGGL((KERNEL<FT, 1, false>), grid, block, lds, h->stream, ra);             \
-        } else if (h->uv_strategy == 2) {                                                                 \
-            if (windowed) hipLaunchKernelGGL((KERNEL<FT, 2, true>), grid, block, lds, h->stream, ra);     \
-            else hipLaunchKernelGGL((KERNEL<FT, 2, false>), grid, block, lds, h->stream, ra);             \
-        } else {                                                                                          \
-            if (windowed) hipLaunchKernelGGL((KERNEL<FT, 0, true>), grid, block, lds, h->stream, ra);     \
-            else hipLaunchKernelGGL((KERNEL<FT, 0, false>), grid, block, lds, h->stream, ra);             \
-        }                                                                                                 \
-    } while (0)
-    SITRK_LAUNCH_RUN(advect_run_kernel);
-#undef SITRK_LAUNCH_RUN
+    if (h->uv_strategy == 1) {
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 1, true>), grid, block, lds, h->stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 1, false>), grid, block, lds, h->stream, ra);
+    } else if (h->uv_strategy == 2) {
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 2, true>), grid, block, lds, h->stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 2, false>), grid, block, lds, h->stream, ra);
+    } else {
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 0, true>), grid, block, lds, h->stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 0, false>), grid, block, lds, h->stream, ra);
+    }
 }
 
 SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
@@ -1168,19 +1152,6 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
         ra.patch_margin = h->patch_margin;
         ra.xcd_group = h->xcd_group;
         ra.f32_class = f32_class_for(h->rdt);
-#ifdef SITRK_DIAG
-        ra.stamps = nullptr;
-        if (h->stamps_on) {
-            const size_t nw = (size_t)nblocks(h->nP, kRunBlock) * (kRunBlock / 64);
-            if (nw > h->stamps_waves) {
-                dev_free(h->stamps); h->stamps = nullptr; h->stamps_waves = 0;
-                HIPCHK(hipMalloc((void **)&h->stamps, nw * 8 * sizeof(unsigned long long)));
-                h->stamps_waves = nw;
-            }
-            HIPCHK(hipMemsetAsync(h->stamps, 0, h->stamps_waves * 8 * sizeof(unsigned long long), h->stream));
-            ra.stamps = h->stamps;
-        }
-#endif
         int used[kMaxFuse];
         for (int r = 0; r < m; r++) {
             const int slot = (slot0 + k + r) % h->nslots;
@@ -1212,20 +1183,6 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
     }
     return SITRK_OK;
 }
-
-#ifdef SITRK_DIAG
-// diagnostic builds only (not in include/sitrk.h): the s_memtime intervals of the last fused launch, 8 per wave
-SITRK_API int sitrk_diag_stamps(sitrk_t *h, unsigned long long *out, long long max_waves, long long *nwaves)
-{
-    NEED(h, "null handle");
-    NEED(out && nwaves, "sitrk_diag_stamps: null output");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const long long n = std::min<long long>((long long)h->stamps_waves, max_waves);
-    *nwaves = n;
-    if (n > 0) HIPCHK(hipMemcpy(out, h->stamps, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return SITRK_OK;
-}
-#endif
 
 SITRK_API int sitrk_launch_stats(sitrk_t *h, int reset, int64_t *fused_launches, int64_t *fused_records, int64_t *step_launches)
 {

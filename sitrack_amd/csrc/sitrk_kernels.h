@@ -13,13 +13,6 @@
 
 #pragma clang fp contract(off)
 
-// The ablation hooks below give WRONG results by design (timing only, profiles/r03s_*): they exist in diagnostic builds
-// (`make DIAG=1`) and nowhere else -- a stray -D must not ship a wrong tracker that still exports every symbol.
-#if (defined(SITRK_ABL_NOEDGE) || defined(SITRK_ABL_NODIAG) || defined(SITRK_ABL_VEL2) || defined(SITRK_ABL_NOK9) || \
-     defined(SITRK_ABL_VELCONST) || defined(SITRK_ABL_VELLDS) || defined(SITRK_NO_LAZY_HIT)) && !defined(SITRK_DIAG)
-#error "SITRK_ABL_* / SITRK_NO_LAZY_HIT are diagnostic ablations (wrong results): they need -DSITRK_DIAG (make DIAG=1)"
-#endif
-
 namespace sitrk {
 
 static constexpr int kBlock = 256;
@@ -238,14 +231,10 @@ __global__ __launch_bounds__(kSvBlock) void survive_kill9_kernel(int Nj, int Ni,
 // (58 us the LDS-tile kernel, 110 us round 2's two passes): 117 MB -> 3.3 TB/s.
 // Same tests, same order, same left-to-right fp64 sum; same validity rules for row bands.
 // ---------------------------------------------------------------------------
-#ifndef SITRK_SV_R
-#define SITRK_SV_R 16                   // measured at 4096^2 (tools/sv_ab.sh, profiles/r03m_*): 8 / 12 / 16 / 32 / 64 rows per wave = 34.7 / 35.4 /
-#endif                                  // 35.3 / 39.3 / 57.1 us -- more waves beat fewer halo rows; 16 keeps the halo at 25 %
-#ifndef SITRK_SV_D
-#define SITRK_SV_D 4
-#endif
-static constexpr int kSvRowsR = SITRK_SV_R;  // output rows per wave
-static constexpr int kSvRowsD = SITRK_SV_D;  // rows in flight per wave; (kSvRowsR + 4) % kSvRowsD == 0
+// kSvRowsR measured at 4096^2 (profiles/r03m_*): 8 / 12 / 16 / 32 / 64 rows per wave = 34.7 / 35.4 / 35.3 / 39.3 / 57.1 us --
+// more waves beat fewer halo rows; 16 keeps the halo at 25 %
+static constexpr int kSvRowsR = 16;  // output rows per wave
+static constexpr int kSvRowsD = 4;   // rows in flight per wave; (kSvRowsR + 4) % kSvRowsD == 0
 static_assert((kSvRowsR + 4) % kSvRowsD == 0, "the row loop is unrolled by the prefetch depth");
 static constexpr int kSvRowsCols = 62 * 4;   // output columns per wave and row
 
@@ -583,11 +572,7 @@ __device__ __forceinline__ int resolve_crossing_tab(pt P1, pt P2, pt bl, pt br, 
     bool hitA = ccw(P1, va, eA) != ccw(P2, va, eA);
     bool hitB = ccw(P1, vb, eB) != ccw(P2, vb, eB);
     // ... and only for lanes that pass it the second half of intersect2Seg (a diagonal move is rare: most waves skip this)
-#ifdef SITRK_NO_LAZY_HIT
-    {
-#else
     if (hitA || hitB) {
-#endif
         hitA = hitA && (ccw(P1, P2, va) != ccw(P1, P2, eA));
         hitB = hitB && (ccw(P1, P2, vb) != ccw(P1, P2, eB));
     }
@@ -640,14 +625,7 @@ __device__ __forceinline__ unsigned xcd_group(unsigned bid, unsigned nwg, unsign
 // The fused loop evaluates `/1000.` and IsInsideQuadrangle without fp64 divisions (sitrk_geom.h: div1000,
 // inside_quad_hot - same results for every input): 0.111 -> 0.101 ms per record on C3.  The one-record kernel is
 // bound by memory latency, not by issue, and was measured 4-6 % SLOWER with them (and with pinned loads): it keeps
-// the plain forms.  `make EXACTDIV=1` builds the plain forms everywhere for A/B timing.
-#ifdef SITRK_EXACT_DIV
-#define SITRK_DIV1000(x, ...) ((x) / 1000.)
-#define SITRK_INSIDE(y, x, q0, q1, q2, q3, eps) inside_quad(y, x, q0, q1, q2, q3)
-#else
-#define SITRK_DIV1000(x, ...) div1000(x, ##__VA_ARGS__)
-#define SITRK_INSIDE(y, x, q0, q1, q2, q3, eps) inside_quad_hot(y, x, q0, q1, q2, q3, eps)
-#endif
+// the plain forms.
 
 // A value that must be loaded where the source loads it: the empty asm is a use the compiler cannot move the load below.
 template <typename T> __device__ __forceinline__ void pin_load(T &v) { asm volatile("" : "+v"(v)); }
@@ -770,9 +748,6 @@ struct RunArgs {
     int dji[4][7][2];                   // its (dj,di) pairs: va, vb, eA, eB, S, A, B per crossed edge (for the patch's own offsets)
     int patch_cells, patch_margin;      // LDS patch: capacity in cells (0 = no patch) and the largest margin to try
     int xcd_group;                      // > 1: runs of that many consecutive workgroups share an XCD
-#ifdef SITRK_DIAG
-    unsigned long long *stamps;         // diagnostic builds: per wave 8 accumulated s_memtime intervals of the record loop (or null)
-#endif
     int f32_class;                      // v_cmp_class mask of div1000_of_f32: finite and non-zero, or 0 when |rdt| is outside
                                         // [2^-700, 2^700] (every lane then divides)
 };
@@ -869,23 +844,15 @@ __device__ __forceinline__ void resolve_crossing_lds(pt P1, pt P2, pt bl, pt br,
                                                      const int *__restrict__ tab, const int *__restrict__ tabL, int &dcell, int &dk,
                                                      int &dlo, bool &killed)
 {
-#ifdef SITRK_ABL_NOEDGE                 // ablation (timing only, WRONG results): the crossed edge from one comparison instead of CrossedEdge
-    const unsigned ro = (P2.x > ur.x) ? 64u : ((P2.y > ur.y) ? 128u : ((P2.y <= bl.y) ? 0u : 192u));
-#else
     const bool sbl = ccw(P1, P2, bl), sbr = ccw(P1, P2, br), sur = ccw(P1, P2, ur), sul = ccw(P1, P2, ul);
     const bool h1 = (ccw(P1, bl, br) != ccw(P2, bl, br)) && (sbl != sbr);
     const bool h2 = (ccw(P1, br, ur) != ccw(P2, br, ur)) && (sbr != sur);
     const bool h3 = (ccw(P1, ur, ul) != ccw(P2, ur, ul)) && (sur != sul);
     const unsigned ro = h1 ? 0u : (h2 ? 64u : (h3 ? 128u : 192u));            // both tables have 64-byte rows
-#endif
     const int *row = (const int *)((const char *)tab + ro), *rowL = (const int *)((const char *)tabL + ro);
     const int4 r1 = *(const int4 *)(row + 4), r2 = *(const int4 *)(row + 8);
     const int bB = row[12];
     const int4 l0 = *(const int4 *)(rowL), l1 = *(const int4 *)(rowL + 4);
-#ifdef SITRK_ABL_NODIAG                 // ablation (timing only, WRONG results): no NewHostCell tests, no extension points
-    bool hitA = false, hitB = false;
-    (void)l0;
-#else
     const pt va = lds_pt_at(lo + (unsigned)l0.x), vb = lds_pt_at(lo + (unsigned)l0.y);     // (the table's offsets carry the bias)
     const pt eA = lds_pt_at(lo + (unsigned)l0.z), eB = lds_pt_at(lo + (unsigned)l0.w);
     bool hitA = ccw(P1, va, eA) != ccw(P2, va, eA);
@@ -894,7 +861,6 @@ __device__ __forceinline__ void resolve_crossing_lds(pt P1, pt P2, pt bl, pt br,
         hitA = hitA && (ccw(P1, P2, va) != ccw(P1, P2, eA));
         hitB = hitB && (ccw(P1, P2, vb) != ccw(P1, P2, eB));
     }
-#endif
     dcell = hitA ? r1.y : (hitB ? r1.z : r1.x);
     dk = hitA ? r2.x : (hitB ? r2.y : r1.w);
     dlo = hitA ? l1.y : (hitB ? l1.z : l1.x);
@@ -909,48 +875,16 @@ static constexpr int kRunLdsFixed = 256 + 256 + 64;      // crossing table, its 
 // Raised priority for the record's loads (they go out before other waves' arithmetic: their latency overlaps more of it) and
 // for the crossing path (the long stretch of a wave's chain, after which it can request its next operands): +1.1 ... +2.2 % on C3,
 // +1.6 % on C2, five interleaved rounds (profiles/r04y_prio_ab.txt); (3,3), (3,1), (1,3), (2,1) are within 0.3 % of (3,2), main
-// path high / the rest low is no better than no hint.  -DSITRK_PRIO_LOADS=0 -DSITRK_PRIO_CROSS=0 builds the loop without the hints.
-#ifndef SITRK_PRIO_LOADS
-#define SITRK_PRIO_LOADS 3
-#endif
-#ifndef SITRK_PRIO_CROSS
-#define SITRK_PRIO_CROSS 2
-#endif
-#ifndef SITRK_PRIO_BASE
-#define SITRK_PRIO_BASE 0
-#endif
-#ifndef SITRK_RUN_BLOCK
-#define SITRK_RUN_BLOCK 256             // workgroup size of the fused kernel (A/B: tools/build_variant.sh x -DSITRK_RUN_BLOCK=128 ...)
-#endif
-static constexpr int kRunBlock = SITRK_RUN_BLOCK;
-#ifndef SITRK_RUN_WAVES
-#define SITRK_RUN_WAVES 7               // 72 VGPRs, no scratch (the cell is stored behind a lane flag, crel and the row-below offset are
-#endif                                  // derived where they are used): +2.6 % over 6 waves; 8 waves (64 VGPRs) spill 32 registers
-#ifndef SITRK_RUN_WAVES_WINDOW
-#define SITRK_RUN_WAVES_WINDOW 6        // the form with per-buoy record windows carries two more registers: 9 spilled at 7 waves (13-25
-                                        // with the window packed into one register, as a single test, or as a predicate on the body)
-#endif
-// In-kernel stamps (diagnostic builds, `make DIAG=1`, knob "stamps"): where ONE wave's time goes inside a record.  s_memtime ticks
-// are shader cycles; the values go to a buffer nothing else reads.  SITRK_STAMP(k) closes interval k.
-#if defined(SITRK_DIAG) && defined(SITRK_NO_STAMPS)      // ablation builds that must keep the shipped register budget
-#define SITRK_STAMP_DECL const bool st_on = false;
-#define SITRK_STAMP_START
-#define SITRK_STAMP(k)
-#define SITRK_STAMP_FLUSH(widx)
-#elif defined(SITRK_DIAG)
-#define SITRK_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_t = 0; const bool st_on = ra.stamps != nullptr;
-#define SITRK_STAMP_START if (st_on) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_t) :: "memory"); }
-#define SITRK_STAMP(k) if (st_on) { unsigned long long st_n; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_n) :: "memory"); st_acc[k] += st_n - st_t; st_t = st_n; }
-#define SITRK_STAMP_FLUSH(widx) if (st_on && (threadIdx.x & 63u) == 0) { for (int q_ = 0; q_ < 8; q_++) ra.stamps[(size_t)(widx) * 8 + q_] = st_acc[q_]; }
-#else
-#define SITRK_STAMP_DECL
-#define SITRK_STAMP_START
-#define SITRK_STAMP(k)
-#define SITRK_STAMP_FLUSH(widx)
-#endif
+// path high / the rest low is no better than no hint.
+static constexpr int kPrioLoads = 3, kPrioCross = 2, kPrioBase = 0;
+static constexpr int kRunBlock = 256;   // workgroup size of the fused kernel
+static constexpr int kRunWaves = 7;     // 72 VGPRs, no scratch (the cell is stored behind a lane flag, crel and the row-below offset are
+                                        // derived where they are used): +2.6 % over 6 waves; 8 waves (64 VGPRs) spill 32 registers
+static constexpr int kRunWavesWindow = 6;   // the form with per-buoy record windows carries two more registers: 9 spilled at 7 waves
+                                            // (13-25 with the window packed into one register, as a single test, or as a predicate on the body)
 
 template <typename FT, int UVS, bool WINDOW>
-__global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_RUN_WAVES) void advect_run_kernel(RunArgs ra)
+__global__ __launch_bounds__(kRunBlock, WINDOW ? kRunWavesWindow : kRunWaves) void advect_run_kernel(RunArgs ra)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int *s_tab = (int *)smem;                            // CrossTab, 64 ints
@@ -1035,11 +969,9 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
     const char *ub_next = (const char *)ra.u[0], *vb_next = (const char *)ra.v[0], *kb_next = (const char *)ra.kill9[0];
     double k1000 = 1000.;                                // div1000's constant, kept in scalar registers
     asm volatile("" : "+s"(k1000));
-    SITRK_STAMP_DECL
 #pragma unroll 1
     for (int r = 0; r < ra.nrec; r++) {
         const int jrec = a.jrec + r;
-        SITRK_STAMP_START
         const char *ub = ub_next, *vb = vb_next, *kb = kb_next;
         const int rn = (r + 1 < ra.nrec) ? r + 1 : r;
         ub_next = (const char *)ra.u[rn]; vb_next = (const char *)ra.v[rn]; kb_next = (const char *)ra.kill9[rn];
@@ -1048,43 +980,12 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
             if (jrec > last) break;
         }
         // the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT]
-#if SITRK_PRIO_LOADS > 0                // the record's loads issued at raised wave priority
-        __builtin_amdgcn_s_setprio(SITRK_PRIO_LOADS);
-#endif
-#ifdef SITRK_ABL_VEL2                   // ablation (timing only, WRONG results): two velocity loads instead of three
-        FT fu1 = *(const FT *)(ub + x.o1), fu0 = fu1;
-        FT fv1 = *(const FT *)(vb + x.o1), fv0 = fv1;
-#else
+        __builtin_amdgcn_s_setprio(kPrioLoads);         // the record's loads issued at raised wave priority
         FT fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)), fu1 = *(const FT *)(ub + x.o1);
         FT fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))), fv1 = *(const FT *)(vb + x.o1);
-#endif
         // ... and the Survive byte of the cell's 8 neighbours for this record (used only if the buoy leaves the cell)
-#ifdef SITRK_ABL_NOK9                   // ablation (timing only, WRONG results): no Survive byte
-        unsigned k9 = 0; (void)kb;
-#else
         unsigned k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
-#endif
-#if SITRK_PRIO_LOADS > 0
-        __builtin_amdgcn_s_setprio(SITRK_PRIO_BASE);
-#endif
-#ifdef SITRK_ABL_VELCONST               // ablation (timing only, WRONG results): a uniform drift instead of the record's velocities, the
-        {                                   // loads kept as dependencies -- from global memory as shipped, or (SITRK_ABL_VELLDS) as LDS
-#ifdef SITRK_ABL_VELLDS                     // reads at a cell-dependent address: what staging u/v patches through LDS could buy at best
-            typedef __attribute__((address_space(3))) const float lds_cf;
-            const unsigned la_ = inl ? lo : geo_la;
-            const float l0 = *(lds_cf *)(uintptr_t)(la_ + kLdsBias), l1 = *(lds_cf *)(uintptr_t)(la_ + kLdsBias + 4),
-                        l2 = *(lds_cf *)(uintptr_t)(la_ + kLdsBias + 8), l3 = *(lds_cf *)(uintptr_t)(la_ + kLdsBias + 12);
-#else
-            const FT l0 = fu0, l1 = fu1, l2 = fv0, l3 = fv1;
-#endif
-            float cu0, cu1, cv0, cv1;       // 0.1 and 0.05 m/s, each "computed from" one loaded value
-            asm volatile("v_mov_b32 %0, 0x3dcccccd" : "=v"(cu0) : "v"(l0));
-            asm volatile("v_mov_b32 %0, 0x3dcccccd" : "=v"(cu1) : "v"(l1));
-            asm volatile("v_mov_b32 %0, 0x3d4ccccd" : "=v"(cv0) : "v"(l2));
-            asm volatile("v_mov_b32 %0, 0x3d4ccccd" : "=v"(cv1) : "v"(l3));
-            fu0 = (FT)cu0; fu1 = (FT)cu1; fv0 = (FT)cv0; fv1 = (FT)cv1;
-        }
-#endif
+        __builtin_amdgcn_s_setprio(kPrioBase);
         double zU, zV;
         FT su = 0, sv = 0;                               // UVS == 1: the selected candidates as loaded
         if (UVS == 0) {                                  // :423-425
@@ -1096,22 +997,10 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
         } else {                                         // :427-441
             // all four candidates are requested up front (pin_load: none is sunk into the branch that selects it)
             // intersect2Seg(P,F,C,D) = (ccw(P,C,D) != ccw(F,C,D)) and (ccw(P,F,C) != ccw(P,F,D)); ccw(F,C,D) is per cell
-#ifdef SITRK_DIAG
-            if (st_on) { pin_load(x.ori); pin_load(x.U11.y); pin_load(x.V11.y); pin_load(x.U10.y); pin_load(x.V01.y); pin_load(x.F11.y); pin_load(x.F00.y); }
-            SITRK_STAMP(0)                               // the cell's context is there (requested by the previous record's crossing path)
-#endif
             const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
             const bool llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
             const bool llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
-#ifdef SITRK_DIAG
-            if (st_on) { int b_ = (llum1 ? 1 : 0) | (llvm1 ? 2 : 0); asm volatile("" : "+v"(b_)); }
-            SITRK_STAMP(1)                               // the pick's orientation tests
-#endif
             pin_load(fu0); pin_load(fv0);
-#ifdef SITRK_DIAG
-            if (st_on) { pin_load(fu1); pin_load(fv1); }
-            SITRK_STAMP(2)                               // the record's velocities are there
-#endif
             su = llum1 ? fu0 : fu1;
             sv = llvm1 ? fv0 : fv1;
             zU = (double)su;
@@ -1120,31 +1009,18 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
         const double dx = zU * a.rdt;                    // :452-458
         const double dy = zV * a.rdt;
         pt Pn;
-#ifndef SITRK_EXACT_DIV
         if (UVS == 1 && sizeof(FT) == 4) {               // binary32 records: the range test of div1000 on the value as loaded
             Pn.x = P.x + div1000_of_f32(dx, (float)su, ra.f32_class, k1000);
             Pn.y = P.y + div1000_of_f32(dy, (float)sv, ra.f32_class, k1000);
-        } else
-#endif
-        {
-            Pn.x = P.x + SITRK_DIV1000(dx, k1000);
-            Pn.y = P.y + SITRK_DIV1000(dy, k1000);
+        } else {
+            Pn.x = P.x + div1000(dx, k1000);
+            Pn.y = P.y + div1000(dy, k1000);
         }
         moved = true;
         bool killed = false;
-#ifdef SITRK_DIAG
-        if (st_on) { pin_load(Pn.x); pin_load(Pn.y); }
-        SITRK_STAMP(3)                                   // Euler update
-#endif
-        const bool still_in = SITRK_INSIDE(Pn.y, Pn.x, x.F00, x.F01, x.F11, x.F10, a.eps_mg);
-#ifdef SITRK_DIAG
-        if (st_on) { int b_ = still_in ? 1 : 0; asm volatile("" : "+v"(b_)); }
-        SITRK_STAMP(4)                                   // cell test
-#endif
+        const bool still_in = inside_quad_hot(Pn.y, Pn.x, x.F00, x.F01, x.F11, x.F10, a.eps_mg);
         if (!still_in) {      // :466-484
-#if SITRK_PRIO_CROSS > 0                // the crossing path -- the long part of a wave's chain -- at raised priority
-            __builtin_amdgcn_s_setprio(SITRK_PRIO_CROSS);
-#endif
+            __builtin_amdgcn_s_setprio(kPrioCross);      // the crossing path -- the long part of a wave's chain -- at raised priority
             const unsigned kcell = x.o1 / (unsigned)sizeof(FT);
             int dcell, dk, dlo = 0;
             pin_load(k9);
@@ -1166,15 +1042,9 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
             inl = patch_covers(pa, crel >> 16, crel & 0xffff);
             if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell + (unsigned)dk, lo, x);
             else load_ctx<sizeof(FT)>(a, gb, kcell + (unsigned)dk, x);
-#if SITRK_PRIO_CROSS > 0
-            __builtin_amdgcn_s_setprio(SITRK_PRIO_BASE);
-#endif
+            __builtin_amdgcn_s_setprio(kPrioBase);
         }
         P = Pn;
-#ifdef SITRK_DIAG
-        if (st_on) { int b_ = c; asm volatile("" : "+v"(b_)); }
-        SITRK_STAMP(5)                                   // crossing path (resolution; the new context is requested, not waited for)
-#endif
         if (killed) {
             c |= SITRK_DEAD_BIT;
             unsigned tk = threadIdx.x;
@@ -1183,7 +1053,6 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
             break;                                       // dead buoys never step again
         }
     }
-    SITRK_STAMP_FLUSH((size_t)blk * (kRunBlock / 64) + (threadIdx.x >> 6))
     // (the buoy's index is recomputed here rather than kept: 16 bytes of state addresses per lane would be spilled to
     // scratch across the loop, i.e. written and read back through HBM)
     unsigned tid = threadIdx.x;
@@ -1195,59 +1064,6 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? SITRK_RUN_WAVES_WINDOW : SITRK_
     }
     if (recelled) a.cell[pe] = c;
 }
-
-#ifdef SITRK_DIAG
-// ---------------------------------------------------------------------------
-// ABLATION KERNELS (diagnostic builds only, `make DIAG=1`; results are WRONG by design).
-//   memonly : issues exactly the loads/stores of the hot path, no predicates  -> memory-side time
-//   nocross : the hot path without CrossedEdge/NewHostCell/Survive            -> price of the crossing path
-// ---------------------------------------------------------------------------
-template <typename FT>
-__global__ __launch_bounds__(kBlock) void advect_memonly_kernel(StepArgs a)
-{
-    int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= a.nP) return;
-    int32_t c = a.cell[p];
-    if (c < 0) return;
-    const int Ni = a.Ni;
-    const size_t k = (size_t)cell_j(c) * Ni + cell_i(c);
-    const FT *__restrict__ u = (const FT *)a.u;
-    const FT *__restrict__ v = (const FT *)a.v;
-    const pt P = a.pos[p];
-    const CellGeo g11 = a.geo[k];
-    const pt F10 = a.geo[k - 1].f, U10 = a.geo[k - 1].u, F01 = a.geo[k - Ni].f, V01 = a.geo[k - Ni].v, F00 = a.geo[k - Ni - 1].f;
-    const double s = (double)u[k] + (double)u[k - 1] + (double)v[k] + (double)v[k - Ni];
-    pt Pn;
-    Pn.y = P.y + 1e-300 * (g11.f.y + g11.u.y + g11.v.y + F10.y + U10.y + F01.y + V01.y + F00.y + s);
-    Pn.x = P.x + 1e-300 * (g11.f.x + g11.u.x + g11.v.x + F10.x + U10.x + F01.x + V01.x + F00.x);
-    a.pos[p] = Pn;
-}
-
-template <typename FT>
-__global__ __launch_bounds__(kBlock) void advect_nocross_kernel(StepArgs a)
-{
-    int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= a.nP) return;
-    int32_t c = a.cell[p];
-    if (c < 0) return;
-    const int Ni = a.Ni;
-    const size_t k = (size_t)cell_j(c) * Ni + cell_i(c);
-    const FT *__restrict__ u = (const FT *)a.u;
-    const FT *__restrict__ v = (const FT *)a.v;
-    const pt P = a.pos[p];
-    const CellGeo g11 = a.geo[k];
-    const pt F10 = a.geo[k - 1].f, U10 = a.geo[k - 1].u, F01 = a.geo[k - Ni].f, V01 = a.geo[k - Ni].v, F00 = a.geo[k - Ni - 1].f;
-    const double u1 = (double)u[k], u0 = (double)u[k - 1], v1 = (double)v[k], v0 = (double)v[k - Ni];
-    const bool llum1 = intersect2seg(P, g11.f, V01, g11.v);
-    const bool llvm1 = intersect2seg(P, g11.f, U10, g11.u);
-    const double zU = llum1 ? u0 : u1, zV = llvm1 ? v0 : v1;
-    pt Pn;
-    Pn.x = P.x + (zU * a.rdt) / 1000.;
-    Pn.y = P.y + (zV * a.rdt) / 1000.;
-    a.pos[p] = Pn;
-    if (!inside_quad(Pn.y, Pn.x, F00, F01, g11.f, F10)) a.cell[p] = c ^ 1;      // keep the test alive, skip the rest
-}
-#endif  // SITRK_DIAG
 
 // ---------------------------------------------------------------------------
 // Predicate probes: the device functions of the hot path evaluated on plain arrays, so that the parity
@@ -1277,12 +1093,10 @@ __global__ void eval_euler_kernel(int64_t n, const double *__restrict__ r, const
     const double w = vel[k];
     const double d = w * rdt;
     const float wf = (float)w;
-    double q = SITRK_DIV1000(d);
-#ifndef SITRK_EXACT_DIV
+    double q = div1000(d);
     double k1000 = 1000.;
     asm volatile("" : "+s"(k1000));
     if ((double)wf == w) q = div1000_of_f32(d, wf, f32_class, k1000);
-#endif
     out[k] = r[k] + q;
 }
 

@@ -4,9 +4,8 @@
     python tools/ab_tune.py [--steps 200] [--rounds 5] [--knobs xcd_remap,nt_state] [--tiles 8x16,16x16]
                             [--fuse 2,4,8] [--values step_block:256:512:1024] [--base fuse=1,nt_state=1]
 Knobs (sitrk_set_tuning): xcd_remap, nt_state (0/1), sort_tile (tile_j*256+tile_i), fuse (1..32), step_block
-(256/512/1024), locate_bruteforce; with `make -C sitrack_amd/csrc -B DIAG=1` also the ablation kernels
-diag_memonly / diag_nocross (--singles).  Prints median / min ms per record for every variant; results must not
-depend on knobs (checked on the final state against the first variant).  This is how the defaults in
+(256/512/1024), survive_tile, locate_bruteforce.  Prints median / min ms per record for every variant; results must not
+depend on knobs (checked on the final state against the first variant; --singles variants are not checked).  This is how the defaults in
 sitrk_internal.h were chosen."""
 import argparse
 import itertools
@@ -33,7 +32,7 @@ def main():
     ap.add_argument("--fuse", default="", help="comma list of records-per-launch values to add as variants, e.g. 2,4,8")
     ap.add_argument("--values", default="", help="knob:v1:v2:... extra variants sweeping one knob's values, e.g. step_block:512:1024")
     ap.add_argument("--base", default="", help="knob=value,... applied to every variant")
-    ap.add_argument("--singles", default="", help="extra variants, one knob each (e.g. diag_memonly,diag_nocross); no result check")
+    ap.add_argument("--singles", default="", help="extra variants, one knob each (e.g. survive_tile); no result check")
     a = ap.parse_args()
     N, nP, K = a.grid, a.buoys, 8
     grid = syn.make_grid(N, N, dkm=4.0, warp=0.0)

@@ -3,7 +3,7 @@
 // kind (8 accumulators per lane, no memory traffic) from 8 waves per SIMD on every SIMD of the chip; the shader clock during the
 // kernel comes from s_memtime (shader cycles) against s_memrealtime (100 MHz).  Output: one JSON line per instruction kind with
 // Ginst/s (wave-instructions) and cycles per instruction per SIMD at the clock the chip held.
-//   hipcc --offload-arch=gfx950 -O2 -o build_ab/valu_issue tools/microbench/valu_issue.hip && build_ab/valu_issue
+//   mkdir -p build && hipcc --offload-arch=gfx950 -O2 -o build/valu_issue tools/microbench/valu_issue.hip && build/valu_issue
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

@@ -4,6 +4,7 @@
 # PMC passes are collected on their own (no trace domains), one counter group per pass, as
 # MI355X_MICROARCH.md (HBM / rocprofv3 PMC slots) prescribes.
 set -o pipefail
+[ -n "$SITRK_LIB_PATH" ] && { echo "profile_gpu.sh: SITRK_LIB_PATH is set, but the profile is filed under the default build's fingerprint: unset it"; exit 2; }
 TAG=${1:-r01}; shift
 ARGS=${@:---steps 128 --warmup 32 --no-cpu-baseline --no-c2 --only-fused}      # multiples of the 32 records per launch: every fused dispatch is a full one
 export TMPDIR=/tmp
