@@ -85,6 +85,26 @@ int sitrk_set_grid(sitrk_t *h, int Nj, int Ni,
  * projection on the segment joining them. */
 int sitrk_set_params(sitrk_t *h, double rdt, int uv_strategy, double rmin_conc);
 
+/* Sub-stepped advection (an EXTRA the reference does not have: it does one Euler step per model record, which is right only
+ * while a buoy crosses less than one cell per record, i.e. for hourly output).  1 <= nsub <= 1024 (else SITRK_EINVAL), default
+ * 1; may be called before or after sitrk_set_params, in any order.  With nsub = n and period rdt:
+ *   - one model record jrec advances every buoy its gate admits (alive, jrec inside [rec_first, rec_last]) by n sub-steps;
+ *   - each sub-step is EXACTLY one reference step (the per-buoy body of si3_part_tracker.py:382-484) with dt = rdt / n, one
+ *     rounded fp64 division done once on the host at launch: velocity pick at the buoy's current position and host cell,
+ *     Euler update, IsInsideQuadrangle, CrossedEdge / NewHostCell / UpdtInd4NewCell, Survive -- all with that record's u, v
+ *     and siconc (its Survive bytes);
+ *   - all sub-steps of a record are gated by the same jrec; a buoy killed in sub-step s takes no further sub-step and its
+ *     kill_rec is jrec.
+ * Equivalently: the reference loop body run n times per record with rdt/n and the same record fields.
+ * Per-record output (sitrk_fetch_record): the position after the buoy's last sub-step in that record, mask 1, if it took at
+ * least one sub-step there (a buoy killed mid-record keeps its death position with mask 1); FillValue and mask 0 otherwise.
+ * With nsub > 1, sitrk_run and sitrk_step launch advect_substep_kernel (counted as fused launches by sitrk_launch_stats;
+ * sitrk_step = one launch of one record).  Where the fused kernels do not apply (buoys set in the two outermost rows or
+ * columns, meshes beyond 2^32 bytes of geometry) the one-record kernel is launched n times per record with dt = rdt / n
+ * (counted as n one-record launches).  nsub = 1 launches exactly what it launched before.
+ * A host cell moves up to nsub cells per record: see the row-band and box rules below (D). */
+int sitrk_set_substeps(sitrk_t *h, int nsub);
+
 /* performance knobs; they never change results.  "xcd_remap" (0/1): each XCD walks a
  * contiguous chunk of the cell-sorted buoys; "nt_state" (0/1): non-temporal loads/stores for
  * the once-per-step position/cell streams; "sort_tile" (tile_j*256 + tile_i, 0 = row-major):
@@ -141,8 +161,9 @@ int   sitrk_commit_record(sitrk_t *h, int slot);
  * Each rank of a multi-GPU run can thus ingest only the band of its own buoys: no collective at all.
  * The library remembers which rows of a slot are valid and checks every step against them: stepping with a partly
  * uploaded slot needs sitrk_buoy_rows() to have been evaluated since sitrk_set_buoys(), and fails with SITRK_EINVAL when
- * [jmin-2-age, jmax+3+age) (age = records stepped since that evaluation; record r of a fused sitrk_run counts age+r) is
- * not inside the uploaded rows.  Slots are allocated with every Survive byte = kill and every field value = NaN. */
+ * [jmin-2-D, jmax+3+D) is not inside the uploaded rows, where a = records stepped since that evaluation (record r of a fused
+ * sitrk_run counts a+r) and D = (a+1)*nsub - 1 (sitrk_set_substeps: a host cell moves by at most one row per SUB-step;
+ * nsub = 1 gives D = a).  Slots are allocated with every Survive byte = kill and every field value = NaN. */
 int sitrk_buoy_rows(sitrk_t *h, int32_t *jmin, int32_t *jmax);
 int sitrk_push_record_rows(sitrk_t *h, int slot, int j0, int j1, const void *u_rows, const void *v_rows, const void *sic_rows);
 /* same derivation for rows [j0,j1) that the caller wrote in place through sitrk_record_ptr (device-side copies) */
@@ -162,8 +183,9 @@ int sitrk_commit_record_rows(sitrk_t *h, int slot, int j0, int j1);
  *   sitrk_commit_record_box   the slab already sits in device memory (written through sitrk_record_ptr: an RCCL broadcast, a
  *                             device-side producer): derive the Survive bytes of the box only, and treat the slot as holding
  *                             that box from now on
- * The library remembers the box a slot holds and checks every step against it exactly like the row bands: age records after
- * sitrk_buoy_box() the slot must hold rows [jmin-2-age, jmax+3+age) and columns [imin-2-age, imax+3+age), else SITRK_EINVAL.
+ * The library remembers the box a slot holds and checks every step against it exactly like the row bands: a records after
+ * sitrk_buoy_box() the slot must hold rows [jmin-2-D, jmax+3+D) and columns [imin-2-D, imax+3+D), D = (a+1)*nsub - 1 (= a
+ * without sub-steps), else SITRK_EINVAL.  The *age of sitrk_buoy_box_end counts records, not sub-steps.
  * sitrk_buoy_rows() evaluates the columns too (a row band is a box of full width). */
 int sitrk_buoy_box(sitrk_t *h, int32_t *jmin, int32_t *jmax, int32_t *imin, int32_t *imax);
 int sitrk_push_record_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1, const void *u_box, const void *v_box, const void *sic_box,
@@ -219,8 +241,8 @@ int sitrk_step(sitrk_t *h, int slot, int jrec);
  * (knob "fuse"; never across a re-sort or the slot ring).  Buoy sets with per-buoy record windows run the kernel form
  * without the window test for every launch whose records lie inside all windows. */
 int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps);
-/* What sitrk_run / sitrk_step really launched since the last reset: fused launches of advect_run_kernel, the records
- * they advanced in total (a launch is cut short at a re-sort and at the end of a run), and one-record launches of
+/* What sitrk_run / sitrk_step really launched since the last reset: fused launches of advect_run_kernel (or, with
+ * nsub > 1, of advect_substep_kernel), the records they advanced in total (a launch is cut short at a re-sort and at the end of a run), and one-record launches of
  * advect_step_kernel.  Any pointer may be NULL.  bench.py prices its roofline per launch from these. */
 int sitrk_launch_stats(sitrk_t *h, int reset, int64_t *fused_launches, int64_t *fused_records, int64_t *step_launches);
 

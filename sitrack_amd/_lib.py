@@ -33,6 +33,7 @@ _SIGNATURES = {
     "sitrk_set_stream": (_int, [_vp, _vp]),
     "sitrk_set_grid": (_int, [_vp, _int, _int] + [_vp] * 7),
     "sitrk_set_params": (_int, [_vp, _dbl, _int, _dbl]),
+    "sitrk_set_substeps": (_int, [_vp, _int]),
     "sitrk_set_tuning": (_int, [_vp, C.c_char_p, _int]),
     "sitrk_alloc_records": (_int, [_vp, _int, _int]),
     "sitrk_push_record": (_int, [_vp, _int, _vp, _vp, _vp]),
@@ -155,6 +156,12 @@ def as_c(a, dtype, shape=None, name="array"):
     return b
 
 
+def reach(age, nsub=1):
+    """The band/box rule of include/sitrk.h: `age` records after the buoys' host cells were evaluated, a buoy can start its
+    step D = (age+1)*nsub - 1 cells away from them (a host cell moves at most one cell per sub-step; D = age for nsub = 1)."""
+    return (int(age) + 1) * int(nsub) - 1
+
+
 class Context:
     """Owns one sitrk_t handle (= one GPU)."""
 
@@ -170,6 +177,7 @@ class Context:
         self.nP = 0
         self.nslots = 0
         self.field_dtype = None
+        self.nsub = 1
 
     # -- plumbing
     def _chk(self, rc):
@@ -216,6 +224,16 @@ class Context:
 
     def set_params(self, rdt=3600., uv_strategy=1, rmin_conc=0.1):
         self._chk(self._L.sitrk_set_params(self._h, float(rdt), int(uv_strategy), float(rmin_conc)))
+
+    def set_substeps(self, nsub):
+        """Advance every record in `nsub` Euler sub-steps of rdt/nsub (sitrk_set_substeps; 1 = the reference's one step)."""
+        self._chk(self._L.sitrk_set_substeps(self._h, int(nsub)))
+        self.nsub = int(nsub)
+
+    def reach(self, age=0):
+        """D: how many cells away from its host cell at the last buoy_rows()/buoy_box() evaluation a buoy can start the
+        step of the record `age` records after it -- one cell per sub-step, (age+1)*nsub - 1 (= age without sub-steps)."""
+        return reach(age, self.nsub)
 
     def set_tuning(self, **knobs):
         for k, v in knobs.items():
@@ -295,12 +313,14 @@ class Context:
         return a.value, b.value
 
     def band(self, age=0):
-        """Rows [j0,j1) of a record the next step(s) can touch: [jmin-2-age, jmax+3+age) clipped to the grid, where `age`
-        = number of records stepped since buoy_rows() was evaluated (a host cell moves at most one row per record)."""
+        """Rows [j0,j1) of a record the next step(s) can touch: [jmin-2-D, jmax+3+D) clipped to the grid, where `age`
+        = number of records stepped since buoy_rows() was evaluated and D = reach(age) (a host cell moves at most one row
+        per sub-step)."""
         jmin, jmax = self.buoy_rows()
         if jmin > jmax:
             return 0, 0
-        return max(0, jmin - 2 - age), min(self.Nj, jmax + 3 + age)
+        d = reach(age, self.nsub)
+        return max(0, jmin - 2 - d), min(self.Nj, jmax + 3 + d)
 
     def buoy_box(self):
         """(jmin, jmax, imin, imax) of the host cells of the buoys still alive; jmin > jmax when there is none."""
@@ -309,19 +329,21 @@ class Context:
         return tuple(x.value for x in v)
 
     def box(self, age=0, align=4):
-        """The box (j0, j1, i0, i1) of a record the next step(s) can touch: rows [jmin-2-age, jmax+3+age) x columns
-        [imin-2-age, imax+3+age) clipped to the grid, the columns widened to multiples of `align` (16-byte lines of an fp32
-        row).  `age` = records stepped since (a host cell moves at most one row and one column per record)."""
+        """The box (j0, j1, i0, i1) of a record the next step(s) can touch: rows [jmin-2-D, jmax+3+D) x columns
+        [imin-2-D, imax+3+D) clipped to the grid, the columns widened to multiples of `align` (16-byte lines of an fp32
+        row).  `age` = records stepped since, D = reach(age) (a host cell moves at most one row and one column per
+        sub-step)."""
         jmin, jmax, imin, imax = self.buoy_box()
         return self.box_of(jmin, jmax, imin, imax, age, align)
 
     def box_of(self, jmin, jmax, imin, imax, age=0, align=4):
         if jmin > jmax:
             return 0, 0, 0, 0
-        i0, i1 = max(0, imin - 2 - age), min(self.Ni, imax + 3 + age)
+        d = reach(age, getattr(self, "nsub", 1))
+        i0, i1 = max(0, imin - 2 - d), min(self.Ni, imax + 3 + d)
         i0 -= i0 % align
         i1 = min(self.Ni, -(-i1 // align) * align)
-        return max(0, jmin - 2 - age), min(self.Nj, jmax + 3 + age), i0, i1
+        return max(0, jmin - 2 - d), min(self.Nj, jmax + 3 + d), i0, i1
 
     def push_record_box(self, slot, j0, j1, i0, i1, u_box, v_box, sic_box):
         """The box rows [j0,j1) x columns [i0,i1) of a record from three (j1-j0, i1-i0) arrays.  Views into whole fields

@@ -229,6 +229,14 @@ SITRK_API int sitrk_set_params(sitrk_t *h, double rdt, int uv_strategy, double r
     return SITRK_OK;
 }
 
+SITRK_API int sitrk_set_substeps(sitrk_t *h, int nsub)
+{
+    NEED(h, "null handle");
+    NEED(nsub >= 1 && nsub <= 1024, "sitrk_set_substeps: nsub must be in 1..1024");
+    h->nsub = nsub;
+    return SITRK_OK;
+}
+
 SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
 {
     NEED(h, "null handle");
@@ -846,7 +854,8 @@ SITRK_API int sitrk_push_record_dev(sitrk_t *h, int slot, const void *slab_dev)
 
 // A slot that holds only a box of its record may be stepped with only while every live buoy is provably inside the box:
 // rows [jmin-2-age, jmax+3+age) and columns [imin-2-age, imax+3+age) with (jmin,jmax,imin,imax) from the last
-// sitrk_buoy_rows() / sitrk_buoy_box() and age = records stepped since.
+// sitrk_buoy_rows() / sitrk_buoy_box() and age = records stepped since (widened to D = (age+1)*nsub - 1 cells when each record
+// is advanced in nsub sub-steps).
 static int check_band(sitrk_ctx *h, int slot, int extra_age)
 {
     const int lo = h->slot_row_lo[slot], hi = h->slot_row_hi[slot], clo = h->slot_col_lo[slot], chi = h->slot_col_hi[slot];
@@ -855,15 +864,18 @@ static int check_band(sitrk_ctx *h, int slot, int extra_age)
         return fail(h, SITRK_EINVAL, "slot %d holds rows [%d,%d) x columns [%d,%d) only: call sitrk_buoy_rows() / sitrk_buoy_box() after "
                     "sitrk_set_buoys() so that the box can be checked", slot, lo, hi, clo, chi);
     if (h->band_jmin > h->band_jmax) return SITRK_OK;       // no live buoy
-    const int age = h->band_age + extra_age;
+    // a host cell moves at most one row and one column per sub-step: record a = age after the evaluation ends nsub*(a+1) sub-steps
+    // after it, so its step can start D = (a+1)*nsub - 1 cells away (D = a for nsub = 1)
+    const int a_rec = h->band_age + extra_age;
+    const int age = (int)std::min<int64_t>((int64_t)(a_rec + 1) * h->nsub - 1, (int64_t)1 << 30);
     const int need_lo = std::max(0, h->band_jmin - 2 - age), need_hi = std::min(h->Nj, h->band_jmax + 3 + age);
     if (lo > need_lo || hi < need_hi)
-        return fail(h, SITRK_EINVAL, "slot %d holds rows [%d,%d) but the buoys (rows %d..%d, %d records ago) can touch rows [%d,%d)",
-                    slot, lo, hi, h->band_jmin, h->band_jmax, age, need_lo, need_hi);
+        return fail(h, SITRK_EINVAL, "slot %d holds rows [%d,%d) but the buoys (rows %d..%d, %d records ago, %d sub-steps per record) can touch rows [%d,%d)",
+                    slot, lo, hi, h->band_jmin, h->band_jmax, a_rec, h->nsub, need_lo, need_hi);
     const int cneed_lo = std::max(0, h->band_imin - 2 - age), cneed_hi = std::min(h->Ni, h->band_imax + 3 + age);
     if (clo > cneed_lo || chi < cneed_hi)
-        return fail(h, SITRK_EINVAL, "slot %d holds columns [%d,%d) but the buoys (columns %d..%d, %d records ago) can touch columns [%d,%d)",
-                    slot, clo, chi, h->band_imin, h->band_imax, age, cneed_lo, cneed_hi);
+        return fail(h, SITRK_EINVAL, "slot %d holds columns [%d,%d) but the buoys (columns %d..%d, %d records ago, %d sub-steps per record) can touch columns [%d,%d)",
+                    slot, clo, chi, h->band_imin, h->band_imax, a_rec, h->nsub, cneed_lo, cneed_hi);
     return SITRK_OK;
 }
 
@@ -1043,6 +1055,16 @@ static void launch_step(sitrk_ctx *h, const StepArgs &a)
     else launch_step_b<FT, 256>(h, a);
 }
 
+// the fused kernels address the geometry with 32-bit byte offsets and have no negative-index wrap: buoy sets seeded in the two
+// outermost rows/columns (the reference itself cancels such seeds, tracking.py:73) and meshes beyond 2^32 / 48 cells
+// (9 460 x 9 460) are stepped record by record with the one-record kernel
+static inline bool fused_ok(const sitrk_ctx *h)
+{
+    return !h->rim_buoys && (uint64_t)h->Nj * h->Ni * sizeof(CellGeo) < ((uint64_t)1 << 32);
+}
+
+static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m);
+
 SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
 {
     NEED(h, "null handle");
@@ -1064,6 +1086,7 @@ SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
     if (rc) return rc;
     rc = slot_wait_sv(h, slot);
     if (rc) return rc;
+    if (h->nsub > 1 && fused_ok(h)) return launch_records(h, slot, jrec, 1);      // the sub-stepping kernel with one record
     const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
     const char *slab = slab_of(h, slot);
     BuoyState &s = h->st[h->cur];
@@ -1073,13 +1096,18 @@ SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
     a.geo = h->geo; a.orient = h->orient; a.kill = h->kill9 + (size_t)slot * n;
     a.u = slab; a.v = slab + n * es;
     a.pos = s.pos; a.cell = s.cell; a.kill_rec = s.kill_rec; a.win = s.win;
-    if (h->dtype == SITRK_F64) launch_step<double>(h, a);
-    else launch_step<float>(h, a);
-    HIPCHK(hipGetLastError());
+    // nsub > 1 where the fused kernels do not apply (buoys in the two outermost rows/columns, meshes beyond 2^32 bytes of geometry):
+    // the one-record kernel nsub times with dt_sub and the same jrec -- the same sub-steps, one launch each
+    if (h->nsub > 1) a.rdt = h->rdt / h->nsub;
+    for (int sub = 0; sub < h->nsub; sub++) {
+        if (h->dtype == SITRK_F64) launch_step<double>(h, a);
+        else launch_step<float>(h, a);
+        HIPCHK(hipGetLastError());
+    }
     rc = launch_mark(h, &slot, 1);
     if (rc) return rc;
     h->steps_since_sort++;
-    h->n_step_launches++;
+    h->n_step_launches += h->nsub;
     if (h->band_age >= 0) h->band_age++;
     if (h->box_pending) h->box_pending_age++;
     return SITRK_OK;
@@ -1111,6 +1139,77 @@ static void launch_run(sitrk_ctx *h, const RunArgs &ra)
     }
 }
 
+template <typename FT>
+static void launch_substep(sitrk_ctx *h, const RunArgs &ra, int nsub)
+{
+    dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
+    const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
+    const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
+    if (h->uv_strategy == 1) {
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 1, true>), grid, block, lds, h->stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 1, false>), grid, block, lds, h->stream, ra, nsub);
+    } else if (h->uv_strategy == 2) {
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 2, true>), grid, block, lds, h->stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 2, false>), grid, block, lds, h->stream, ra, nsub);
+    } else {
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 0, true>), grid, block, lds, h->stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 0, false>), grid, block, lds, h->stream, ra, nsub);
+    }
+}
+
+// records jrec0 .. jrec0+m-1 from slots (slot_first + r) % nslots in ONE launch: advect_run_kernel (nsub == 1) or
+// advect_substep_kernel (nsub > 1, also for m == 1: sitrk_step).  Both are counted as fused launches.
+static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m)
+{
+    BuoyState &s = h->st[h->cur];
+    const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
+    const double dt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;        // dt_sub: one rounded division
+    RunArgs ra;
+    ra.s.nP = h->nP; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0;
+    ra.s.rdt = dt; ra.s.rmin_conc = h->rmin_conc; ra.s.eps_mg = h->eps_mg; ra.s.geo = h->geo; ra.s.orient = h->orient; ra.s.kill = nullptr; ra.s.u = ra.s.v = nullptr;
+    ra.s.pos = s.pos; ra.s.cell = s.cell; ra.s.kill_rec = s.kill_rec; ra.s.win = s.win;
+    ra.nrec = m;
+    make_cross_tab(h->Ni, ra.tab, ra.dji);
+    ra.geoF = h->geoF;
+    ra.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
+    ra.patch_margin = h->patch_margin;
+    ra.xcd_group = h->xcd_group;
+    ra.f32_class = f32_class_for(dt);
+    int used[kMaxFuse];
+    for (int r = 0; r < m; r++) {
+        const int slot = (slot_first + r) % h->nslots;
+        used[r] = slot;
+        int rc = check_band(h, slot, r);
+        if (rc) return rc;
+        if (h->slot_dirty[slot]) {
+            rc = derive_mask(h, slot);
+            if (rc) return rc;
+        }
+        rc = slot_wait_upload(h, slot);
+        if (rc) return rc;
+        rc = slot_wait_sv(h, slot);
+        if (rc) return rc;
+        const char *slab = slab_of(h, slot);
+        ra.u[r] = slab; ra.v[r] = slab + n * es; ra.kill9[r] = h->kill9 + (size_t)slot * n;
+    }
+    if (h->nsub > 1) {
+        if (h->dtype == SITRK_F64) launch_substep<double>(h, ra, h->nsub);
+        else launch_substep<float>(h, ra, h->nsub);
+    } else {
+        if (h->dtype == SITRK_F64) launch_run<double>(h, ra);
+        else launch_run<float>(h, ra);
+    }
+    HIPCHK(hipGetLastError());
+    int rc = launch_mark(h, used, m);
+    if (rc) return rc;
+    h->steps_since_sort += m;
+    h->n_fused_launches++;
+    h->n_fused_records += m;
+    if (h->band_age >= 0) h->band_age += m;
+    if (h->box_pending) h->box_pending_age += m;
+    return SITRK_OK;
+}
+
 SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
 {
     NEED(h, "null handle");
@@ -1120,11 +1219,7 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
     NEED(h->st[0].pos, "sitrk_run: call sitrk_set_buoys first");
     if (h->nP == 0) return SITRK_OK;
     int fuse = std::max(1, std::min(std::min(h->fuse, kMaxFuse), h->nslots));    // a launch never wraps the slot ring
-    // the fused kernel addresses the geometry with 32-bit byte offsets and has no negative-index wrap: buoy sets seeded in
-    // the two outermost rows/columns (the reference itself cancels such seeds, tracking.py:73) and meshes beyond
-    // 2^32 / 48 cells (9 460 x 9 460) are stepped record by record
-    if (h->rim_buoys || (uint64_t)h->Nj * h->Ni * sizeof(CellGeo) >= ((uint64_t)1 << 32)) fuse = 1;
-    const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
+    if (!fused_ok(h)) fuse = 1;
     int k = 0;
     while (k < nsteps) {
         if (h->resort_every > 0 && h->steps_since_sort >= h->resort_every) {
@@ -1140,45 +1235,8 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
             continue;
         }
         // m consecutive records, all resident in distinct slots, in one launch
-        BuoyState &s = h->st[h->cur];
-        RunArgs ra;
-        ra.s.nP = h->nP; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0 + k;
-        ra.s.rdt = h->rdt; ra.s.rmin_conc = h->rmin_conc; ra.s.eps_mg = h->eps_mg; ra.s.geo = h->geo; ra.s.orient = h->orient; ra.s.kill = nullptr; ra.s.u = ra.s.v = nullptr;
-        ra.s.pos = s.pos; ra.s.cell = s.cell; ra.s.kill_rec = s.kill_rec; ra.s.win = s.win;
-        ra.nrec = m;
-        make_cross_tab(h->Ni, ra.tab, ra.dji);
-        ra.geoF = h->geoF;
-        ra.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
-        ra.patch_margin = h->patch_margin;
-        ra.xcd_group = h->xcd_group;
-        ra.f32_class = f32_class_for(h->rdt);
-        int used[kMaxFuse];
-        for (int r = 0; r < m; r++) {
-            const int slot = (slot0 + k + r) % h->nslots;
-            used[r] = slot;
-            int rc = check_band(h, slot, r);
-            if (rc) return rc;
-            if (h->slot_dirty[slot]) {
-                rc = derive_mask(h, slot);
-                if (rc) return rc;
-            }
-            rc = slot_wait_upload(h, slot);
-            if (rc) return rc;
-            rc = slot_wait_sv(h, slot);
-            if (rc) return rc;
-            const char *slab = slab_of(h, slot);
-            ra.u[r] = slab; ra.v[r] = slab + n * es; ra.kill9[r] = h->kill9 + (size_t)slot * n;
-        }
-        if (h->dtype == SITRK_F64) launch_run<double>(h, ra);
-        else launch_run<float>(h, ra);
-        HIPCHK(hipGetLastError());
-        int rc = launch_mark(h, used, m);
+        int rc = launch_records(h, (slot0 + k) % h->nslots, jrec0 + k, m);
         if (rc) return rc;
-        h->steps_since_sort += m;
-        h->n_fused_launches++;
-        h->n_fused_records += m;
-        if (h->band_age >= 0) h->band_age += m;
-        if (h->box_pending) h->box_pending_age += m;
         k += m;
     }
     return SITRK_OK;

@@ -103,6 +103,7 @@ struct sitrk_ctx {
 
     // parameters
     double rdt = 3600.0;
+    int nsub = 1;                       // Euler sub-steps per record (sitrk_set_substeps); dt_sub = rdt / nsub at launch
     int uv_strategy = 1;
     double rmin_conc = 0.1;
     double eps_mg = 0.0;                // 2^-48 * max |Yf|,|Xf| (inside_quad_hot)

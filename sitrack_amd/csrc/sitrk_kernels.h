@@ -1066,7 +1066,201 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? kRunWavesWindow : kRunWaves) vo
 }
 
 // ---------------------------------------------------------------------------
-// Predicate probes: the device functions of the hot path evaluated on plain arrays, so that the parity
+// Sub-stepped advection (sitrk_set_substeps, nsub > 1): the fused loop with an inner loop of `nsub` Euler sub-steps per
+// record.  ra.s.rdt and ra.f32_class are those of the sub-step dt_sub = rdt / nsub (the host divides once).  Every sub-step
+// is the reference's per-buoy body with dt_sub and the record's fields: velocity pick at the current position, Euler update,
+// inside test, crossing + Survive.  The four velocity candidates and the Survive byte of the host cell are loaded at the top
+// of a record and again only after a crossing (a cell change): while the buoy stays in its cell they are the same values.
+// A buoy killed in sub-step s takes no further sub-step; all sub-steps of a record are gated by the same record window.
+// Same operations on the same operands in the same order as advect_run_kernel, sub-step by sub-step.  The LDS patch is the
+// same: a buoy now moves up to nsub cells per record, so it leaves the patch sooner and then reads global memory
+// (patch_covers is tested at every crossing, as there).
+// ---------------------------------------------------------------------------
+// the candidates and k9 live across the sub-step loop: 80 VGPRs at 6 waves/SIMD for binary32 records without the window test
+// (7 waves would spill), 5 waves (up to 96 VGPRs) for fp64 records (16 B/lane of scratch at 6) and for the window form
+static constexpr int kSubWaves = 6;
+static constexpr int kSubWavesWide = 5;
+
+template <typename FT, int UVS, bool WINDOW>
+__global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesWide : kSubWaves) void advect_substep_kernel(RunArgs ra, int nsub)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int *s_tab = (int *)smem;
+    int *s_tabL = s_tab + 64;
+    int *s_box = s_tabL + 64;
+    const StepArgs &a = ra.s;
+    const unsigned blk = (a.tune & TUNE_XCD_REMAP) ? xcd_remap(blockIdx.x, gridDim.x)
+                         : (ra.xcd_group > 1 ? xcd_group(blockIdx.x, gridDim.x, (unsigned)ra.xcd_group) : blockIdx.x);
+    const int64_t p = (int64_t)blk * kRunBlock + threadIdx.x;
+    const bool nt = (a.tune & TUNE_NT_STATE) != 0;
+    int32_t c = -1;
+    if (p < a.nP) c = nt ? __builtin_nontemporal_load(&a.cell[p]) : a.cell[p];
+    const bool live = c >= 0;
+    if (threadIdx.x < 64) s_tab[threadIdx.x] = ((const int *)&ra.tab)[threadIdx.x];
+    if (threadIdx.x == 0) { s_box[0] = 0x7fffffff; s_box[1] = -1; s_box[2] = 0x7fffffff; s_box[3] = -1; }
+    __syncthreads();
+    {
+        int jlo = live ? cell_j(c) : 0x7fffffff, jhi = live ? cell_j(c) : -1, ilo = live ? cell_i(c) : 0x7fffffff, ihi = live ? cell_i(c) : -1;
+        for (int off = 32; off > 0; off >>= 1) {
+            jlo = min(jlo, __shfl_xor(jlo, off)); jhi = max(jhi, __shfl_xor(jhi, off));
+            ilo = min(ilo, __shfl_xor(ilo, off)); ihi = max(ihi, __shfl_xor(ihi, off));
+        }
+        if ((threadIdx.x & 63) == 0 && jhi >= 0) {
+            atomicMin(&s_box[0], jlo); atomicMax(&s_box[1], jhi); atomicMin(&s_box[2], ilo); atomicMax(&s_box[3], ihi);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int R0 = 0, C0 = 0, PR = 3, PC = 3;
+        if (s_box[1] >= 0 && ra.patch_cells > 0) {
+            const int nr = s_box[1] - s_box[0] + 1 + 3, nc = s_box[3] - s_box[2] + 1 + 3;
+            int m = -1;
+            for (int t = 0; t <= ra.patch_margin; t++)
+                if ((int64_t)(nr + 2 * t) * (nc + 2 * t) <= ra.patch_cells) m = t;
+            if (m >= 0) {
+                R0 = max(0, s_box[0] - 2 - m); C0 = max(0, s_box[2] - 2 - m);
+                PR = min(a.Nj, s_box[1] + 2 + m) - R0; PC = min(a.Ni, s_box[3] + 2 + m) - C0;
+            }
+        }
+        s_box[4] = R0; s_box[5] = C0; s_box[6] = PR; s_box[7] = PC;
+    }
+    __syncthreads();
+    Patch pa;
+    pa.R0 = s_box[4]; pa.C0 = s_box[5]; pa.PR = s_box[6]; pa.PC = s_box[7];
+    char *s_geo = smem + kRunLdsFixed;
+    if (threadIdx.x < 28) {
+        const int e = threadIdx.x / 7, q = threadIdx.x % 7;
+        s_tabL[16 * e + q] = (ra.dji[e][q][0] * pa.PC + ra.dji[e][q][1]) * (int)sizeof(pt) + (q < 4 ? kLdsBias : 0);
+    }
+    const char *__restrict__ gb = (const char *)a.geo;
+    if (pa.PR > 3) {
+        const int ncell = pa.PR * pa.PC;
+        for (int t = threadIdx.x; t < ncell; t += kRunBlock) {
+            const int r = t / pa.PC, cc = t - r * pa.PC;
+            *(v2d *)(s_geo + (size_t)t * sizeof(pt)) = *(const v2d *)(ra.geoF + ((size_t)(pa.R0 + r) * a.Ni + pa.C0 + cc));
+        }
+    }
+    __syncthreads();                                     // last barrier: from here on lanes may leave
+    if (!live) return;
+    int first = 0, last = 0x7fffffff;
+    if (WINDOW) { const int2 w = a.win[p]; first = w.x; last = w.y; }
+    pt P = nt ? load_pt_nt(&a.pos[p]) : a.pos[p];
+    bool moved = false, recelled = false;
+    CellCtx x;
+    const int porg = (pa.R0 << 16) | pa.C0;
+    int crel = c - porg;
+    const unsigned geo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)s_geo - (unsigned)kLdsBias;
+    unsigned lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+    bool inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+    {
+        const unsigned kcell = (unsigned)(cell_j(c) * a.Ni + cell_i(c));
+        if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell, lo, x);
+        else load_ctx<sizeof(FT)>(a, gb, kcell, x);
+    }
+    const char *ub_next = (const char *)ra.u[0], *vb_next = (const char *)ra.v[0], *kb_next = (const char *)ra.kill9[0];
+    double k1000 = 1000.;
+    asm volatile("" : "+s"(k1000));
+    bool killed = false;
+#pragma unroll 1
+    for (int r = 0; r < ra.nrec; r++) {
+        const int jrec = a.jrec + r;
+        const char *ub = ub_next, *vb = vb_next, *kb = kb_next;
+        const int rn = (r + 1 < ra.nrec) ? r + 1 : r;
+        ub_next = (const char *)ra.u[rn]; vb_next = (const char *)ra.v[rn]; kb_next = (const char *)ra.kill9[rn];
+        if (WINDOW) {
+            if (jrec < first) continue;
+            if (jrec > last) break;
+        }
+        // the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] and the neighbours' Survive byte of the host
+        // cell for this record; reloaded below after every crossing
+        __builtin_amdgcn_s_setprio(kPrioLoads);
+        FT fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)), fu1 = *(const FT *)(ub + x.o1);
+        FT fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))), fv1 = *(const FT *)(vb + x.o1);
+        unsigned k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+        __builtin_amdgcn_s_setprio(kPrioBase);
+#pragma unroll 1
+        for (int s = 0; s < nsub; s++) {
+            double zU, zV;
+            FT su = 0, sv = 0;
+            if (UVS == 0) {                              // :423-425
+                zU = 0.5 * ((double)fu1 + (double)fu0);
+                zV = 0.5 * ((double)fv1 + (double)fv0);
+            } else if (UVS == 2) {                       // extra: linear interpolation (not in the reference)
+                zU = lerp_on_segment(P, x.U10, x.U11, (double)fu0, (double)fu1);
+                zV = lerp_on_segment(P, x.V01, x.V11, (double)fv0, (double)fv1);
+            } else {                                     // :427-441, at the sub-step's position
+                const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
+                const bool llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
+                const bool llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
+                pin_load(fu0); pin_load(fv0);
+                su = llum1 ? fu0 : fu1;
+                sv = llvm1 ? fv0 : fv1;
+                zU = (double)su;
+                zV = (double)sv;
+            }
+            const double dx = zU * a.rdt;                // :452-458 with dt_sub
+            const double dy = zV * a.rdt;
+            pt Pn;
+            if (UVS == 1 && sizeof(FT) == 4) {
+                Pn.x = P.x + div1000_of_f32(dx, (float)su, ra.f32_class, k1000);
+                Pn.y = P.y + div1000_of_f32(dy, (float)sv, ra.f32_class, k1000);
+            } else {
+                Pn.x = P.x + div1000(dx, k1000);
+                Pn.y = P.y + div1000(dy, k1000);
+            }
+            moved = true;
+            const bool still_in = inside_quad_hot(Pn.y, Pn.x, x.F00, x.F01, x.F11, x.F10, a.eps_mg);
+            if (!still_in) {      // :466-484
+                __builtin_amdgcn_s_setprio(kPrioCross);
+                const unsigned kcell = x.o1 / (unsigned)sizeof(FT);
+                int dcell, dk, dlo = 0;
+                pin_load(k9);
+                if (inl) {
+                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, s_tab, s_tabL, dcell, dk, dlo, killed);
+                } else {
+                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, s_tab, dcell, dk, killed);
+                }
+                c += dcell;
+                recelled = true;
+                const int crel = c - porg;
+                if (inl) {
+                    lo += (unsigned)dlo;
+                } else {
+                    lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+                }
+                inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+                if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell + (unsigned)dk, lo, x);
+                else load_ctx<sizeof(FT)>(a, gb, kcell + (unsigned)dk, x);
+                if (!killed && s + 1 < nsub) {           // the new cell's candidates and Survive byte, same record
+                    fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)); fu1 = *(const FT *)(ub + x.o1);
+                    fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); fv1 = *(const FT *)(vb + x.o1);
+                    k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+                }
+                __builtin_amdgcn_s_setprio(kPrioBase);
+            }
+            P = Pn;
+            if (killed) break;
+        }
+        if (killed) {
+            c |= SITRK_DEAD_BIT;
+            unsigned tk = threadIdx.x;
+            asm volatile("" : "+v"(tk));
+            a.kill_rec[(int64_t)blk * kRunBlock + tk] = jrec;
+            break;                                       // dead buoys never step again
+        }
+    }
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int64_t pe = (int64_t)blk * kRunBlock + tid;
+    if (moved) {
+        if (nt) store_pt_nt(&a.pos[pe], P);
+        else a.pos[pe] = P;
+    }
+    if (recelled) a.cell[pe] = c;
+}
+
+// ---------------------------------------------------------------------------
+// Predicate probes:the device functions of the hot path evaluated on plain arrays, so that the parity
 // tests can hold them against the reference's golden vectors one predicate at a time (sitrk_eval_*).
 // ---------------------------------------------------------------------------
 __global__ void eval_inside_kernel(int64_t n, const pt *__restrict__ pts, const pt *__restrict__ quads, int8_t *__restrict__ out)

@@ -5,7 +5,8 @@ Same flags and defaults (reference si3_part_tracker.py:42-73), same module const
 `./seed/Initialized_buoys_<SeedName>_<CONF>.npz` cache keys (:205-255), same per-buoy record windows in
 2-D-time mode (:264-318), same NetCDF outputs (:515-571) -- the per-buoy loop (:378-490) and the
 per-record inverse projection (:493) run on the GPU.  Differences, all opt-in or forced:
-extra flags `--device`, `--uv-strategy`; under `torchrun` (WORLD_SIZE > 1) the buoys are range-partitioned over the
+extra flags `--device`, `--uv-strategy`, `--rdt` (model output period: the reference's constant 3600, or `auto` = the spacing
+of the model file's time axis) and `--nsub` (Euler sub-steps per record, default 1); under `torchrun` (WORLD_SIZE > 1) the buoys are range-partitioned over the
 ranks by latitude band and every rank reads only the rows of each record its own buoys can touch (row-band ingest, no
 collective; `--full-records`: rank 0 reads, RCCL broadcast), rank 0 writes the files; errors raise instead of
 `print; exit(0)`; maps need the
@@ -25,7 +26,7 @@ from . import _lib, ncio
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit
 
-rdt = 3600.          # time step [s] = model output period (reference :31)
+rdt = 3600.          # time step [s] = model output period (reference :31); the default of --rdt
 FILL = ncio.FillValue
 
 
@@ -71,7 +72,64 @@ def parse_args(argv=None):
     ap.add_argument('--full-records', action='store_true',
                     help='read and upload whole records (under torchrun: rank 0 reads, RCCL broadcast) instead of only the rows '
                          'each rank\'s buoys can touch (extra; same results)')
+    ap.add_argument('--rdt', type=_rdt_arg, default=rdt,
+                    help='period of the model output [s], SECONDS or `auto` = the spacing of the model file\'s time_counter (extra; '
+                         'default 3600, the reference\'s constant): each record advances the buoys by that much time')
+    ap.add_argument('--nsub', type=_nsub_arg, default=1,
+                    help='advance every record in NSUB Euler sub-steps of rdt/NSUB, each the reference\'s full step logic (extra; '
+                         'default 1 = one step per record like the reference; 1..1024): keeps a buoy within one cell per '
+                         'sub-step on 6-hourly or daily output')
     return ap.parse_args(argv)
+
+
+def _rdt_arg(text):
+    if text == 'auto':
+        return 'auto'
+    try:
+        val = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--rdt: expected seconds or 'auto', got %r" % text)
+    if not (np.isfinite(val) and val > 0):
+        raise argparse.ArgumentTypeError("--rdt: must be > 0 seconds, got %r" % text)
+    return val
+
+
+def _nsub_arg(text):
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--nsub: expected an integer, got %r" % text)
+    if not 1 <= n <= 1024:
+        raise argparse.ArgumentTypeError("--nsub: must be in 1..1024, got %d" % n)
+    return n
+
+
+def axis_spacing(ztime_model):
+    """The spacing [s] of a uniform model time axis (what `--rdt auto` takes); ValueError for an axis of fewer than two
+    records or with unequal spacings."""
+    tm = np.asarray(ztime_model, dtype=np.float64).reshape(-1)
+    if tm.size < 2:
+        raise ValueError('--rdt auto: the model time axis has %d record(s); its spacing needs at least 2' % tm.size)
+    d = np.diff(tm)
+    if not (d[0] > 0 and np.all(d == d[0])):
+        raise ValueError('--rdt auto: the model time axis is not uniform (spacings %s .. %s s); give --rdt SECONDS'
+                         % (d.min(), d.max()))
+    return float(d[0])
+
+
+def run_rdt(arg, ztime_model, say=print):
+    """The period a run uses: `auto` -> axis_spacing(); an explicit value is kept, with one warning line when the axis is
+    uniform with another spacing."""
+    if arg == 'auto':
+        return axis_spacing(ztime_model)
+    val = float(arg)
+    try:
+        sp = axis_spacing(ztime_model)
+    except ValueError:
+        return val
+    if sp != val:
+        say(' *** WARNING: rdt = %g s but the model time axis is uniform with a spacing of %g s (--rdt auto would take it)' % (val, sp))
+    return val
 
 
 _IDEALISED_KINDS = ('nemoTsi3', 'nemoTmm', 'sidfex')
@@ -158,13 +216,13 @@ def _savez_deflate(fname, **arrays):
         f.write(struct.pack('<IHHHHIIH', 0x06054b50, 0, 0, 0xffff, 0xffff, 0xffffffff, 0xffffffff, 0))
 
 
-def record_windows(zTpos, ztime_model, kstrt, kstop, iTmA, iTmB, nP):
+def record_windows(zTpos, ztime_model, kstrt, kstop, iTmA, iTmB, nP, rdt=3600.):
     """Per-buoy first / last model record in 2-D-time mode (reference :264-312).
 
     The reference loops over the late starters / early stoppers with one `np.where` over the model time axis each
     (`idx[-1]+1`, `idx[0]-1`).  On an increasing time axis those are counts, i.e. two `searchsorted` for all buoys at
     once (10^7 buoys: 5 s -> 0.1 s); any other axis takes the reference's loop.  Same IndexError when the search
-    comes back empty."""
+    comes back empty.  `rdt` = the model output period (reference :31, the default)."""
     z1st = np.zeros(nP, dtype=int) + kstrt
     zLst = np.zeros(nP, dtype=int) + kstop
     half = int(rdt / 2)
@@ -243,6 +301,10 @@ def main(argv=None):
     cdtbin, csfkm = seed_name_tokens(path.basename(fNCseed))
     idateSeedA, idateSeedB, SeedName, SeedBatch, zTpos = ncio.SeedFileTimeInfo(fNCseed, ltime2d=lUse2DTime)
     Nt0, ztime_model, idateModA, idateModB, ModConf, ModExp = ncio.ModelFileTimeInfo(cf_uv)
+    rdt = run_rdt(a.rdt, ztime_model, say)              # the module constant's value unless --rdt says otherwise
+    nsub = a.nsub
+    if rdt != 3600. or nsub != 1:
+        say(' *** rdt = %g s per model record, %d Euler sub-step(s) of %g s each' % (rdt, nsub, rdt / nsub))
 
     date_stop = None
     if cdate_stop:
@@ -310,7 +372,7 @@ def main(argv=None):
             zTpos = zTpos[:, idxK]
         if zTpos.shape != (2, nP):
             raise ValueError('wrong shape for the 2D time array `zTpos`: %s vs nP=%d' % (zTpos.shape, nP))
-        z1stModelRec, zLstModelRec = record_windows(zTpos, ztime_model, kstrt, kstop, iTmA, iTmB, nP)
+        z1stModelRec, zLstModelRec = record_windows(zTpos, ztime_model, kstrt, kstop, iTmA, iTmB, nP, rdt=rdt)
     k0 = z1stModelRec - kstrt
 
     # ---- device state.  Under torchrun every rank owns a contiguous range of the buoys ordered by host row, i.e. a
@@ -330,7 +392,8 @@ def main(argv=None):
     (u0,) = records.fields(kstrt, ('u_ice',))
     fdt = np.float64 if np.asarray(u0).dtype == np.float64 else np.float32
     K = int(max(2, min(a.slots, 64)))
-    trk = IceTracker(xYf, xXf, xYu, xXu, xYv, xXv, imaskt, rdt=rdt, iUVstrategy=iUVstrategy, nslots=K, field_dtype=fdt, ctx=ctx)
+    trk = IceTracker(xYf, xXf, xYu, xXu, xYv, xXv, imaskt, rdt=rdt, iUVstrategy=iUVstrategy, nslots=K, field_dtype=fdt, ctx=ctx,
+                     nsub=nsub)
     trk.set_buoys(xPosC0[mine], vJIt[mine], z1stModelRec[mine] if lUse2DTime else None, zLstModelRec[mine] if lUse2DTime else None)
 
     # ---- outputs (rank 0).  The reference allocates the whole series -- xPosC, xPosG (Nt+1,nP,2) f8, xmask -- and writes it at the

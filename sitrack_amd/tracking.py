@@ -149,10 +149,12 @@ class IceTracker:
     """
 
     def __init__(self, xYf, xXf, xYu, xXu, xYv, xXv, imaskt, rdt=3600., iUVstrategy=1, rmin=rmin_conc,
-                 nslots=1, field_dtype=np.float32, device=0, ctx=None):
+                 nslots=1, field_dtype=np.float32, device=0, ctx=None, nsub=1):
+        """`nsub` (extra): every record is advanced in nsub Euler sub-steps of rdt/nsub (sitrk_set_substeps)."""
         self.ctx = ctx or _lib.Context(device)
         self.ctx.set_grid(xYf, xXf, xYu, xXu, xYv, xXv, imaskt)
         self.ctx.set_params(rdt, iUVstrategy, rmin)
+        self.ctx.set_substeps(nsub)
         self.ctx.alloc_records(nslots, field_dtype)
 
     def set_buoys(self, xPosC0, vJIt, z1stModelRec=None, zLstModelRec=None, sort=True):
