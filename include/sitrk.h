@@ -120,7 +120,16 @@ int sitrk_set_substeps(sitrk_t *h, int nsub);
  * fused kernel share an XCD (its L2); "step_block" (256/512/1024): workgroup size of the one-record kernel; "fuse" (1..32):
  * consecutive resident records advanced per launch by sitrk_run (loop interchange: the buoys are independent, each lane keeps
  * its buoy in registers across the records); "subsample_block" (256..4096, powers of two, default 1024): points per workgroup of
- * sitrk_subsample_cloud's resolve kernel. */
+ * sitrk_subsample_cloud's resolve kernel;
+ * "lanes" (1/2, default 2) / "lane_min_wg" (>= 1, default 7168): with lanes = 2, sitrk_run splits the cell-sorted buoys into two
+ * contiguous lanes (cut at a multiple of 256 * 8 * xcd_group buoys) and queues each lane's fused launches on a stream of its own
+ * -- lane 0 on the compute stream, lane 1 on the ingest stream, its first launch half as long, so that the lanes' launch
+ * boundaries alternate and the chip does not drain at them -- wherever the records up to the next re-sort or the end of the call
+ * hold two full launches per lane behind that short one (2.5 * fuse records), the shorter lane keeps lane_min_wg workgroups of 256
+ * buoys, and the ingest stream has no Survive derivation queued.  Everywhere else, and always with lanes = 1, the launch
+ * sequence is the one-lane one.  The lanes fork from and join the compute stream by events inside sitrk_run (no host wait):
+ * outside it all buoy state is ordered on the compute stream as before.  sitrk_launch_stats counts record batches, whatever the
+ * number of lanes; sitrk_lane_stats counts the lanes' own launches. */
 int sitrk_set_tuning(sitrk_t *h, const char *knob, int value);
 
 /* ---- model records (u_ice, v_ice, siconc) -------------------------------
@@ -245,6 +254,9 @@ int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps);
  * nsub > 1, of advect_substep_kernel), the records they advanced in total (a launch is cut short at a re-sort and at the end of a run), and one-record launches of
  * advect_step_kernel.  Any pointer may be NULL.  bench.py prices its roofline per launch from these. */
 int sitrk_launch_stats(sitrk_t *h, int reset, int64_t *fused_launches, int64_t *fused_records, int64_t *step_launches);
+/* ... and, of those, what went on two lanes (knob "lanes"): segments (runs of records between two joins) and the kernel
+ * launches the two lanes queued for them.  Both stay 0 with lanes = 1.  Any pointer may be NULL. */
+int sitrk_lane_stats(sitrk_t *h, int reset, int64_t *lane_segments, int64_t *lane_launches);
 
 /* Current state in the caller's buoy order (any pointer may be NULL):
  * yx (nP,2) current position; jiT (nP,2) = vJIt; alive (nP) = iAlive;

@@ -42,6 +42,7 @@ _SIGNATURES = {
     "sitrk_stage_submit": (_int, [_vp, _int, _int, _int]),
     "sitrk_stage_release": (_int, [_vp]),
     "sitrk_launch_stats": (_int, [_vp, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_lane_stats": (_int, [_vp, _int, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_buoy_rows": (_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sitrk_push_record_rows": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp]),
     "sitrk_commit_record_rows": (_int, [_vp, _int, _int, _int]),
@@ -305,6 +306,12 @@ class Context:
         a, b, c = _i64(0), _i64(0), _i64(0)
         self._chk(self._L.sitrk_launch_stats(self._h, int(bool(reset)), C.byref(a), C.byref(b), C.byref(c)))
         return {"fused_launches": a.value, "fused_records": b.value, "step_launches": c.value}
+
+    def lane_stats(self, reset=False):
+        """what of launch_stats() went on two lanes (knob "lanes"): segments between two joins, kernel launches of the lanes"""
+        a, b = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_lane_stats(self._h, int(bool(reset)), C.byref(a), C.byref(b)))
+        return {"lane_segments": a.value, "lane_launches": b.value}
 
     def buoy_rows(self):
         """(jmin, jmax) of the host rows of the buoys still alive; jmin > jmax when there is none."""

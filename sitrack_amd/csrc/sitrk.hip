@@ -115,6 +115,8 @@ SITRK_API int sitrk_create(sitrk_t **out, int device)
     for (int b = 0; b < sitrk_ctx::kStage && e == hipSuccess; b++) e = hipEventCreateWithFlags(&c->stage_done[b], hipEventDisableTiming);
     for (int k = 0; k < sitrk_ctx::kLaunchRing && e == hipSuccess; k++) e = hipEventCreateWithFlags(&c->launch_ev[k], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->box_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->lane_join, hipEventDisableTiming);
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->box_host, 4 * sizeof(int), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&c->counter, 4 * sizeof(unsigned long long));     // reductions: 2 x 4 ints / one 64-bit count
     if (e != hipSuccess) {
@@ -138,6 +140,8 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
+    if (h->lane_fork) (void)hipEventDestroy(h->lane_fork);
+    if (h->lane_join) (void)hipEventDestroy(h->lane_join);
     if (h->box_host) (void)hipHostFree(h->box_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -264,6 +268,16 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
     else if (!strcmp(knob, "patch_kb")) {            // LDS bytes (KiB) per workgroup for the fused kernel's geometry patch
         if (value < 0 || value > 63) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: patch_kb must be 0..63");
         h->patch_kb = value;
+        return SITRK_OK;
+    }
+    else if (!strcmp(knob, "lanes")) {               // sitrk_run: buoy lanes whose fused launches overlap (1 = one stream, one launch at a time)
+        if (value < 1 || value > 2) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: lanes must be 1 or 2");
+        h->lanes = value;
+        return SITRK_OK;
+    }
+    else if (!strcmp(knob, "lane_min_wg")) {         // ... only where each lane keeps at least that many workgroups
+        if (value < 1) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: lane_min_wg must be >= 1");
+        h->lane_min_wg = value;
         return SITRK_OK;
     }
     else if (!strcmp(knob, "xcd_group")) {
@@ -1063,7 +1077,7 @@ static inline bool fused_ok(const sitrk_ctx *h)
     return !h->rim_buoys && (uint64_t)h->Nj * h->Ni * sizeof(CellGeo) < ((uint64_t)1 << 32);
 }
 
-static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m);
+static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m, int64_t off = 0, int64_t cnt = -1, hipStream_t lane = nullptr);
 
 SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
 {
@@ -1121,53 +1135,59 @@ static int f32_class_for(double rdt)
 }
 
 template <typename FT>
-static void launch_run(sitrk_ctx *h, const RunArgs &ra)
+static void launch_run(sitrk_ctx *h, const RunArgs &ra, hipStream_t stream)
 {
     dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
     // dynamic LDS: tables + the patch's F-points
     const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
     const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
     if (h->uv_strategy == 1) {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 1, true>), grid, block, lds, h->stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 1, false>), grid, block, lds, h->stream, ra);
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 1, true>), grid, block, lds, stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 1, false>), grid, block, lds, stream, ra);
     } else if (h->uv_strategy == 2) {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 2, true>), grid, block, lds, h->stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 2, false>), grid, block, lds, h->stream, ra);
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 2, true>), grid, block, lds, stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 2, false>), grid, block, lds, stream, ra);
     } else {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 0, true>), grid, block, lds, h->stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 0, false>), grid, block, lds, h->stream, ra);
+        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 0, true>), grid, block, lds, stream, ra);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, 0, false>), grid, block, lds, stream, ra);
     }
 }
 
 template <typename FT>
-static void launch_substep(sitrk_ctx *h, const RunArgs &ra, int nsub)
+static void launch_substep(sitrk_ctx *h, const RunArgs &ra, int nsub, hipStream_t stream)
 {
     dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
     const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
     const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
     if (h->uv_strategy == 1) {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 1, true>), grid, block, lds, h->stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 1, false>), grid, block, lds, h->stream, ra, nsub);
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 1, true>), grid, block, lds, stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 1, false>), grid, block, lds, stream, ra, nsub);
     } else if (h->uv_strategy == 2) {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 2, true>), grid, block, lds, h->stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 2, false>), grid, block, lds, h->stream, ra, nsub);
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 2, true>), grid, block, lds, stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 2, false>), grid, block, lds, stream, ra, nsub);
     } else {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 0, true>), grid, block, lds, h->stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 0, false>), grid, block, lds, h->stream, ra, nsub);
+        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 0, true>), grid, block, lds, stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_substep_kernel<FT, 0, false>), grid, block, lds, stream, ra, nsub);
     }
 }
 
 // records jrec0 .. jrec0+m-1 from slots (slot_first + r) % nslots in ONE launch: advect_run_kernel (nsub == 1) or
 // advect_substep_kernel (nsub > 1, also for m == 1: sitrk_step).  Both are counted as fused launches.
-static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m)
+// The launch covers the buoys [off, off + cnt) of the sorted order (cnt < 0: all of them): the kernels index from the pointers
+// they are given.  lane == nullptr: the whole of a record batch on the compute stream -- its slots are made ready there, the
+// launch is marked and counted.  lane != nullptr: one lane's share of a batch on that stream (run_lanes), which has made the
+// slots ready before its fork and marks and counts behind its join.
+static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m, int64_t off, int64_t cnt, hipStream_t lane)
 {
     BuoyState &s = h->st[h->cur];
+    const hipStream_t stream = lane ? lane : h->stream;
+    if (cnt < 0) cnt = h->nP - off;
     const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
     const double dt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;        // dt_sub: one rounded division
     RunArgs ra;
-    ra.s.nP = h->nP; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0;
+    ra.s.nP = cnt; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0;
     ra.s.rdt = dt; ra.s.rmin_conc = h->rmin_conc; ra.s.eps_mg = h->eps_mg; ra.s.geo = h->geo; ra.s.orient = h->orient; ra.s.kill = nullptr; ra.s.u = ra.s.v = nullptr;
-    ra.s.pos = s.pos; ra.s.cell = s.cell; ra.s.kill_rec = s.kill_rec; ra.s.win = s.win;
+    ra.s.pos = s.pos + off; ra.s.cell = s.cell + off; ra.s.kill_rec = s.kill_rec + off; ra.s.win = s.win ? s.win + off : nullptr;
     ra.nrec = m;
     make_cross_tab(h->Ni, ra.tab, ra.dji);
     ra.geoF = h->geoF;
@@ -1179,27 +1199,30 @@ static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m)
     for (int r = 0; r < m; r++) {
         const int slot = (slot_first + r) % h->nslots;
         used[r] = slot;
-        int rc = check_band(h, slot, r);
-        if (rc) return rc;
-        if (h->slot_dirty[slot]) {
-            rc = derive_mask(h, slot);
+        if (!lane) {
+            int rc = check_band(h, slot, r);
+            if (rc) return rc;
+            if (h->slot_dirty[slot]) {
+                rc = derive_mask(h, slot);
+                if (rc) return rc;
+            }
+            rc = slot_wait_upload(h, slot);
+            if (rc) return rc;
+            rc = slot_wait_sv(h, slot);
             if (rc) return rc;
         }
-        rc = slot_wait_upload(h, slot);
-        if (rc) return rc;
-        rc = slot_wait_sv(h, slot);
-        if (rc) return rc;
         const char *slab = slab_of(h, slot);
         ra.u[r] = slab; ra.v[r] = slab + n * es; ra.kill9[r] = h->kill9 + (size_t)slot * n;
     }
     if (h->nsub > 1) {
-        if (h->dtype == SITRK_F64) launch_substep<double>(h, ra, h->nsub);
-        else launch_substep<float>(h, ra, h->nsub);
+        if (h->dtype == SITRK_F64) launch_substep<double>(h, ra, h->nsub, stream);
+        else launch_substep<float>(h, ra, h->nsub, stream);
     } else {
-        if (h->dtype == SITRK_F64) launch_run<double>(h, ra);
-        else launch_run<float>(h, ra);
+        if (h->dtype == SITRK_F64) launch_run<double>(h, ra, stream);
+        else launch_run<float>(h, ra, stream);
     }
     HIPCHK(hipGetLastError());
+    if (lane) return SITRK_OK;
     int rc = launch_mark(h, used, m);
     if (rc) return rc;
     h->steps_since_sort += m;
@@ -1207,6 +1230,92 @@ static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m)
     h->n_fused_records += m;
     if (h->band_age >= 0) h->band_age += m;
     if (h->box_pending) h->box_pending_age += m;
+    return SITRK_OK;
+}
+
+// --------------------------------------------------------------------------- lanes
+// Buoys never interact: workgroup b of a launch depends on workgroup b of the launch before it and on nothing else.  On one
+// stream a launch still starts only when the last wave of the one before has left, so at every launch boundary the chip drains,
+// idles for the dispatch gap and ramps up through the prologue.  sitrk_run therefore may split the
+// cell-sorted buoys into two contiguous LANES, each with its own chain of launches on its own stream, and staggers lane 1 by
+// half a launch so that one lane's boundary falls in the middle of the other's launch.
+
+// first buoy of lane 1, or 0 where one lane is used: whole spans of xcd_group(), and lane_min_wg workgroups in the shorter lane
+static int64_t lane_cut(const sitrk_ctx *h)
+{
+    if (h->lanes < 2) return 0;
+    const int64_t unit = (int64_t)kRunBlock * 8 * std::max(1, h->xcd_group);
+    const int64_t cut = ((h->nP + unit - 1) / unit + 1) / 2 * unit;
+    if (cut >= h->nP) return 0;
+    return (h->nP - cut + kRunBlock - 1) / kRunBlock >= h->lane_min_wg ? cut : 0;
+}
+
+// What launch_records does per slot before a launch, for all `seg` records from slot_first at once and BEFORE the fork, so that
+// lane 1 is ordered behind it too (nothing can make a slot pending again while sitrk_run is running).  *ok = false: this
+// segment goes the one-lane way -- a slot's box does not hold the buoys (that path then reports it at the record where it
+// happens), or the ingest stream, which carries lane 1, still has Survive work of other slots queued.
+static int lanes_prepare(sitrk_ctx *h, int slot_first, int seg, bool *ok)
+{
+    *ok = false;
+    for (int q = 0; q < seg; q++)
+        if (check_band(h, (slot_first + q) % h->nslots, q)) return SITRK_OK;
+    for (int q = 0; q < std::min(seg, h->nslots); q++) {
+        const int slot = (slot_first + q) % h->nslots;
+        int rc = SITRK_OK;
+        if (h->slot_dirty[slot]) rc = derive_mask(h, slot);
+        if (!rc) rc = slot_wait_upload(h, slot);
+        if (!rc) rc = slot_wait_sv(h, slot);
+        if (rc) return rc;
+    }
+    for (int k = 0; k < h->nslots; k++)
+        if (h->slot_sv_pending[k]) return SITRK_OK;
+    *ok = true;
+    return SITRK_OK;
+}
+
+// `seg` records (no re-sort inside) from slot_first / jrec0 on two lanes: lane 0 = buoys [0, cut) on the compute stream with
+// the launch sequence of the one-lane path, lane 1 = buoys [cut, nP) on the ingest stream (idle here: lanes_prepare) with a
+// first launch of fuse/2 records.  Fork and join are events; the host waits for nothing.
+static int run_lanes(sitrk_ctx *h, int slot_first, int jrec0, int seg, int fuse, int64_t cut)
+{
+    const hipStream_t l1 = h->sv_stream;
+    HIPCHK(hipEventRecord(h->lane_fork, h->stream));
+    HIPCHK(hipStreamWaitEvent(l1, h->lane_fork, 0));
+    int rc = SITRK_OK;
+    int a = 0, b = 0;                   // records queued on lane 0 / lane 1; the lane that is behind goes next
+    while (rc == SITRK_OK && (a < seg || b < seg)) {
+        if (a < seg && (a <= b || b >= seg)) {
+            const int m = std::min(fuse, seg - a);
+            rc = launch_records(h, (slot_first + a) % h->nslots, jrec0 + a, m, 0, cut, h->stream);
+            a += m;
+            h->n_lane_launches++;
+        } else {
+            const int m = std::min(b == 0 ? fuse / 2 : fuse, seg - b);
+            rc = launch_records(h, (slot_first + b) % h->nslots, jrec0 + b, m, cut, h->nP - cut, l1);
+            b += m;
+            h->n_lane_launches++;
+        }
+    }
+    // the join, whatever was queued: outside sitrk_run all buoy state is ordered on the compute stream
+    hipError_t e = hipEventRecord(h->lane_join, l1);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->lane_join, 0);
+    if (rc) return rc;
+    HIPCHK(e);
+    // one mark behind the join covers both lanes' use of every slot of the segment
+    const long long seq = ++h->launch_seq;
+    HIPCHK(hipEventRecord(h->launch_ev[seq % sitrk_ctx::kLaunchRing], h->stream));
+    for (int q = 0; q < std::min(seg, h->nslots); q++) h->slot_used_seq[(slot_first + q) % h->nslots] = seq;
+    // the counters stay logical: the record batches of the one-lane path, one fused launch each
+    for (int q = 0; q < seg;) {
+        const int m = std::min(fuse, seg - q);
+        if (m <= 1 && h->nsub == 1) h->n_step_launches++;             // (there a lone record takes sitrk_step's kernel)
+        else { h->n_fused_launches++; h->n_fused_records += m; }
+        q += m;
+    }
+    h->n_lane_segments++;
+    h->steps_since_sort += seg;
+    if (h->band_age >= 0) h->band_age += seg;
+    if (h->box_pending) h->box_pending_age += seg;
     return SITRK_OK;
 }
 
@@ -1220,11 +1329,29 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
     if (h->nP == 0) return SITRK_OK;
     int fuse = std::max(1, std::min(std::min(h->fuse, kMaxFuse), h->nslots));    // a launch never wraps the slot ring
     if (!fused_ok(h)) fuse = 1;
+    const int64_t cut = fuse >= 2 ? lane_cut(h) : 0;
     int k = 0;
     while (k < nsteps) {
         if (h->resort_every > 0 && h->steps_since_sort >= h->resort_every) {
             int rc = sitrk_sort_buoys(h);
             if (rc) return rc;
+        }
+        if (cut > 0) {
+            // a segment = the records up to the next join (re-sort or return).  Lanes where it holds two full launches per lane
+            // behind lane 1's short first one; anything shorter is stepped exactly as with one lane.
+            int seg = nsteps - k;
+            if (h->resort_every > 0) seg = std::min(seg, h->resort_every - h->steps_since_sort);
+            bool ok = false;
+            if (seg >= 2 * fuse + fuse / 2) {
+                int rc = lanes_prepare(h, (slot0 + k) % h->nslots, seg, &ok);
+                if (rc) return rc;
+            }
+            if (ok) {
+                int rc = run_lanes(h, (slot0 + k) % h->nslots, jrec0 + k, seg, fuse, cut);
+                if (rc) return rc;
+                k += seg;
+                continue;
+            }
         }
         int m = std::min(fuse, nsteps - k);
         if (h->resort_every > 0) m = std::min(m, h->resort_every - h->steps_since_sort);
@@ -1249,6 +1376,15 @@ SITRK_API int sitrk_launch_stats(sitrk_t *h, int reset, int64_t *fused_launches,
     if (fused_records) *fused_records = h->n_fused_records;
     if (step_launches) *step_launches = h->n_step_launches;
     if (reset) h->n_fused_launches = h->n_fused_records = h->n_step_launches = 0;
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_lane_stats(sitrk_t *h, int reset, int64_t *lane_segments, int64_t *lane_launches)
+{
+    NEED(h, "null handle");
+    if (lane_segments) *lane_segments = h->n_lane_segments;
+    if (lane_launches) *lane_launches = h->n_lane_launches;
+    if (reset) h->n_lane_segments = h->n_lane_launches = 0;
     return SITRK_OK;
 }
 

@@ -116,6 +116,10 @@ struct sitrk_ctx {
     int patch_kb = 16;                  // fused kernel: LDS bytes per workgroup for its geometry patch (0 = none, all reads global)
     int xcd_group = 16;                 // fused kernel: runs of that many consecutive workgroups on one XCD (0/1 = hardware order)
     int patch_margin = 8;               // ... and the widest margin of cells around the buoys' bounding box it may take
+    int lanes = 2;                      // sitrk_run: 2 = the sorted buoys split into two lanes whose fused launches overlap, lane 1 on
+                                        // sv_stream and half a launch behind lane 0 (1 = one stream, one launch at a time)
+    int lane_min_wg = 7168;             // ... where the shorter lane keeps that many workgroups (4 rounds of 256 CUs x 7 workgroups)
+    hipEvent_t lane_fork = nullptr, lane_join = nullptr;
     int subsample_block = 1024;         // sitrk_subsample_cloud: points per workgroup of its resolve kernel (never changes results)
     int fill_threads = 8;               // host threads copying a pushed record (>= 8 MB) into the pinned staging (2 / 4 / 8: 26 / 36 / 47 GB/s on the box rows of C3)
 
@@ -158,6 +162,7 @@ struct sitrk_ctx {
     int box_pending_age = 0;
     // launch accounting (sitrk_launch_stats)
     long long n_fused_launches = 0, n_fused_records = 0, n_step_launches = 0;
+    long long n_lane_segments = 0, n_lane_launches = 0;     // (sitrk_lane_stats)
 
     // buoys
     int64_t nP = 0;
