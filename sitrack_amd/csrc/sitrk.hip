@@ -9,9 +9,9 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
-#include "../../include/sitrk.h"
 #include "sitrk_internal.h"
 #include "sitrk_kernels.h"
 #include "sitrk_locate.h"
@@ -19,11 +19,9 @@
 
 using namespace sitrk;
 
-#define SITRK_API extern "C" __attribute__((visibility("default")))
-
 static thread_local char g_create_err[512] = {0};
 
-static int fail(sitrk_ctx *h, int code, const char *fmt, ...)
+int sitrk::fail(sitrk_ctx *h, int code, const char *fmt, ...)
 {
     char *dst = h ? h->err : g_create_err;
     va_list ap;
@@ -33,19 +31,7 @@ static int fail(sitrk_ctx *h, int code, const char *fmt, ...)
     return code;
 }
 
-#define HIPCHK(call)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) return fail(h, SITRK_EHIP, "%s -> %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-#define NEED(cond, msg)                                \
-    do {                                               \
-        if (!(cond)) return fail(h, SITRK_EINVAL, msg); \
-    } while (0)
-
 static inline unsigned nblocks(int64_t n, int bs = kBlock) { return (unsigned)((n + bs - 1) / bs); }
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <typename T>
 static hipError_t dev_alloc(T **p, size_t count)
@@ -58,7 +44,7 @@ static void dev_free(void *p)
     if (p) (void)hipFree(p);
 }
 
-static int ensure_scratch(sitrk_ctx *h, size_t bytes)
+int sitrk::ensure_scratch(sitrk_ctx *h, size_t bytes)
 {
     if (h->scratch_bytes >= bytes) return SITRK_OK;
     dev_free(h->scratch);
@@ -197,12 +183,11 @@ SITRK_API int sitrk_set_grid(sitrk_t *h, int Nj, int Ni, const double *Yf, const
     HIPCHK(dev_alloc(&h->orient, n));
     HIPCHK(dev_alloc(&h->tmask, n));
     // stage the six arrays in scratch, interleave on the device
-    int rc = ensure_scratch(h, 6 * n * sizeof(double));
-    if (rc) return rc;
-    double *s = (double *)h->scratch;
+    double *s;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(s, 6 * n, 1); }));      // six arrays back to back, no padding
     const double *src[6] = {Yf, Xf, Yu, Xu, Yv, Xv};
-    for (int a = 0; a < 6; a++) HIPCHK(hipMemcpyAsync(s + a * n, src[a], n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->tmask, tmask, n, hipMemcpyHostToDevice, h->stream));
+    for (int a = 0; a < 6; a++) HIPCHK(upload(h, s + a * n, src[a], n));
+    HIPCHK(upload(h, h->tmask, tmask, n));
     hipLaunchKernelGGL(build_geo_kernel, dim3(nblocks((int64_t)n)), dim3(kBlock), 0, h->stream, n, s, s + n, s + 2 * n, s + 3 * n,
                        s + 4 * n, s + 5 * n, h->geo, h->geoF);
     HIPCHK(hipGetLastError());
@@ -450,17 +435,14 @@ static int derive_mask_box_batch(sitrk_ctx *h, const int *slots, int nb, int j0,
     const bool empty = (j0 >= j1 || i0 >= i1);           // (a slot that holds nothing: check_band refuses to step with it)
     if (!on_ingest) {
         for (int k = 0; k < nb; k++) {
-            int rc = slot_wait_upload(h, slots[k]);
-            if (rc) return rc;
-            rc = slot_wait_sv(h, slots[k]);             // an earlier derivation of the same slot writes the same bytes
-            if (rc) return rc;
+            RCCHK(slot_wait_upload(h, slots[k]));
+            RCCHK(slot_wait_sv(h, slots[k]));      // an earlier derivation of the same slot writes the same bytes
         }
         if (!empty) {
-            int rc = launch_survive(h, h->dtype == SITRK_F64, (const char *)h->slabs + 2 * n * es, nullptr, h->kill9, j0, j1, i0, i1,
-                                    slots, nb, (long long)(h->slab_bytes / es), (long long)n);
-            if (rc) return rc;
-            rc = launch_mark(h, slots, nb);             // it reads the slots' siconc and writes their bytes: uploads and ingest-side
-            if (rc) return rc;                          // derivations of these slots stay behind it
+            RCCHK(launch_survive(h, h->dtype == SITRK_F64, (const char *)h->slabs + 2 * n * es, nullptr, h->kill9, j0, j1, i0, i1,
+                                 slots, nb, (long long)(h->slab_bytes / es), (long long)n));
+            RCCHK(launch_mark(h, slots, nb));           // it reads the slots' siconc and writes their bytes: uploads and ingest-side
+                                                        // derivations of these slots stay behind it
         }
     } else if (!empty) {
         for (int k = 0; k < nb; k++) {
@@ -469,9 +451,8 @@ static int derive_mask_box_batch(sitrk_ctx *h, const int *slots, int nb, int j0,
             if (h->slot_used_seq[slot] >= 0)
                 HIPCHK(hipStreamWaitEvent(h->sv_stream, h->launch_ev[h->slot_used_seq[slot] % sitrk_ctx::kLaunchRing], 0));
         }
-        int rc = launch_survive(h, h->dtype == SITRK_F64, (const char *)h->slabs + 2 * n * es, nullptr, h->kill9, j0, j1, i0, i1,
-                                slots, nb, (long long)(h->slab_bytes / es), (long long)n, h->sv_stream);
-        if (rc) return rc;
+        RCCHK(launch_survive(h, h->dtype == SITRK_F64, (const char *)h->slabs + 2 * n * es, nullptr, h->kill9, j0, j1, i0, i1,
+                             slots, nb, (long long)(h->slab_bytes / es), (long long)n, h->sv_stream));
         for (int k = 0; k < nb; k++) {
             const int slot = slots[k];
             if (!h->slot_sv[slot]) HIPCHK(hipEventCreateWithFlags(&h->slot_sv[slot], hipEventDisableTiming));
@@ -494,20 +475,76 @@ static int derive_mask(sitrk_ctx *h, int slot)
     return derive_mask_box(h, slot, h->slot_row_lo[slot], h->slot_row_hi[slot], h->slot_col_lo[slot], h->slot_col_hi[slot]);
 }
 
+// THE way a slot is made ready for the compute stream, which every stepping path takes before the first launch that reads the
+// slot: its Survive bytes re-derived if the slab was rewritten in place, then the compute stream ordered behind an upload and
+// behind a Survive derivation still in flight on the ingest side
+static int slot_make_ready(sitrk_ctx *h, int slot)
+{
+    if (h->slot_dirty[slot]) RCCHK(derive_mask(h, slot));      // slab written through sitrk_record_ptr and not committed yet
+    RCCHK(slot_wait_upload(h, slot));
+    return slot_wait_sv(h, slot);
+}
+
+// ... and the bookkeeping behind every path that stepped `m` records: the re-sort cadence and the age of the buoys' box
+static inline void records_stepped(sitrk_ctx *h, int m)
+{
+    h->steps_since_sort += m;
+    if (h->band_age >= 0) h->band_age += m;
+    if (h->box_pending) h->box_pending_age += m;
+}
+
 static inline void slot_holds(sitrk_ctx *h, int slot, int j0, int j1, int i0, int i1)
 {
     h->slot_row_lo[slot] = j0; h->slot_row_hi[slot] = j1;
     h->slot_col_lo[slot] = i0; h->slot_col_hi[slot] = i1;
 }
 
-SITRK_API int sitrk_commit_record(sitrk_t *h, int slot)
+// What every ingest entry point checks first, reported under the name `fn` of the function the caller called: the handle, the
+// record slabs and the slot (the staging calls name none: slot 0 exists wherever slabs do)
+static int ingest_check(sitrk_ctx *h, const char *fn, int slot = 0, const char *slot_name = "slot")
 {
     NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_commit_record: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_commit_record: slot out of range");
+    if (!h->slabs) return fail(h, SITRK_EINVAL, "%s: call sitrk_alloc_records first", fn);
+    if (slot < 0 || slot >= h->nslots) return fail(h, SITRK_EINVAL, "%s: %s out of range", fn, slot_name);
+    return SITRK_OK;
+}
+
+static inline bool box_in_range(const sitrk_ctx *h, int j0, int j1, int i0, int i1)
+{
+    return j0 >= 0 && j1 <= h->Nj && j0 <= j1 && i0 >= 0 && i1 <= h->Ni && i0 <= i1;
+}
+
+// Rows are boxes of full width and a whole record is the box of all rows: the three forms of an ingest call go through
+// ingest_check() and then through one core, which names the box `what` ("rows" / "box") in its range message.  An empty box
+// leaves a slot that holds nothing.
+static int commit_box(sitrk_ctx *h, const char *fn, const char *what, int slot, int j0, int j1, int i0, int i1)
+{
+    if (!box_in_range(h, j0, j1, i0, i1)) return fail(h, SITRK_EINVAL, "%s: %s out of range", fn, what);
+    if (j0 == j1 || i0 == i1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
+    slot_holds(h, slot, j0, j1, i0, i1);
     HIPCHK(hipSetDevice(h->device));
-    slot_holds(h, slot, 0, h->Nj, 0, h->Ni);
-    return derive_mask(h, slot);
+    return derive_mask_box(h, slot, j0, j1, i0, i1);
+}
+
+SITRK_API int sitrk_commit_record(sitrk_t *h, int slot)
+{
+    const char *fn = "sitrk_commit_record";
+    RCCHK(ingest_check(h, fn, slot));
+    return commit_box(h, fn, "box", slot, 0, h->Nj, 0, h->Ni);
+}
+
+SITRK_API int sitrk_commit_record_rows(sitrk_t *h, int slot, int j0, int j1)
+{
+    const char *fn = "sitrk_commit_record_rows";
+    RCCHK(ingest_check(h, fn, slot));
+    return commit_box(h, fn, "rows", slot, j0, j1, 0, h->Ni);
+}
+
+SITRK_API int sitrk_commit_record_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1)
+{
+    const char *fn = "sitrk_commit_record_box";
+    RCCHK(ingest_check(h, fn, slot));
+    return commit_box(h, fn, "box", slot, j0, j1, i0, i1);
 }
 
 // ---- pinned staging + copy stream -------------------------------------------------------------------------
@@ -529,22 +566,25 @@ static int stage_acquire_box(sitrk_ctx *h, int nrows, int ncols, void **u, void 
     return SITRK_OK;
 }
 
+static int stage_acquire(sitrk_ctx *h, const char *fn, const char *what, int nrows, int ncols, void **u, void **v, void **sic)
+{
+    if (!(nrows >= 1 && nrows <= h->Nj && ncols >= 1 && ncols <= h->Ni)) return fail(h, SITRK_EINVAL, "%s: %s out of range", fn, what);
+    if (!(u && v && sic)) return fail(h, SITRK_EINVAL, "%s: null output", fn);
+    return stage_acquire_box(h, nrows, ncols, u, v, sic);
+}
+
 SITRK_API int sitrk_stage_acquire(sitrk_t *h, int nrows, void **u, void **v, void **sic)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_stage_acquire: call sitrk_alloc_records first");
-    NEED(nrows >= 1 && nrows <= h->Nj, "sitrk_stage_acquire: nrows out of range");
-    NEED(u && v && sic, "sitrk_stage_acquire: null output");
-    return stage_acquire_box(h, nrows, h->Ni, u, v, sic);
+    const char *fn = "sitrk_stage_acquire";
+    RCCHK(ingest_check(h, fn));
+    return stage_acquire(h, fn, "nrows", nrows, h->Ni, u, v, sic);
 }
 
 SITRK_API int sitrk_stage_acquire_box(sitrk_t *h, int nrows, int ncols, void **u, void **v, void **sic)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_stage_acquire_box: call sitrk_alloc_records first");
-    NEED(nrows >= 1 && nrows <= h->Nj && ncols >= 1 && ncols <= h->Ni, "sitrk_stage_acquire_box: box out of range");
-    NEED(u && v && sic, "sitrk_stage_acquire_box: null output");
-    return stage_acquire_box(h, nrows, ncols, u, v, sic);
+    const char *fn = "sitrk_stage_acquire_box";
+    RCCHK(ingest_check(h, fn));
+    return stage_acquire(h, fn, "box", nrows, ncols, u, v, sic);
 }
 
 // the staged fields travel as the box rows [j0,j1) x columns [i0,i1) of `slot`: full-width boxes as three linear copies,
@@ -580,25 +620,26 @@ static int stage_submit_box(sitrk_ctx *h, int slot, int j0, int j1, int i0, int 
     return derive_mask_box_batch(h, &slot, 1, j0, j1, i0, i1, h->async_survive != 0);
 }
 
+static int stage_submit(sitrk_ctx *h, const char *fn, const char *mismatch, int slot, int j0, int j1, int i0, int i1)
+{
+    if (h->stage_rows < 0) return fail(h, SITRK_EINVAL, "%s: nothing acquired", fn);
+    if (!(j0 >= 0 && j1 <= h->Nj && j1 - j0 == h->stage_rows && i0 >= 0 && i1 <= h->Ni && i1 - i0 == h->stage_cols))
+        return fail(h, SITRK_EINVAL, "%s: %s", fn, mismatch);
+    return stage_submit_box(h, slot, j0, j1, i0, i1);
+}
+
 SITRK_API int sitrk_stage_submit(sitrk_t *h, int slot, int j0, int j1)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_stage_submit: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_stage_submit: slot out of range");
-    NEED(h->stage_rows >= 0, "sitrk_stage_submit: nothing acquired");
-    NEED(j0 >= 0 && j1 <= h->Nj && j1 - j0 == h->stage_rows && h->stage_cols == h->Ni, "sitrk_stage_submit: rows [j0,j1) do not match the acquired buffer");
-    return stage_submit_box(h, slot, j0, j1, 0, h->Ni);
+    const char *fn = "sitrk_stage_submit";
+    RCCHK(ingest_check(h, fn, slot));
+    return stage_submit(h, fn, "rows [j0,j1) do not match the acquired buffer", slot, j0, j1, 0, h->Ni);
 }
 
 SITRK_API int sitrk_stage_submit_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_stage_submit_box: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_stage_submit_box: slot out of range");
-    NEED(h->stage_rows >= 0, "sitrk_stage_submit_box: nothing acquired");
-    NEED(j0 >= 0 && j1 <= h->Nj && j1 - j0 == h->stage_rows && i0 >= 0 && i1 <= h->Ni && i1 - i0 == h->stage_cols,
-         "sitrk_stage_submit_box: the box does not match the acquired buffer");
-    return stage_submit_box(h, slot, j0, j1, i0, i1);
+    const char *fn = "sitrk_stage_submit_box";
+    RCCHK(ingest_check(h, fn, slot));
+    return stage_submit(h, fn, "the box does not match the acquired buffer", slot, j0, j1, i0, i1);
 }
 
 SITRK_API int sitrk_stage_release(sitrk_t *h)
@@ -634,8 +675,7 @@ static inline void copy_row_stream(char *d, const char *s, size_t n)
 static int push_box(sitrk_ctx *h, int slot, int j0, int j1, int i0, int i1, const void *u, const void *v, const void *sic, int64_t ld)
 {
     void *su, *sv, *ss;
-    int rc = stage_acquire_box(h, j1 - j0, i1 - i0, &su, &sv, &ss);
-    if (rc) return rc;
+    RCCHK(stage_acquire_box(h, j1 - j0, i1 - i0, &su, &sv, &ss));
     const size_t es = elem_size(h->dtype);
     const size_t nr = (size_t)(j1 - j0), rowb = (size_t)(i1 - i0) * es, srcb = (size_t)ld * es;
     const size_t nb = nr * rowb;
@@ -673,13 +713,56 @@ static int push_box(sitrk_ctx *h, int slot, int j0, int j1, int i0, int i1, cons
     return stage_submit_box(h, slot, j0, j1, i0, i1);
 }
 
+static int push_record_box(sitrk_ctx *h, const char *fn, const char *what, int slot, int j0, int j1, int i0, int i1, const void *u,
+                           const void *v, const void *sic, int64_t ld)
+{
+    if (!box_in_range(h, j0, j1, i0, i1)) return fail(h, SITRK_EINVAL, "%s: %s out of range", fn, what);
+    if (j0 == j1 || i0 == i1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
+    if (!(u && v && sic)) return fail(h, SITRK_EINVAL, "%s: null field", fn);
+    if (ld < (int64_t)(i1 - i0)) return fail(h, SITRK_EINVAL, "%s: ld is smaller than the box is wide", fn);
+    return push_box(h, slot, j0, j1, i0, i1, u, v, sic, ld);
+}
+
 SITRK_API int sitrk_push_record(sitrk_t *h, int slot, const void *u, const void *v, const void *sic)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_push_record: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_push_record: slot out of range");
-    NEED(u && v && sic, "sitrk_push_record: null field");
-    return push_box(h, slot, 0, h->Nj, 0, h->Ni, u, v, sic, h->Ni);
+    const char *fn = "sitrk_push_record";
+    RCCHK(ingest_check(h, fn, slot));
+    return push_record_box(h, fn, "box", slot, 0, h->Nj, 0, h->Ni, u, v, sic, h->Ni);
+}
+
+SITRK_API int sitrk_push_record_rows(sitrk_t *h, int slot, int j0, int j1, const void *u_rows, const void *v_rows, const void *sic_rows)
+{
+    const char *fn = "sitrk_push_record_rows";
+    RCCHK(ingest_check(h, fn, slot));
+    return push_record_box(h, fn, "rows", slot, j0, j1, 0, h->Ni, u_rows, v_rows, sic_rows, h->Ni);
+}
+
+SITRK_API int sitrk_push_record_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1, const void *u_box, const void *v_box,
+                                    const void *sic_box, int64_t ld)
+{
+    const char *fn = "sitrk_push_record_box";
+    RCCHK(ingest_check(h, fn, slot));
+    return push_record_box(h, fn, "box", slot, j0, j1, i0, i1, u_box, v_box, sic_box, ld);
+}
+
+// The reduction of the live buoys' host cells to {max j, max -j, max i, max -i}, queued on the compute stream: into the four ints
+// `d` of h->counter (the synchronous and the begin / end form use different halves of it), then copied to the host's `res`
+static int queue_buoy_box(sitrk_ctx *h, int *d, int *res)
+{
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemsetAsync(d, 0x80, 4 * sizeof(int), h->stream));    // four maxima start at -2139062144
+    hipLaunchKernelGGL(buoy_box_kernel, dim3(std::min(nblocks(h->nP, 4 * kBlock), 2048u)), dim3(kBlock), 0, h->stream, h->nP, h->st[h->cur].cell, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(download(h, res, d, 4));
+    return SITRK_OK;
+}
+
+// ... and its result adopted as the box the partly uploaded slots are checked against (res[0] < 0: no live buoy, an empty box)
+static void adopt_buoy_box(sitrk_ctx *h, const int *res, int age)
+{
+    h->band_jmin = 1; h->band_jmax = 0; h->band_imin = 1; h->band_imax = 0;
+    if (res[0] >= 0) { h->band_jmax = res[0]; h->band_jmin = -res[1]; h->band_imax = res[2]; h->band_imin = -res[3]; }
+    h->band_age = age;
 }
 
 // rows and columns of the live buoys' host cells (one small kernel + one synchronisation of the compute stream)
@@ -690,16 +773,10 @@ static int eval_buoy_box(sitrk_ctx *h)
     h->band_age = -1;                   // no box is known until this evaluation has succeeded (check_band refuses partial slots meanwhile)
     if (h->nP == 0) { h->band_age = 0; return SITRK_OK; }
     NEED(h->st[0].pos, "sitrk_buoy_rows: call sitrk_set_buoys first");
-    HIPCHK(hipSetDevice(h->device));
     int res[4];
-    int *d = (int *)h->counter;                                     // first half of the 32-byte reduction scratch
-    HIPCHK(hipMemsetAsync(d, 0x80, 4 * sizeof(int), h->stream));    // four maxima start at -2139062144
-    hipLaunchKernelGGL(buoy_box_kernel, dim3(std::min(nblocks(h->nP, 4 * kBlock), 2048u)), dim3(kBlock), 0, h->stream, h->nP, h->st[h->cur].cell, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(res, d, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    RCCHK(queue_buoy_box(h, (int *)h->counter, res));      // first half of the 32-byte reduction scratch
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (res[0] >= 0) { h->band_jmax = res[0]; h->band_jmin = -res[1]; h->band_imax = res[2]; h->band_imin = -res[3]; }
-    h->band_age = 0;
+    adopt_buoy_box(h, res, 0);
     return SITRK_OK;
 }
 
@@ -708,8 +785,7 @@ SITRK_API int sitrk_buoy_rows(sitrk_t *h, int32_t *jmin, int32_t *jmax)
     NEED(h, "null handle");
     NEED(jmin && jmax, "sitrk_buoy_rows: null output");
     *jmin = 1; *jmax = 0;
-    int rc = eval_buoy_box(h);
-    if (rc) return rc;
+    RCCHK(eval_buoy_box(h));
     *jmin = h->band_jmin; *jmax = h->band_jmax;
     return SITRK_OK;
 }
@@ -719,8 +795,7 @@ SITRK_API int sitrk_buoy_box(sitrk_t *h, int32_t *jmin, int32_t *jmax, int32_t *
     NEED(h, "null handle");
     NEED(jmin && jmax && imin && imax, "sitrk_buoy_box: null output");
     *jmin = 1; *jmax = 0; *imin = 1; *imax = 0;
-    int rc = eval_buoy_box(h);
-    if (rc) return rc;
+    RCCHK(eval_buoy_box(h));
     *jmin = h->band_jmin; *jmax = h->band_jmax; *imin = h->band_imin; *imax = h->band_imax;
     return SITRK_OK;
 }
@@ -736,12 +811,7 @@ SITRK_API int sitrk_buoy_box_begin(sitrk_t *h)
     h->box_pending_age = 0;
     if (h->nP == 0) { h->box_pending = true; return SITRK_OK; }
     NEED(h->st[0].pos, "sitrk_buoy_box_begin: call sitrk_set_buoys first");
-    HIPCHK(hipSetDevice(h->device));
-    int *d = (int *)h->counter + 4;                                 // second half of the 32-byte reduction scratch
-    HIPCHK(hipMemsetAsync(d, 0x80, 4 * sizeof(int), h->stream));
-    hipLaunchKernelGGL(buoy_box_kernel, dim3(std::min(nblocks(h->nP, 4 * kBlock), 2048u)), dim3(kBlock), 0, h->stream, h->nP, h->st[h->cur].cell, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->box_host, d, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    RCCHK(queue_buoy_box(h, (int *)h->counter + 4, h->box_host));      // second half of the 32-byte reduction scratch
     HIPCHK(hipEventRecord(h->box_ev, h->stream));
     h->box_pending = true;              // only now: an evaluation that failed to queue leaves nothing to collect
     return SITRK_OK;
@@ -754,63 +824,10 @@ SITRK_API int sitrk_buoy_box_end(sitrk_t *h, int32_t *jmin, int32_t *jmax, int32
     NEED(jmin && jmax && imin && imax, "sitrk_buoy_box_end: null output");
     if (h->nP > 0) HIPCHK(hipEventSynchronize(h->box_ev));
     h->box_pending = false;
-    if (h->nP > 0 && h->box_host[0] >= 0) {
-        h->band_jmax = h->box_host[0]; h->band_jmin = -h->box_host[1]; h->band_imax = h->box_host[2]; h->band_imin = -h->box_host[3];
-    } else {
-        h->band_jmin = 1; h->band_jmax = 0; h->band_imin = 1; h->band_imax = 0;
-    }
-    h->band_age = h->box_pending_age;
+    adopt_buoy_box(h, h->box_host, h->box_pending_age);          // (no buoys: the begin left {-1, 0, -1, 0} there)
     *jmin = h->band_jmin; *jmax = h->band_jmax; *imin = h->band_imin; *imax = h->band_imax;
     if (age) *age = h->band_age;
     return SITRK_OK;
-}
-
-SITRK_API int sitrk_push_record_rows(sitrk_t *h, int slot, int j0, int j1, const void *u_rows, const void *v_rows, const void *sic_rows)
-{
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_push_record_rows: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_push_record_rows: slot out of range");
-    NEED(j0 >= 0 && j1 <= h->Nj && j0 <= j1, "sitrk_push_record_rows: rows out of range");
-    if (j0 == j1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
-    NEED(u_rows && v_rows && sic_rows, "sitrk_push_record_rows: null field");
-    return push_box(h, slot, j0, j1, 0, h->Ni, u_rows, v_rows, sic_rows, h->Ni);
-}
-
-SITRK_API int sitrk_push_record_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1, const void *u_box, const void *v_box,
-                                    const void *sic_box, int64_t ld)
-{
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_push_record_box: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_push_record_box: slot out of range");
-    NEED(j0 >= 0 && j1 <= h->Nj && j0 <= j1 && i0 >= 0 && i1 <= h->Ni && i0 <= i1, "sitrk_push_record_box: box out of range");
-    if (j0 == j1 || i0 == i1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
-    NEED(u_box && v_box && sic_box, "sitrk_push_record_box: null field");
-    NEED(ld >= (int64_t)(i1 - i0), "sitrk_push_record_box: ld is smaller than the box is wide");
-    return push_box(h, slot, j0, j1, i0, i1, u_box, v_box, sic_box, ld);
-}
-
-SITRK_API int sitrk_commit_record_rows(sitrk_t *h, int slot, int j0, int j1)
-{
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_commit_record_rows: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_commit_record_rows: slot out of range");
-    NEED(j0 >= 0 && j1 <= h->Nj && j0 <= j1, "sitrk_commit_record_rows: rows out of range");
-    if (j0 == j1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
-    slot_holds(h, slot, j0, j1, 0, h->Ni);
-    HIPCHK(hipSetDevice(h->device));
-    return derive_mask_box(h, slot, j0, j1, 0, h->Ni);
-}
-
-SITRK_API int sitrk_commit_record_box(sitrk_t *h, int slot, int j0, int j1, int i0, int i1)
-{
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_commit_record_box: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_commit_record_box: slot out of range");
-    NEED(j0 >= 0 && j1 <= h->Nj && j0 <= j1 && i0 >= 0 && i1 <= h->Ni && i0 <= i1, "sitrk_commit_record_box: box out of range");
-    if (j0 == j1 || i0 == i1) { slot_holds(h, slot, 0, 0, 0, 0); return SITRK_OK; }
-    slot_holds(h, slot, j0, j1, i0, i1);
-    HIPCHK(hipSetDevice(h->device));
-    return derive_mask_box(h, slot, j0, j1, i0, i1);
 }
 
 static int commit_records_box(sitrk_ctx *h, int slot0, int nrec, int j0, int j1, int i0, int i1, bool on_ingest);
@@ -827,11 +844,9 @@ SITRK_API int sitrk_commit_records_box_async(sitrk_t *h, int slot0, int nrec, in
 
 static int commit_records_box(sitrk_ctx *h, int slot0, int nrec, int j0, int j1, int i0, int i1, bool on_ingest)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_commit_records_box: call sitrk_alloc_records first");
-    NEED(slot0 >= 0 && slot0 < h->nslots, "sitrk_commit_records_box: slot0 out of range");
+    RCCHK(ingest_check(h, "sitrk_commit_records_box", slot0, "slot0"));
     NEED(nrec >= 0 && nrec <= h->nslots, "sitrk_commit_records_box: more records than slots");
-    NEED(j0 >= 0 && j1 <= h->Nj && j0 <= j1 && i0 >= 0 && i1 <= h->Ni && i0 <= i1, "sitrk_commit_records_box: box out of range");
+    NEED(box_in_range(h, j0, j1, i0, i1), "sitrk_commit_records_box: box out of range");
     HIPCHK(hipSetDevice(h->device));
     const bool empty = (j0 == j1 || i0 == i1);
     for (int k = 0; k < nrec; k += kSvMaxBatch) {
@@ -843,24 +858,19 @@ static int commit_records_box(sitrk_ctx *h, int slot0, int nrec, int j0, int j1,
             else slot_holds(h, slots[q], j0, j1, i0, i1);
         }
         if (empty) continue;
-        int rc = derive_mask_box_batch(h, slots, nb, j0, j1, i0, i1, on_ingest);
-        if (rc) return rc;
+        RCCHK(derive_mask_box_batch(h, slots, nb, j0, j1, i0, i1, on_ingest));
     }
     return SITRK_OK;
 }
 
 SITRK_API int sitrk_push_record_dev(sitrk_t *h, int slot, const void *slab_dev)
 {
-    NEED(h, "null handle");
-    NEED(h->slabs, "sitrk_push_record_dev: call sitrk_alloc_records first");
-    NEED(slot >= 0 && slot < h->nslots, "sitrk_push_record_dev: slot out of range");
+    RCCHK(ingest_check(h, "sitrk_push_record_dev", slot));
     NEED(slab_dev, "sitrk_push_record_dev: null slab");
     HIPCHK(hipSetDevice(h->device));
     void *d = slab_of(h, slot);
-    int rc = slot_wait_upload(h, slot);
-    if (rc) return rc;
-    rc = slot_wait_sv(h, slot);                         // (a derivation still reading the slot's siconc on the ingest stream)
-    if (rc) return rc;
+    RCCHK(slot_wait_upload(h, slot));
+    RCCHK(slot_wait_sv(h, slot));      // (a derivation still reading the slot's siconc on the ingest stream)
     if (d != slab_dev) HIPCHK(hipMemcpyAsync(d, slab_dev, h->slab_bytes, hipMemcpyDeviceToDevice, h->stream));
     slot_holds(h, slot, 0, h->Nj, 0, h->Ni);
     return derive_mask(h, slot);
@@ -953,13 +963,13 @@ SITRK_API int sitrk_set_buoys(sitrk_t *h, int64_t nP, const double *yx, const in
     h->nP = nP;
     if (nP == 0) return SITRK_OK;
     BuoyState &s = h->st[0];
-    HIPCHK(hipMemcpyAsync(s.pos, yx, (size_t)nP * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s.cell, packed.data(), (size_t)nP * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(s.kill_rec, 0xff, (size_t)nP * 4, h->stream));          // -1
+    HIPCHK(upload(h, s.pos, yx, nP));
+    HIPCHK(upload(h, s.cell, packed.data(), nP));
+    HIPCHK(hipMemsetAsync(s.kill_rec, 0xff, (size_t)nP * sizeof(*s.kill_rec), h->stream));          // -1
     hipLaunchKernelGGL(iota_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, s.perm);
     HIPCHK(hipGetLastError());
     if (h->windowed) {
-        HIPCHK(hipMemcpyAsync(s.win, win.data(), (size_t)nP * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(upload(h, s.win, win.data(), nP));
     }
     HIPCHK(hipStreamSynchronize(h->stream));      // `packed` must outlive the copy
     return SITRK_OK;
@@ -973,18 +983,15 @@ SITRK_API int sitrk_restore_state(sitrk_t *h, const int8_t *alive, const int32_t
     const int64_t nP = h->nP;
     if (nP == 0) return SITRK_OK;
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_a = align256((size_t)nP), b_k = align256((size_t)nP * 4);
-    int rc = ensure_scratch(h, b_a + b_k);
-    if (rc) return rc;
-    char *w = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(w, alive, (size_t)nP, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(w + b_a, kill_rec, (size_t)nP * 4, hipMemcpyHostToDevice, h->stream));
+    int8_t *d_al; int32_t *d_kr;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_al, nP); c.take(d_kr, nP); }));
+    HIPCHK(upload(h, d_al, alive, nP));
+    HIPCHK(upload(h, d_kr, kill_rec, nP));
     HIPCHK(hipMemsetAsync(h->counter, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(restore_state_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->st[h->cur], (const int8_t *)w,
-                       (const int32_t *)(w + b_a), h->counter);
+    hipLaunchKernelGGL(restore_state_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->st[h->cur], d_al, d_kr, h->counter);
     HIPCHK(hipGetLastError());
     unsigned long long rim = 0;
-    HIPCHK(hipMemcpyAsync(&rim, h->counter, sizeof(rim), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, &rim, h->counter, 1));
     HIPCHK(hipStreamSynchronize(h->stream));          // the caller's arrays are its own again
     h->rim_buoys = rim != 0;                          // dead buoys sit where they died, often in the rim: they never step
     return SITRK_OK;
@@ -1044,29 +1051,38 @@ static inline bool window_test_needed(const sitrk_ctx *h, int jrec0, int n)
     return h->windowed && !(jrec0 >= h->win_first_max && (int64_t)jrec0 + n - 1 <= h->win_last_min);
 }
 
-template <typename FT, int BLOCK>
-static void launch_step_b(sitrk_ctx *h, const StepArgs &a)
+// The one choice of a stepping kernel's instance: launch(ft, uvs, win) is called with tags for the field type (h->dtype), the
+// velocity pick (h->uv_strategy) and the per-buoy window test; the launchers below supply kernel, grid, block, LDS and arguments.
+template <typename T> struct TypeTag { using type = T; };
+
+template <typename Launch>
+static void pick_kernel(const sitrk_ctx *h, bool windowed, Launch &&launch)
 {
-    const bool windowed = window_test_needed(h, a.jrec, 1);
-    dim3 grid(nblocks(a.nP, BLOCK)), block(BLOCK);
-    if (h->uv_strategy == 1) {
-        if (windowed) hipLaunchKernelGGL((advect_step_kernel<FT, 1, true, BLOCK>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((advect_step_kernel<FT, 1, false, BLOCK>), grid, block, 0, h->stream, a);
-    } else if (h->uv_strategy == 2) {
-        if (windowed) hipLaunchKernelGGL((advect_step_kernel<FT, 2, true, BLOCK>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((advect_step_kernel<FT, 2, false, BLOCK>), grid, block, 0, h->stream, a);
-    } else {
-        if (windowed) hipLaunchKernelGGL((advect_step_kernel<FT, 0, true, BLOCK>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((advect_step_kernel<FT, 0, false, BLOCK>), grid, block, 0, h->stream, a);
-    }
+    auto pick_ft = [&](auto uvs, auto win) {
+        if (h->dtype == SITRK_F64) launch(TypeTag<double>(), uvs, win);
+        else launch(TypeTag<float>(), uvs, win);
+    };
+    auto pick_win = [&](auto uvs) {
+        if (windowed) pick_ft(uvs, std::true_type());
+        else pick_ft(uvs, std::false_type());
+    };
+    if (h->uv_strategy == 1) pick_win(std::integral_constant<int, 1>());
+    else if (h->uv_strategy == 2) pick_win(std::integral_constant<int, 2>());
+    else pick_win(std::integral_constant<int, 0>());
 }
 
-template <typename FT>
 static void launch_step(sitrk_ctx *h, const StepArgs &a)
 {
-    if (h->step_block == 1024) launch_step_b<FT, 1024>(h, a);
-    else if (h->step_block == 512) launch_step_b<FT, 512>(h, a);
-    else launch_step_b<FT, 256>(h, a);
+    pick_kernel(h, window_test_needed(h, a.jrec, 1), [&](auto ft, auto uvs, auto win) {
+        using FT = typename decltype(ft)::type;
+        constexpr int UVS = decltype(uvs)::value;
+        constexpr bool WIN = decltype(win)::value;
+        const int bs = h->step_block == 1024 || h->step_block == 512 ? h->step_block : 256;
+        const dim3 grid(nblocks(a.nP, bs)), block(bs);
+        if (bs == 1024) hipLaunchKernelGGL((advect_step_kernel<FT, UVS, WIN, 1024>), grid, block, 0, h->stream, a);
+        else if (bs == 512) hipLaunchKernelGGL((advect_step_kernel<FT, UVS, WIN, 512>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((advect_step_kernel<FT, UVS, WIN, 256>), grid, block, 0, h->stream, a);
+    });
 }
 
 // the fused kernels address the geometry with 32-bit byte offsets and have no negative-index wrap: buoy sets seeded in the two
@@ -1086,20 +1102,11 @@ SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
     NEED(h->slabs, "sitrk_step: call sitrk_alloc_records first");
     NEED(slot >= 0 && slot < h->nslots, "sitrk_step: slot out of range");
     if (h->nP == 0) return SITRK_OK;
-    int rc = check_band(h, slot, 0);
-    if (rc) return rc;
+    RCCHK(check_band(h, slot, 0));
     if (h->resort_every > 0 && h->steps_since_sort >= h->resort_every) {
-        rc = sitrk_sort_buoys(h);
-        if (rc) return rc;
+        RCCHK(sitrk_sort_buoys(h));
     }
-    if (h->slot_dirty[slot]) {            // slab written through sitrk_record_ptr and not committed yet
-        rc = derive_mask(h, slot);
-        if (rc) return rc;
-    }
-    rc = slot_wait_upload(h, slot);
-    if (rc) return rc;
-    rc = slot_wait_sv(h, slot);
-    if (rc) return rc;
+    RCCHK(slot_make_ready(h, slot));
     if (h->nsub > 1 && fused_ok(h)) return launch_records(h, slot, jrec, 1);      // the sub-stepping kernel with one record
     const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
     const char *slab = slab_of(h, slot);
@@ -1114,16 +1121,12 @@ SITRK_API int sitrk_step(sitrk_t *h, int slot, int jrec)
     // the one-record kernel nsub times with dt_sub and the same jrec -- the same sub-steps, one launch each
     if (h->nsub > 1) a.rdt = h->rdt / h->nsub;
     for (int sub = 0; sub < h->nsub; sub++) {
-        if (h->dtype == SITRK_F64) launch_step<double>(h, a);
-        else launch_step<float>(h, a);
+        launch_step(h, a);
         HIPCHK(hipGetLastError());
     }
-    rc = launch_mark(h, &slot, 1);
-    if (rc) return rc;
-    h->steps_since_sort++;
+    RCCHK(launch_mark(h, &slot, 1));
     h->n_step_launches += h->nsub;
-    if (h->band_age >= 0) h->band_age++;
-    if (h->box_pending) h->box_pending_age++;
+    records_stepped(h, 1);
     return SITRK_OK;
 }
 
@@ -1134,41 +1137,19 @@ static int f32_class_for(double rdt)
     return (ar >= 0x1p-700 && ar <= 0x1p700) ? kClassFiniteNonzeroF32 : 0;
 }
 
-template <typename FT>
-static void launch_run(sitrk_ctx *h, const RunArgs &ra, hipStream_t stream)
+// advect_run_kernel (nsub == 1) or advect_substep_kernel (nsub > 1) over the records of `ra`
+static void launch_run(sitrk_ctx *h, const RunArgs &ra, int nsub, hipStream_t stream)
 {
-    dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
+    const dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
     // dynamic LDS: tables + the patch's F-points
     const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
-    const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
-    if (h->uv_strategy == 1) {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 1, true>), grid, block, lds, stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 1, false>), grid, block, lds, stream, ra);
-    } else if (h->uv_strategy == 2) {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 2, true>), grid, block, lds, stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 2, false>), grid, block, lds, stream, ra);
-    } else {
-        if (windowed) hipLaunchKernelGGL((advect_run_kernel<FT, 0, true>), grid, block, lds, stream, ra);
-        else hipLaunchKernelGGL((advect_run_kernel<FT, 0, false>), grid, block, lds, stream, ra);
-    }
-}
-
-template <typename FT>
-static void launch_substep(sitrk_ctx *h, const RunArgs &ra, int nsub, hipStream_t stream)
-{
-    dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
-    const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
-    const bool windowed = window_test_needed(h, ra.s.jrec, ra.nrec);
-    if (h->uv_strategy == 1) {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 1, true>), grid, block, lds, stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 1, false>), grid, block, lds, stream, ra, nsub);
-    } else if (h->uv_strategy == 2) {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 2, true>), grid, block, lds, stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 2, false>), grid, block, lds, stream, ra, nsub);
-    } else {
-        if (windowed) hipLaunchKernelGGL((advect_substep_kernel<FT, 0, true>), grid, block, lds, stream, ra, nsub);
-        else hipLaunchKernelGGL((advect_substep_kernel<FT, 0, false>), grid, block, lds, stream, ra, nsub);
-    }
+    pick_kernel(h, window_test_needed(h, ra.s.jrec, ra.nrec), [&](auto ft, auto uvs, auto win) {
+        using FT = typename decltype(ft)::type;
+        constexpr int UVS = decltype(uvs)::value;
+        constexpr bool WIN = decltype(win)::value;
+        if (nsub > 1) hipLaunchKernelGGL((advect_substep_kernel<FT, UVS, WIN>), grid, block, lds, stream, ra, nsub);
+        else hipLaunchKernelGGL((advect_run_kernel<FT, UVS, WIN>), grid, block, lds, stream, ra);
+    });
 }
 
 // records jrec0 .. jrec0+m-1 from slots (slot_first + r) % nslots in ONE launch: advect_run_kernel (nsub == 1) or
@@ -1200,36 +1181,19 @@ static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m, int64_
         const int slot = (slot_first + r) % h->nslots;
         used[r] = slot;
         if (!lane) {
-            int rc = check_band(h, slot, r);
-            if (rc) return rc;
-            if (h->slot_dirty[slot]) {
-                rc = derive_mask(h, slot);
-                if (rc) return rc;
-            }
-            rc = slot_wait_upload(h, slot);
-            if (rc) return rc;
-            rc = slot_wait_sv(h, slot);
-            if (rc) return rc;
+            RCCHK(check_band(h, slot, r));
+            RCCHK(slot_make_ready(h, slot));
         }
         const char *slab = slab_of(h, slot);
         ra.u[r] = slab; ra.v[r] = slab + n * es; ra.kill9[r] = h->kill9 + (size_t)slot * n;
     }
-    if (h->nsub > 1) {
-        if (h->dtype == SITRK_F64) launch_substep<double>(h, ra, h->nsub, stream);
-        else launch_substep<float>(h, ra, h->nsub, stream);
-    } else {
-        if (h->dtype == SITRK_F64) launch_run<double>(h, ra, stream);
-        else launch_run<float>(h, ra, stream);
-    }
+    launch_run(h, ra, h->nsub, stream);
     HIPCHK(hipGetLastError());
     if (lane) return SITRK_OK;
-    int rc = launch_mark(h, used, m);
-    if (rc) return rc;
-    h->steps_since_sort += m;
+    RCCHK(launch_mark(h, used, m));
     h->n_fused_launches++;
     h->n_fused_records += m;
-    if (h->band_age >= 0) h->band_age += m;
-    if (h->box_pending) h->box_pending_age += m;
+    records_stepped(h, m);
     return SITRK_OK;
 }
 
@@ -1260,12 +1224,7 @@ static int lanes_prepare(sitrk_ctx *h, int slot_first, int seg, bool *ok)
     for (int q = 0; q < seg; q++)
         if (check_band(h, (slot_first + q) % h->nslots, q)) return SITRK_OK;
     for (int q = 0; q < std::min(seg, h->nslots); q++) {
-        const int slot = (slot_first + q) % h->nslots;
-        int rc = SITRK_OK;
-        if (h->slot_dirty[slot]) rc = derive_mask(h, slot);
-        if (!rc) rc = slot_wait_upload(h, slot);
-        if (!rc) rc = slot_wait_sv(h, slot);
-        if (rc) return rc;
+        RCCHK(slot_make_ready(h, (slot_first + q) % h->nslots));
     }
     for (int k = 0; k < h->nslots; k++)
         if (h->slot_sv_pending[k]) return SITRK_OK;
@@ -1313,9 +1272,7 @@ static int run_lanes(sitrk_ctx *h, int slot_first, int jrec0, int seg, int fuse,
         q += m;
     }
     h->n_lane_segments++;
-    h->steps_since_sort += seg;
-    if (h->band_age >= 0) h->band_age += seg;
-    if (h->box_pending) h->box_pending_age += seg;
+    records_stepped(h, seg);
     return SITRK_OK;
 }
 
@@ -1333,8 +1290,7 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
     int k = 0;
     while (k < nsteps) {
         if (h->resort_every > 0 && h->steps_since_sort >= h->resort_every) {
-            int rc = sitrk_sort_buoys(h);
-            if (rc) return rc;
+            RCCHK(sitrk_sort_buoys(h));
         }
         if (cut > 0) {
             // a segment = the records up to the next join (re-sort or return).  Lanes where it holds two full launches per lane
@@ -1343,12 +1299,10 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
             if (h->resort_every > 0) seg = std::min(seg, h->resort_every - h->steps_since_sort);
             bool ok = false;
             if (seg >= 2 * fuse + fuse / 2) {
-                int rc = lanes_prepare(h, (slot0 + k) % h->nslots, seg, &ok);
-                if (rc) return rc;
+                RCCHK(lanes_prepare(h, (slot0 + k) % h->nslots, seg, &ok));
             }
             if (ok) {
-                int rc = run_lanes(h, (slot0 + k) % h->nslots, jrec0 + k, seg, fuse, cut);
-                if (rc) return rc;
+                RCCHK(run_lanes(h, (slot0 + k) % h->nslots, jrec0 + k, seg, fuse, cut));
                 k += seg;
                 continue;
             }
@@ -1356,14 +1310,12 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
         int m = std::min(fuse, nsteps - k);
         if (h->resort_every > 0) m = std::min(m, h->resort_every - h->steps_since_sort);
         if (m <= 1) {
-            int rc = sitrk_step(h, (slot0 + k) % h->nslots, jrec0 + k);
-            if (rc) return rc;
+            RCCHK(sitrk_step(h, (slot0 + k) % h->nslots, jrec0 + k));
             k += 1;
             continue;
         }
         // m consecutive records, all resident in distinct slots, in one launch
-        int rc = launch_records(h, (slot0 + k) % h->nslots, jrec0 + k, m);
-        if (rc) return rc;
+        RCCHK(launch_records(h, (slot0 + k) % h->nslots, jrec0 + k, m));
         k += m;
     }
     return SITRK_OK;
@@ -1396,21 +1348,17 @@ SITRK_API int sitrk_fetch(sitrk_t *h, double *yx, int32_t *jiT, int8_t *alive, i
     const int64_t nP = h->nP;
     if (nP == 0) return SITRK_OK;
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_yx = align256((size_t)nP * sizeof(pt)), b_ji = align256((size_t)nP * 8), b_al = align256((size_t)nP),
-                 b_kr = align256((size_t)nP * 4);
-    int rc = ensure_scratch(h, b_yx + b_ji + b_al + b_kr);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    pt *d_yx = yx ? (pt *)s : nullptr;
-    int32_t *d_ji = jiT ? (int32_t *)(s + b_yx) : nullptr;
-    int8_t *d_al = alive ? (int8_t *)(s + b_yx + b_ji) : nullptr;
-    int32_t *d_kr = kill_rec ? (int32_t *)(s + b_yx + b_ji + b_al) : nullptr;
-    hipLaunchKernelGGL(fetch_state_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->st[h->cur], d_yx, d_ji, d_al, d_kr);
+    pt *d_yx; int32_t *d_ji, *d_kr; int8_t *d_al;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_yx, nP); c.take(d_ji, 2 * nP); c.take(d_al, nP); c.take(d_kr, nP);
+    }));
+    hipLaunchKernelGGL(fetch_state_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->st[h->cur], yx ? d_yx : nullptr,
+                       jiT ? d_ji : nullptr, alive ? d_al : nullptr, kill_rec ? d_kr : nullptr);
     HIPCHK(hipGetLastError());
-    if (yx) HIPCHK(hipMemcpyAsync(yx, d_yx, (size_t)nP * sizeof(pt), hipMemcpyDeviceToHost, h->stream));
-    if (jiT) HIPCHK(hipMemcpyAsync(jiT, d_ji, (size_t)nP * 8, hipMemcpyDeviceToHost, h->stream));
-    if (alive) HIPCHK(hipMemcpyAsync(alive, d_al, (size_t)nP, hipMemcpyDeviceToHost, h->stream));
-    if (kill_rec) HIPCHK(hipMemcpyAsync(kill_rec, d_kr, (size_t)nP * 4, hipMemcpyDeviceToHost, h->stream));
+    if (yx) HIPCHK(download(h, yx, d_yx, nP));
+    if (jiT) HIPCHK(download(h, jiT, d_ji, 2 * nP));
+    if (alive) HIPCHK(download(h, alive, d_al, nP));
+    if (kill_rec) HIPCHK(download(h, kill_rec, d_kr, nP));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1442,22 +1390,17 @@ SITRK_API int sitrk_fetch_record(sitrk_t *h, int jrec, double *yx_rec, int8_t *m
     const int64_t nP = h->nP;
     if (nP == 0) return SITRK_OK;
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_yx = align256((size_t)nP * sizeof(pt)), b_mk = align256((size_t)nP);
-    int rc = ensure_scratch(h, 2 * b_yx + b_mk);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    pt *d_yx = (pt *)s;
-    int8_t *d_mk = (int8_t *)(s + b_yx);
-    ll *d_ll = (ll *)(s + b_yx + b_mk);
+    pt *d_yx; int8_t *d_mk; ll *d_ll;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_yx, nP); c.take(d_mk, nP); c.take(d_ll, nP); }));
     hipLaunchKernelGGL(fetch_record_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, jrec, h->st[h->cur], h->windowed, d_yx, d_mk);
     HIPCHK(hipGetLastError());
     if (latlon) {
         hipLaunchKernelGGL(cart2geo_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, make_proj(70., -45.), d_yx, d_ll);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(latlon, d_ll, (size_t)nP * sizeof(ll), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(download(h, latlon, d_ll, nP));
     }
-    if (yx_rec) HIPCHK(hipMemcpyAsync(yx_rec, d_yx, (size_t)nP * sizeof(pt), hipMemcpyDeviceToHost, h->stream));
-    if (mask) HIPCHK(hipMemcpyAsync(mask, d_mk, (size_t)nP, hipMemcpyDeviceToHost, h->stream));
+    if (yx_rec) HIPCHK(download(h, yx_rec, d_yx, nP));
+    if (mask) HIPCHK(download(h, mask, d_mk, nP));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1474,7 +1417,7 @@ SITRK_API int sitrk_count_alive(sitrk_t *h, int64_t *nalive)
     hipLaunchKernelGGL(count_alive_kernel, dim3(std::min(nblocks(h->nP), 2048u)), dim3(kBlock), 0, h->stream, h->nP, h->st[h->cur].cell, h->counter);
     HIPCHK(hipGetLastError());
     unsigned long long v = 0;
-    HIPCHK(hipMemcpyAsync(&v, h->counter, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, &v, h->counter, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     *nalive = (int64_t)v;
     return SITRK_OK;
@@ -1489,41 +1432,43 @@ SITRK_API int sitrk_find_cells(sitrk_t *h, int64_t n, const double *yx, const in
     if (n == 0) return SITRK_OK;
     NEED(yx && jiT_guess && jiT_out && found, "sitrk_find_cells: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_yx = align256((size_t)n * sizeof(pt)), b_ji = align256((size_t)n * 8), b_f = align256((size_t)n);
-    int rc = ensure_scratch(h, b_yx + 2 * b_ji + b_f);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    pt *d_yx = (pt *)s;
-    int32_t *d_g = (int32_t *)(s + b_yx), *d_o = (int32_t *)(s + b_yx + b_ji);
-    int8_t *d_f = (int8_t *)(s + b_yx + 2 * b_ji);
-    HIPCHK(hipMemcpyAsync(d_yx, yx, (size_t)n * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_g, jiT_guess, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    pt *d_yx; int32_t *d_g, *d_o; int8_t *d_f;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_yx, n); c.take(d_g, 2 * n); c.take(d_o, 2 * n); c.take(d_f, n);
+    }));
+    HIPCHK(upload(h, d_yx, yx, n));
+    HIPCHK(upload(h, d_g, jiT_guess, 2 * n));
     hipLaunchKernelGGL(find_cells_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, h->Nj, h->Ni, h->geo, d_yx, d_g, d_o, d_f);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(jiT_out, d_o, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(found, d_f, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, jiT_out, d_o, 2 * n));
+    HIPCHK(download(h, found, d_f, n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
 
 // Nearest T-point of nP seeds by exact branch-and-bound over bounding spheres of the mesh (sitrk_locate.h):
-// kernels are enqueued on h->stream; *kb / *db (flat index, Haversine distance) live in the work buffer *w, which the
-// caller frees after synchronising.  Seeds farther than anything NearestPoint's acceptance loop can accept get
+// kernels are enqueued on h->stream; kb / db (flat index, Haversine distance) live in a work buffer of their own, which is
+// freed here once `finish(kb, db)` has queued the kernel that consumes them and the stream has drained; errors of that tail
+// are reported as "<what> launch" / "<what_sync>".  Seeds farther than anything NearestPoint's acceptance loop can accept get
 // kb = 0xffffffff without a search.
+template <typename Finish>
 static int nearest_search(sitrk_ctx *h, int64_t nP, const ll *d_ll, const double *d_lat, const double *d_lon, const double *resolkm_host,
-                          double rd_found_km, int max_itr, char **w_out, uint32_t **kb_out, double **db_out)
+                          double rd_found_km, int max_itr, const char *what, const char *what_sync, Finish &&finish)
 {
     const size_t n = (size_t)h->Nj * h->Ni;
     const int nbj = (h->Nj + kLB - 1) / kLB, nbi = (h->Ni + kLB - 1) / kLB, sbf = 16;
     const int nsj = (nbj + sbf - 1) / sbf, nsi = (nbi + sbf - 1) / sbf;
-    const size_t b_u = align256(n * 8), b_blk = align256((size_t)nbj * nbi * sizeof(Sphere)),
-                 b_sb = align256((size_t)nsj * nsi * sizeof(Sphere)), b_kb = align256((size_t)nP * 4), b_db = align256((size_t)nP * 8);
-    char *w = nullptr;
-    HIPCHK(hipMalloc((void **)&w, 3 * b_u + b_blk + b_sb + b_kb + b_db));
-    double *ux = (double *)w, *uy = (double *)(w + b_u), *uz = (double *)(w + 2 * b_u);
-    Sphere *blk = (Sphere *)(w + 3 * b_u), *sblk = (Sphere *)(w + 3 * b_u + b_blk);
-    uint32_t *kb = (uint32_t *)(w + 3 * b_u + b_blk + b_sb);
-    double *db = (double *)(w + 3 * b_u + b_blk + b_sb + b_kb);
+    double *ux, *uy, *uz, *db; Sphere *blk, *sblk; uint32_t *kb;
+    auto layout = [&](Carver &c) {
+        c.take(ux, n); c.take(uy, n); c.take(uz, n);
+        c.take(blk, (size_t)nbj * nbi); c.take(sblk, (size_t)nsj * nsi);
+        c.take(kb, nP); c.take(db, nP);
+    };
+    Carver w;
+    layout(w);
+    HIPCHK(hipMalloc((void **)&w.base, w.off));
+    w.off = 0;
+    layout(w);
     hipLaunchKernelGGL(unitvec_kernel, dim3(nblocks((int64_t)n)), dim3(kBlock), 0, h->stream, n, d_lat, d_lon, ux, uy, uz);
     hipLaunchKernelGGL(block_sphere_kernel, dim3((unsigned)(nbj * nbi)), dim3(kBlock), 0, h->stream, h->Nj, h->Ni, nbi, ux, uy, uz, blk);
     hipLaunchKernelGGL(superblock_sphere_kernel, dim3((unsigned)(nsj * nsi)), dim3(kBlock), 0, h->stream, nbj, nbi, sbf, nsi, blk, sblk);
@@ -1545,7 +1490,12 @@ static int nearest_search(sitrk_ctx *h, int64_t nP, const ll *d_ll, const double
         sa.far2 = (std::isfinite(dmax) && dmax >= 0.0) ? chord * chord : __builtin_inf();
     }
     hipLaunchKernelGGL(seed_search_kernel, dim3(nblocks(nP, kBlock / 64)), dim3(kBlock), 0, h->stream, sa);
-    *w_out = w; *kb_out = kb; *db_out = db;
+    finish(kb, db);
+    hipError_t le = hipGetLastError();
+    hipError_t se = hipStreamSynchronize(h->stream);
+    (void)hipFree(w.base);
+    if (le != hipSuccess) return fail(h, SITRK_EHIP, "%s launch -> %s", what, hipGetErrorString(le));
+    if (se != hipSuccess) return fail(h, SITRK_EHIP, "%s -> %s", what_sync, hipGetErrorString(se));
     return SITRK_OK;
 }
 
@@ -1560,26 +1510,18 @@ SITRK_API int sitrk_seed_init(sitrk_t *h, int64_t nP, const double *latlon, cons
     NEED(latlon && yx && latT && lonT && sic && jiT_out && keep, "sitrk_seed_init: null array");
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->Nj * h->Ni;
-    const size_t b_pt = align256((size_t)nP * sizeof(pt)), b_g = align256(n * 8), b_ji = align256((size_t)nP * 8),
-                 b_k = align256((size_t)nP);
-    int rc = ensure_scratch(h, 2 * b_pt + 4 * b_g + b_ji + 2 * b_k);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    ll *d_ll = (ll *)s;                 s += b_pt;
-    pt *d_yx = (pt *)s;                 s += b_pt;
-    double *d_lat = (double *)s;        s += b_g;
-    double *d_lon = (double *)s;        s += b_g;
-    double *d_res = (double *)s;        s += b_g;
-    double *d_sic = (double *)s;        s += b_g;
-    int32_t *d_ji = (int32_t *)s;       s += b_ji;
-    int8_t *d_keep = (int8_t *)s;       s += b_k;
-    int8_t *d_why = (int8_t *)s;
-    HIPCHK(hipMemcpyAsync(d_ll, latlon, (size_t)nP * sizeof(ll), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_yx, yx, (size_t)nP * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lat, latT, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lon, lonT, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (resolkm) HIPCHK(hipMemcpyAsync(d_res, resolkm, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_sic, sic, n * 8, hipMemcpyHostToDevice, h->stream));
+    ll *d_ll; pt *d_yx; double *d_lat, *d_lon, *d_res, *d_sic; int32_t *d_ji; int8_t *d_keep, *d_why;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_ll, nP); c.take(d_yx, nP);
+        c.take(d_lat, n); c.take(d_lon, n); c.take(d_res, n); c.take(d_sic, n);
+        c.take(d_ji, 2 * nP); c.take(d_keep, nP); c.take(d_why, nP);
+    }));
+    HIPCHK(upload(h, d_ll, latlon, nP));
+    HIPCHK(upload(h, d_yx, yx, nP));
+    HIPCHK(upload(h, d_lat, latT, n));
+    HIPCHK(upload(h, d_lon, lonT, n));
+    if (resolkm) HIPCHK(upload(h, d_res, resolkm, n));
+    HIPCHK(upload(h, d_sic, sic, n));
     // rFoundKM = 2.5 (tracking.py:5), max_itr = 10 (tracking.py:134)
     if (h->tune & TUNE_LOCATE_BRUTEFORCE) {
         hipLaunchKernelGGL(seed_init_bruteforce_kernel, dim3((unsigned)nP), dim3(kBlock), 0, h->stream, nP, h->Nj, h->Ni, d_ll, d_yx,
@@ -1587,22 +1529,14 @@ SITRK_API int sitrk_seed_init(sitrk_t *h, int64_t nP, const double *latlon, cons
         HIPCHK(hipGetLastError());
     } else {
         // exact branch-and-bound over bounding spheres of the mesh (sitrk_locate.h)
-        char *w = nullptr;
-        uint32_t *kb = nullptr;
-        double *db = nullptr;
-        rc = nearest_search(h, nP, d_ll, d_lat, d_lon, resolkm, 2.5, 10, &w, &kb, &db);
-        if (rc) return rc;
-        hipLaunchKernelGGL(seed_finish_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->Nj, h->Ni, kb, db, d_yx,
-                           resolkm ? d_res : nullptr, d_sic, h->tmask, h->geo, h->rmin_conc, 2.5, 10, d_ji, d_keep, d_why);
-        hipError_t le = hipGetLastError();
-        hipError_t se = hipStreamSynchronize(h->stream);
-        (void)hipFree(w);
-        if (le != hipSuccess) return fail(h, SITRK_EHIP, "seed search launch -> %s", hipGetErrorString(le));
-        if (se != hipSuccess) return fail(h, SITRK_EHIP, "seed search -> %s", hipGetErrorString(se));
+        RCCHK(nearest_search(h, nP, d_ll, d_lat, d_lon, resolkm, 2.5, 10, "seed search", "seed search", [&](const uint32_t *kb, const double *db) {
+            hipLaunchKernelGGL(seed_finish_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->Nj, h->Ni, kb, db, d_yx,
+                               resolkm ? d_res : nullptr, d_sic, h->tmask, h->geo, h->rmin_conc, 2.5, 10, d_ji, d_keep, d_why);
+        }));
     }
-    HIPCHK(hipMemcpyAsync(jiT_out, d_ji, (size_t)nP * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(keep, d_keep, (size_t)nP, hipMemcpyDeviceToHost, h->stream));
-    if (why) HIPCHK(hipMemcpyAsync(why, d_why, (size_t)nP, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, jiT_out, d_ji, 2 * nP));
+    HIPCHK(download(h, keep, d_keep, nP));
+    if (why) HIPCHK(download(h, why, d_why, nP));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1618,35 +1552,23 @@ SITRK_API int sitrk_nearest_point(sitrk_t *h, int64_t nP, const double *latlon, 
     NEED(latlon && latT && lonT && ji_out, "sitrk_nearest_point: null array");
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->Nj * h->Ni;
-    const size_t b_pt = align256((size_t)nP * sizeof(ll)), b_g = align256(n * 8), b_ji = align256((size_t)nP * 8),
-                 b_d = align256((size_t)nP * 8);
-    int rc = ensure_scratch(h, b_pt + 3 * b_g + b_ji + b_d);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    ll *d_ll = (ll *)s;                 s += b_pt;
-    double *d_lat = (double *)s;        s += b_g;
-    double *d_lon = (double *)s;        s += b_g;
-    double *d_res = (double *)s;        s += b_g;
-    int32_t *d_ji = (int32_t *)s;       s += b_ji;
-    double *d_dm = (double *)s;
-    HIPCHK(hipMemcpyAsync(d_ll, latlon, (size_t)nP * sizeof(ll), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lat, latT, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lon, lonT, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (resolkm) HIPCHK(hipMemcpyAsync(d_res, resolkm, n * 8, hipMemcpyHostToDevice, h->stream));
-    char *w = nullptr;
-    uint32_t *kb = nullptr;
-    double *db = nullptr;
-    rc = nearest_search(h, nP, d_ll, d_lat, d_lon, resolkm, rd_found_km, max_itr, &w, &kb, &db);
-    if (rc) return rc;
-    hipLaunchKernelGGL(nearest_finish_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->Ni, kb, db,
-                       resolkm ? d_res : nullptr, rd_found_km, max_itr, d_ji, d_dm);
-    hipError_t le = hipGetLastError();
-    hipError_t se = hipStreamSynchronize(h->stream);
-    (void)hipFree(w);
-    if (le != hipSuccess) return fail(h, SITRK_EHIP, "nearest-point launch -> %s", hipGetErrorString(le));
-    if (se != hipSuccess) return fail(h, SITRK_EHIP, "nearest-point search -> %s", hipGetErrorString(se));
-    HIPCHK(hipMemcpyAsync(ji_out, d_ji, (size_t)nP * 8, hipMemcpyDeviceToHost, h->stream));
-    if (dmin_out) HIPCHK(hipMemcpyAsync(dmin_out, d_dm, (size_t)nP * 8, hipMemcpyDeviceToHost, h->stream));
+    ll *d_ll; double *d_lat, *d_lon, *d_res, *d_dm; int32_t *d_ji;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_ll, nP);
+        c.take(d_lat, n); c.take(d_lon, n); c.take(d_res, n);
+        c.take(d_ji, 2 * nP); c.take(d_dm, nP);
+    }));
+    HIPCHK(upload(h, d_ll, latlon, nP));
+    HIPCHK(upload(h, d_lat, latT, n));
+    HIPCHK(upload(h, d_lon, lonT, n));
+    if (resolkm) HIPCHK(upload(h, d_res, resolkm, n));
+    RCCHK(nearest_search(h, nP, d_ll, d_lat, d_lon, resolkm, rd_found_km, max_itr, "nearest-point", "nearest-point search",
+                         [&](const uint32_t *kb, const double *db) {
+        hipLaunchKernelGGL(nearest_finish_kernel, dim3(nblocks(nP)), dim3(kBlock), 0, h->stream, nP, h->Ni, kb, db,
+                           resolkm ? d_res : nullptr, rd_found_km, max_itr, d_ji, d_dm);
+    }));
+    HIPCHK(download(h, ji_out, d_ji, 2 * nP));
+    if (dmin_out) HIPCHK(download(h, dmin_out, d_dm, nP));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1659,16 +1581,13 @@ SITRK_API int sitrk_eval_haversine(sitrk_t *h, int64_t n, const double *plat, co
     if (n == 0) return SITRK_OK;
     NEED(plat && plon && xlat && xlon && dist, "sitrk_eval_haversine: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b = align256((size_t)n * 8);
-    int rc = ensure_scratch(h, 5 * b);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
+    double *d[5] = {nullptr};           // plat, plon, xlat, xlon, dist
+    RCCHK(carve_scratch(h, [&](Carver &c) { for (double *&p : d) c.take(p, n); }));
     const double *src[4] = {plat, plon, xlat, xlon};
-    for (int a = 0; a < 4; a++) HIPCHK(hipMemcpyAsync(s + a * b, src[a], (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(eval_haversine_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, (const double *)s, (const double *)(s + b),
-                       (const double *)(s + 2 * b), (const double *)(s + 3 * b), (double *)(s + 4 * b));
+    for (int a = 0; a < 4; a++) HIPCHK(upload(h, d[a], src[a], n));
+    hipLaunchKernelGGL(eval_haversine_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, d[0], d[1], d[2], d[3], d[4]);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dist, s + 4 * b, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, dist, d[4], n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1681,16 +1600,13 @@ SITRK_API int sitrk_eval_inside(sitrk_t *h, int64_t n, const double *pts, const 
     if (n == 0) return SITRK_OK;
     NEED(pts && quads && inside, "sitrk_eval_inside: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_p = align256((size_t)n * sizeof(pt)), b_q = align256((size_t)n * 4 * sizeof(pt)), b_o = align256((size_t)n);
-    int rc = ensure_scratch(h, b_p + b_q + b_o);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(s, pts, (size_t)n * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s + b_p, quads, (size_t)n * 4 * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(eval_inside_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, (const pt *)s, (const pt *)(s + b_p),
-                       (int8_t *)(s + b_p + b_q));
+    pt *d_p, *d_q; int8_t *d_o;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_p, n); c.take(d_q, 4 * n); c.take(d_o, n); }));
+    HIPCHK(upload(h, d_p, pts, n));
+    HIPCHK(upload(h, d_q, quads, 4 * n));
+    hipLaunchKernelGGL(eval_inside_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, d_p, d_q, d_o);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(inside, s + b_p + b_q, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, inside, d_o, n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1702,16 +1618,13 @@ SITRK_API int sitrk_eval_euler(sitrk_t *h, int64_t n, const double *r, const dou
     if (n == 0) return SITRK_OK;
     NEED(r && vel && out, "sitrk_eval_euler: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b = align256((size_t)n * sizeof(double));
-    int rc = ensure_scratch(h, 3 * b);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(s, r, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s + b, vel, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(eval_euler_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, (const double *)s, (const double *)(s + b),
-                       rdt, f32_class_for(rdt), (double *)(s + 2 * b));
+    double *d_r, *d_v, *d_o;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_r, n); c.take(d_v, n); c.take(d_o, n); }));
+    HIPCHK(upload(h, d_r, r, n));
+    HIPCHK(upload(h, d_v, vel, n));
+    hipLaunchKernelGGL(eval_euler_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, d_r, d_v, rdt, f32_class_for(rdt), d_o);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, s + 2 * b, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, out, d_o, n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1723,16 +1636,13 @@ SITRK_API int sitrk_eval_intersect(sitrk_t *h, int64_t n, const double *segs, in
     if (n == 0) return SITRK_OK;
     NEED(segs && intersect, "sitrk_eval_intersect: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_s = align256((size_t)n * 4 * sizeof(pt)), b_o = align256((size_t)n);
-    int rc = ensure_scratch(h, b_s + 2 * b_o);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(s, segs, (size_t)n * 4 * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(eval_intersect_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, (const pt *)s, (int8_t *)(s + b_s),
-                       ccw_abc ? (int8_t *)(s + b_s + b_o) : nullptr);
+    pt *d_s; int8_t *d_x, *d_c;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_s, 4 * n); c.take(d_x, n); c.take(d_c, n); }));
+    HIPCHK(upload(h, d_s, segs, 4 * n));
+    hipLaunchKernelGGL(eval_intersect_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, d_s, d_x, ccw_abc ? d_c : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(intersect, s + b_s, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (ccw_abc) HIPCHK(hipMemcpyAsync(ccw_abc, s + b_s + b_o, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, intersect, d_x, n));
+    if (ccw_abc) HIPCHK(download(h, ccw_abc, d_c, n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1750,22 +1660,21 @@ SITRK_API int sitrk_eval_crossing(sitrk_t *h, int64_t n, const double *P1, const
             return fail(h, SITRK_EINDEX, "sitrk_eval_crossing: host cell (%d,%d) outside 1..%d x 1..%d", jiT[2 * p], jiT[2 * p + 1],
                         h->Nj - 2, h->Ni - 2);
     HIPCHK(hipSetDevice(h->device));
-    const size_t b_p = align256((size_t)n * sizeof(pt)), b_j = align256((size_t)n * 8);
-    int rc = ensure_scratch(h, 2 * b_p + 3 * b_j);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    pt *d1 = (pt *)s, *d2 = (pt *)(s + b_p);
-    int32_t *dj = (int32_t *)(s + 2 * b_p), *dn = (int32_t *)(s + 2 * b_p + b_j), *dc = (int32_t *)(s + 2 * b_p + 2 * b_j);
-    HIPCHK(hipMemcpyAsync(d1, P1, (size_t)n * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d2, P2, (size_t)n * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dj, jiT, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    pt *d1, *d2; int32_t *dj, *dn, *dc;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d1, n); c.take(d2, n);
+        c.take(dj, 2 * n); c.take(dn, 2 * n); c.take(dc, 2 * n);
+    }));
+    HIPCHK(upload(h, d1, P1, n));
+    HIPCHK(upload(h, d2, P2, n));
+    HIPCHK(upload(h, dj, jiT, 2 * n));
     CrossTab tab;
     make_cross_tab(h->Ni, tab);
     hipLaunchKernelGGL(eval_crossing_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, h->Nj, h->Ni, h->geo, d1, d2, dj, dn,
                        codes ? dc : nullptr, tab);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(jiT_new, dn, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (codes) HIPCHK(hipMemcpyAsync(codes, dc, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, jiT_new, dn, 2 * n));
+    if (codes) HIPCHK(download(h, codes, dc, 2 * n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1777,15 +1686,12 @@ SITRK_API int sitrk_survive_mask(sitrk_t *h, const double *sic, int8_t *mask)
     NEED(sic && mask, "sitrk_survive_mask: null array");
     HIPCHK(hipSetDevice(h->device));
     const size_t cells = (size_t)h->Nj * h->Ni;
-    const size_t b_s = align256(cells * 8), b_m = align256(cells);
-    int rc = ensure_scratch(h, b_s + 2 * b_m);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(s, sic, cells * 8, hipMemcpyHostToDevice, h->stream));
+    double *d_sic; int8_t *d_kill; uint8_t *d_kill9;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_sic, cells); c.take(d_kill, cells); c.take(d_kill9, cells); }));
+    HIPCHK(upload(h, d_sic, sic, cells));
     // the very kernel that derives a resident record's bytes (the packed neighbourhoods go to scratch and are dropped)
-    rc = launch_survive(h, true, s, (int8_t *)(s + b_s), (uint8_t *)(s + b_s + b_m), 0, h->Nj, 0, h->Ni);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(mask, s + b_s, cells, hipMemcpyDeviceToHost, h->stream));
+    RCCHK(launch_survive(h, true, d_sic, d_kill, d_kill9, 0, h->Nj, 0, h->Ni));
+    HIPCHK(download(h, mask, d_kill, cells));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1798,16 +1704,15 @@ static int project(sitrk_ctx *h, int64_t n, const double *in, double lat0, doubl
     if (n == 0) return SITRK_OK;
     NEED(in && out, "projection: null array");
     HIPCHK(hipSetDevice(h->device));
-    const size_t b = align256((size_t)n * 16);
-    int rc = ensure_scratch(h, 2 * b);
-    if (rc) return rc;
-    char *s = (char *)h->scratch;
-    HIPCHK(hipMemcpyAsync(s, in, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+    static_assert(sizeof(pt) == sizeof(ll), "one staging layout serves both directions");
+    pt *d_in, *d_out;
+    RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_in, n); c.take(d_out, n); }));
+    HIPCHK(upload(h, d_in, in, n));
     ProjParams pp = make_proj(lat0, lon0);
-    if (inverse) hipLaunchKernelGGL(cart2geo_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, pp, (const pt *)s, (ll *)(s + b));
-    else hipLaunchKernelGGL(geo2cart_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, pp, (const ll *)s, (pt *)(s + b));
+    if (inverse) hipLaunchKernelGGL(cart2geo_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, pp, d_in, (ll *)d_out);
+    else hipLaunchKernelGGL(geo2cart_kernel, dim3(nblocks(n)), dim3(kBlock), 0, h->stream, n, pp, (const ll *)d_in, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, s + b, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, out, d_out, n));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
@@ -1841,31 +1746,24 @@ SITRK_API int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t
     s.with_f = latF ? 1 : 0;
     const size_t n = (size_t)Nj * Ni;
     const int64_t ns = (int64_t)s.Njs * s.Nis, nblk_t = (ns + kSeedBlock - 1) / kSeedBlock, nblk = 2 * nblk_t;
-    const size_t b_d = align256(n * 8), b_m = align256(n), b_c = align256((size_t)nblk * 4), b_o = align256((size_t)nblk * 8),
-                 b_out = align256((size_t)capacity * 16);
-    int rc = ensure_scratch(h, 5 * b_d + 2 * b_m + b_c + b_o + 256 + 2 * b_out);
-    if (rc) return rc;
-    char *w = (char *)h->scratch;
-    double *d_latT = (double *)w;           w += b_d;
-    double *d_lonT = (double *)w;           w += b_d;
-    double *d_sic = (double *)w;            w += b_d;
-    double *d_latF = (double *)w;           w += b_d;
-    double *d_lonF = (double *)w;           w += b_d;
-    int8_t *d_tm = (int8_t *)w;             w += b_m;
-    int8_t *d_rm = (int8_t *)w;             w += b_m;
-    unsigned *d_cnt = (unsigned *)w;        w += b_c;
-    int64_t *d_off = (int64_t *)w;          w += b_o;
-    int64_t *d_tot = (int64_t *)w;          w += 256;
-    ll *d_ll = (ll *)w;                     w += b_out;
-    pt *d_yx = (pt *)w;
-    HIPCHK(hipMemcpyAsync(d_latT, latT, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lonT, lonT, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_sic, sic, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_tm, tmask, n, hipMemcpyHostToDevice, h->stream));
-    if (rmask) HIPCHK(hipMemcpyAsync(d_rm, rmask, n, hipMemcpyHostToDevice, h->stream));
+    double *d_latT, *d_lonT, *d_sic, *d_latF, *d_lonF; int8_t *d_tm, *d_rm; unsigned *d_cnt; int64_t *d_off, *d_tot; ll *d_ll;
+    pt *d_yx;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_latT, n); c.take(d_lonT, n); c.take(d_sic, n);
+        c.take(d_latF, n); c.take(d_lonF, n);
+        c.take(d_tm, n); c.take(d_rm, n);
+        c.take(d_cnt, nblk); c.take(d_off, nblk);
+        c.take(d_tot, 2);                      // (one 256-byte block)
+        c.take(d_ll, capacity); c.take(d_yx, capacity);
+    }));
+    HIPCHK(upload(h, d_latT, latT, n));
+    HIPCHK(upload(h, d_lonT, lonT, n));
+    HIPCHK(upload(h, d_sic, sic, n));
+    HIPCHK(upload(h, d_tm, tmask, n));
+    if (rmask) HIPCHK(upload(h, d_rm, rmask, n));
     if (latF) {
-        HIPCHK(hipMemcpyAsync(d_latF, latF, n * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d_lonF, lonF, n * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(upload(h, d_latF, latF, n));
+        HIPCHK(upload(h, d_lonF, lonF, n));
     }
     s.tmask = d_tm; s.rmask = rmask ? d_rm : nullptr;
     s.latT = d_latT; s.lonT = d_lonT; s.sic = d_sic; s.latF = d_latF; s.lonF = d_lonF;
@@ -1874,7 +1772,7 @@ SITRK_API int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t
     hipLaunchKernelGGL(seed_scan_kernel, dim3(1), dim3(kSeedBlock), 0, h->stream, nblk, nblk_t, d_cnt, d_off, d_tot);
     HIPCHK(hipGetLastError());
     int64_t tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, tot, d_tot, 2));
     HIPCHK(hipStreamSynchronize(h->stream));
     *nT = tot[0]; *nF = tot[1];
     if (capacity == 0) return SITRK_OK;                 // counting call
@@ -1884,315 +1782,9 @@ SITRK_API int sitrk_nemo_seed(sitrk_t *h, int Nj, int Ni, int khss, const int8_t
                        d_ll, yx ? d_yx : nullptr);
     HIPCHK(hipGetLastError());
     const size_t nout = (size_t)(tot[0] + tot[1]);
-    HIPCHK(hipMemcpyAsync(latlon, d_ll, nout * 16, hipMemcpyDeviceToHost, h->stream));
-    if (yx) HIPCHK(hipMemcpyAsync(yx, d_yx, nout * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(download(h, latlon, d_ll, nout));
+    if (yx) HIPCHK(download(h, yx, d_yx, nout));
     HIPCHK(hipStreamSynchronize(h->stream));
-    return SITRK_OK;
-}
-
-// --------------------------------------------------------------------------- seed-cloud coarsening
-// Kernels in sitrk_subsample.hip (algorithm and rules there).  Everything lives in h->scratch, which the stepping never reads.
-SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, double rd_km, int8_t *keep, int64_t *nkeep,
-                                    int32_t *launches)
-{
-    NEED(h, "null handle");
-    NEED(n >= 0 && n < ((int64_t)1 << 31) - 1, "sitrk_subsample_cloud: n must be in 0..2^31-2");
-    NEED(nkeep, "sitrk_subsample_cloud: null nkeep");
-    NEED(n == 0 || (yx && keep), "sitrk_subsample_cloud: null array");
-    if (!std::isfinite(rd_km) || !(rd_km > 0.0))
-        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: rd_km must be finite and > 0 (got %g)", rd_km);
-    *nkeep = 0;
-    if (launches) *launches = 0;
-    if (n == 0) return SITRK_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t un = (size_t)n;
-    const size_t b_pt = align256(un * sizeof(pt)), b_4 = align256(un * 4), b_1 = align256(un);
-    // the cell grid is known after the bounding box; size the scratch for the largest grid allowed (cells <= n + 1024)
-    const int64_t max_cells = n + 1024;
-    const size_t b_c = align256((size_t)max_cells * 4);
-    size_t b_sort = 0;
-    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, h->stream));
-    b_sort = align256(b_sort);
-    const int ppt = h->subsample_block / 256;
-    const int64_t nwg = (n + h->subsample_block - 1) / h->subsample_block;
-    const size_t b_red = 256, b_done = align256((size_t)nwg);
-    int rc = ensure_scratch(h, 2 * b_pt + 5 * b_4 + 3 * b_1 + 2 * b_c + b_sort + b_red + b_done);
-    if (rc) return rc;
-    char *w = (char *)h->scratch;
-    pt *d_yx = (pt *)w;                             w += b_pt;
-    pt *d_yxs = (pt *)w;                            w += b_pt;
-    uint32_t *k0 = (uint32_t *)w;                   w += b_4;
-    uint32_t *k1 = (uint32_t *)w;                   w += b_4;
-    int32_t *v0 = (int32_t *)w;                     w += b_4;
-    int32_t *perm = (int32_t *)w;                   w += b_4;
-    int32_t *cur_q = (int32_t *)w;                  w += b_4;
-    uint8_t *state = (uint8_t *)w;                  w += b_1;
-    uint8_t *cur_k = (uint8_t *)w;                  w += b_1;
-    int8_t *d_keep = (int8_t *)w;                   w += b_1;
-    int32_t *cstart = (int32_t *)w;                 w += b_c;
-    int32_t *cend = (int32_t *)w;                   w += b_c;
-    void *sort_tmp = w;                             w += b_sort;
-    unsigned long long *red = (unsigned long long *)w; w += b_red;     // [0..4] bbox + first non-finite, [5] undecided, [6] kept
-    uint8_t *done = (uint8_t *)w;
-
-    HIPCHK(hipMemcpyAsync(d_yx, yx, un * sizeof(pt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(subsample_bbox(n, d_yx, red, h->stream));
-    unsigned long long bb[5];
-    HIPCHK(hipMemcpyAsync(bb, red, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (bb[4] != ~0ull)
-        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: non-finite coordinate at index %llu", bb[4]);
-    SubGrid g;
-    g.ymin = subsample_key_to_double(bb[0]); g.xmin = subsample_key_to_double(bb[1]);
-    const double ymax = subsample_key_to_double(bb[2]), xmax = subsample_key_to_double(bb[3]);
-    // side h >= rd, padded so that the rounding of a cell coordinate ((v - v0) * inv_h, <= 2^20) can never put a pair with
-    // d2 < r2 two cells apart; doubled while the grid exceeds n + 1024 cells or 2^20 cells a side (a coarser grid is only slower)
-    double side = rd_km * (1.0 + 1.0 / 1024.0);
-    int64_t ny = 1, nx = 1;
-    for (int it = 0; it < 2100; it++) {
-        g.inv_h = 1.0 / side;
-        const double ty = (ymax - g.ymin) * g.inv_h, tx = (xmax - g.xmin) * g.inv_h;
-        if (ty < 1048576.0 && tx < 1048576.0) {
-            ny = (int64_t)std::floor(ty) + 1; nx = (int64_t)std::floor(tx) + 1;
-            if (ny * nx <= max_cells) break;
-        }
-        side *= 2.0;
-    }
-    if (ny * nx > max_cells || !(g.inv_h > 0.0)) return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: no cell grid fits the cloud's extent");
-    g.ny = (int)ny; g.nx = (int)nx;
-    const int64_t ncells = ny * nx;
-    unsigned end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)ncells) end_bit++;
-
-    // bin: key = cell, stable radix sort (index order inside a cell), sorted coordinates, cell ranges
-    HIPCHK(subsample_bin_keys(g, n, d_yx, k0, v0, h->stream));
-    size_t tb = b_sort;
-    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, h->stream));
-    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * 4, h->stream));
-    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * 4, h->stream));
-    HIPCHK(subsample_bin_gather(n, d_yx, k1, perm, d_yxs, cstart, cend, h->stream));
-    HIPCHK(hipMemsetAsync(state, 0, un, h->stream));
-    HIPCHK(hipMemsetAsync(cur_k, 0, un, h->stream));
-    HIPCHK(hipMemsetAsync(cur_q, 0xff, un * 4, h->stream));
-    HIPCHK(hipMemsetAsync(done, 0, (size_t)nwg, h->stream));
-
-    SubResolveArgs a;
-    a.g = g; a.n = n; a.r2 = rd_km * rd_km; a.ppt = ppt;
-    a.yx = d_yxs; a.perm = perm; a.cstart = cstart; a.cend = cend;
-    a.state = state; a.cur_q = cur_q; a.cur_k = cur_k; a.done = done;
-    // launches in batches; the last launch of a batch counts what it leaves undecided (an over-count at worst, and always
-    // below the previous batch's count, since every launch decides the lowest undecided point): stop at 0, give up if it stalls
-    unsigned long long prev = (unsigned long long)n + 1, und = 0;
-    int64_t nl = 0;
-    int batch = 4;
-    for (;;) {
-        for (int b = 0; b < batch; b++) {
-            a.undecided = nullptr;
-            if (b == batch - 1) {
-                HIPCHK(hipMemsetAsync(red + 5, 0, sizeof(unsigned long long), h->stream));
-                a.undecided = red + 5;
-            }
-            HIPCHK(subsample_resolve(a, h->stream));
-        }
-        nl += batch;
-        HIPCHK(hipMemcpyAsync(&und, red + 5, sizeof(und), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (und == 0) break;
-        if (und >= prev || nl > n + 64)
-            return fail(h, SITRK_EHIP, "sitrk_subsample_cloud: undecided count stalled at %llu after %lld launches", und, (long long)nl);
-        prev = und;
-        batch = std::min(2 * batch, 64);
-    }
-    HIPCHK(hipMemsetAsync(red + 6, 0, sizeof(unsigned long long), h->stream));
-    HIPCHK(subsample_emit(n, perm, state, d_keep, red + 6, h->stream));
-    unsigned long long nk = 0;
-    HIPCHK(hipMemcpyAsync(keep, d_keep, un, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&nk, red + 6, sizeof(nk), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *nkeep = (int64_t)nk;
-    if (launches) *launches = (int32_t)std::min<int64_t>(nl, INT32_MAX);
-    return SITRK_OK;
-}
-
-// --------------------------------------------------------------------------- overlap cleaning of a tracked cloud
-// Kernels in sitrk_overlap.hip (algorithm there, bounds in DESIGN.md section 3.6).  Everything lives in h->scratch, which the
-// stepping never reads.  Stage 1 leaves, in input order, nn (nearest other valid buoy with Haversine < rd_km, else -1) and dmin.
-struct OverlapScratch {
-    int32_t *nn = nullptr, *flag = nullptr, *pos = nullptr, *cidx = nullptr, *cnn = nullptr;
-    double *dmin = nullptr;
-    void *scan_tmp = nullptr;
-    size_t scan_bytes = 0;
-    unsigned long long *red = nullptr;
-};
-
-static int overlap_stage1(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, const int8_t *valid,
-                          double rd_km, OverlapScratch &o)
-{
-    HIPCHK(hipSetDevice(h->device));
-    const size_t un = (size_t)n;
-    const size_t b_8 = align256(un * 8), b_4 = align256(un * 4), b_1 = align256(un);
-    const size_t b_v3 = align256(un * sizeof(V3)), b_ll = align256(un * sizeof(ll));
-    const int64_t max_cells = n + 1024;                 // the grid is known after the bounding box: size for the largest allowed
-    const size_t b_c = align256((size_t)max_cells * 4);
-    size_t b_sort = 0, b_scan = 0;
-    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, h->stream));
-    HIPCHK(overlap_compact(nullptr, &b_scan, n, nullptr, nullptr, nullptr, nullptr, nullptr, h->stream));
-    b_sort = align256(b_sort);
-    b_scan = align256(b_scan);
-    const size_t b_red = 256;
-    int rc = ensure_scratch(h, 3 * b_8 + b_1 + 9 * b_4 + b_v3 + b_ll + 2 * b_c + b_sort + b_scan + b_red);
-    if (rc) return rc;
-    char *w = (char *)h->scratch;
-    double *d_lat = (double *)w;                    w += b_8;
-    double *d_lon = (double *)w;                    w += b_8;
-    o.dmin = (double *)w;                           w += b_8;
-    int8_t *d_valid = (int8_t *)w;                  w += b_1;
-    uint32_t *k0 = (uint32_t *)w;                   w += b_4;
-    uint32_t *k1 = (uint32_t *)w;                   w += b_4;
-    int32_t *v0 = (int32_t *)w;                     w += b_4;
-    int32_t *perm = (int32_t *)w;                   w += b_4;
-    o.nn = (int32_t *)w;                            w += b_4;
-    o.flag = (int32_t *)w;                          w += b_4;
-    o.pos = (int32_t *)w;                           w += b_4;
-    o.cidx = (int32_t *)w;                          w += b_4;
-    o.cnn = (int32_t *)w;                           w += b_4;
-    V3 *uv_s = (V3 *)w;                             w += b_v3;
-    ll *ll_s = (ll *)w;                             w += b_ll;
-    int32_t *cstart = (int32_t *)w;                 w += b_c;
-    int32_t *cend = (int32_t *)w;                   w += b_c;
-    void *sort_tmp = w;                             w += b_sort;
-    o.scan_tmp = w;                                 w += b_scan;
-    o.scan_bytes = b_scan;
-    o.red = (unsigned long long *)w;                // [0..5] bbox keys, [6] first non-finite valid index, [7] valid count
-
-    HIPCHK(hipMemcpyAsync(d_lat, lat, un * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_lon, lon, un * 8, hipMemcpyHostToDevice, h->stream));
-    if (valid) HIPCHK(hipMemcpyAsync(d_valid, valid, un, hipMemcpyHostToDevice, h->stream));
-    const int8_t *dv = valid ? d_valid : nullptr;
-    HIPCHK(overlap_bbox(n, d_lat, d_lon, dv, o.red, h->stream));
-    unsigned long long bb[8];
-    HIPCHK(hipMemcpyAsync(bb, o.red, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (bb[6] != ~0ull) return fail(h, SITRK_EINVAL, "%s: non-finite coordinate of valid buoy at index %llu", fn, bb[6]);
-    OvGrid g;
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    if (bb[7]) {
-        for (int c = 0; c < 3; c++) { lo[c] = subsample_key_to_double(bb[c]); hi[c] = subsample_key_to_double(bb[3 + c]); }
-    }
-    g.x0 = lo[0]; g.y0 = lo[1]; g.z0 = lo[2];
-    // chord of rd (rd <= 9999 km: half-angle <= 0.79 rad, sin increasing); side h >= that chord, padded so that neither the
-    // rounding of the Haversine (~1e-15 relative) nor that of the unit vectors (~1e-16) nor that of a cell coordinate
-    // ((v - v0) * inv_h, < 2^20) can put a pair with Haversine < rd two cells apart; doubled while the grid exceeds n + 1024
-    // cells or 2^20 cells a side (a coarser grid is only slower)
-    const double chord = 2.0 * std::sin(rd_km / (2.0 * 6360.0));
-    const double cut = chord * (1.0 + 1.0 / 1024.0) + 1e-12;
-    double side = cut;
-    int64_t ncell[3] = {1, 1, 1};
-    bool ok = false;
-    for (int it = 0; it < 2100 && !ok; it++) {
-        g.inv_h = 1.0 / side;
-        ok = true;
-        for (int c = 0; c < 3 && ok; c++) {
-            const double t = (hi[c] - lo[c]) * g.inv_h;
-            if (!(t < 1048576.0)) ok = false;
-            else ncell[c] = (int64_t)std::floor(t) + 1;
-        }
-        if (ok && ncell[0] * ncell[1] * ncell[2] > max_cells) ok = false;
-        if (!ok) side *= 2.0;
-    }
-    if (!ok || !(g.inv_h > 0.0)) return fail(h, SITRK_EINVAL, "%s: no cell grid fits the cloud's extent", fn);
-    g.nx = (int)ncell[0]; g.ny = (int)ncell[1]; g.nz = (int)ncell[2];
-    const int64_t ncells = ncell[0] * ncell[1] * ncell[2];
-    g.ncells = (uint32_t)ncells;
-    unsigned end_bit = 1;                               // keys 0..ncells (ncells: invalid buoys)
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)ncells) end_bit++;
-
-    HIPCHK(overlap_bin_keys(g, n, d_lat, d_lon, dv, k0, v0, h->stream));
-    size_t tb = b_sort;
-    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, h->stream));
-    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * 4, h->stream));
-    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * 4, h->stream));
-    HIPCHK(overlap_bin_gather(g, n, d_lat, d_lon, k1, perm, uv_s, ll_s, cstart, cend, h->stream));
-    HIPCHK(overlap_nearest(g, n, rd_km, cut * cut, k1, perm, uv_s, ll_s, cstart, cend, o.nn, o.dmin, h->stream));
-    return SITRK_OK;
-}
-
-static int overlap_check(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, double rd_km)
-{
-    NEED(h, "null handle");
-    if (!(n >= 0 && n < ((int64_t)1 << 31) - 1)) return fail(h, SITRK_EINVAL, "%s: n must be in 0..2^31-2", fn);
-    if (n > 0 && !(lat && lon)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
-    if (!std::isfinite(rd_km) || !(rd_km > 0.0) || rd_km > 9999.0)
-        return fail(h, SITRK_EINVAL, "%s: rd_km must be finite and in (0, 9999] (got %g)", fn, rd_km);
-    return SITRK_OK;
-}
-
-SITRK_API int sitrk_nearest_buoy(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid, double rd_km,
-                                 int32_t *nn, double *dmin)
-{
-    const char *fn = "sitrk_nearest_buoy";
-    int rc = overlap_check(h, fn, n, lat, lon, rd_km);
-    if (rc) return rc;
-    if (n > 0 && !(nn && dmin)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
-    if (n == 0) return SITRK_OK;
-    OverlapScratch o;
-    rc = overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(nn, o.nn, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(dmin, o.dmin, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return SITRK_OK;
-}
-
-SITRK_API int sitrk_cancel_too_close(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid,
-                                     const int32_t *nrec_all, const int32_t *nrec_before, double rd_km, int8_t *keep, int64_t *nkeep,
-                                     int64_t *nclose)
-{
-    const char *fn = "sitrk_cancel_too_close";
-    int rc = overlap_check(h, fn, n, lat, lon, rd_km);
-    if (rc) return rc;
-    if (!nkeep) return fail(h, SITRK_EINVAL, "%s: null nkeep", fn);
-    if (n > 0 && !(nrec_all && nrec_before && keep)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
-    *nkeep = 0;
-    if (nclose) *nclose = 0;
-    if (n == 0) return SITRK_OK;
-    OverlapScratch o;
-    rc = overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o);
-    if (rc) return rc;
-    // stage 2: the close set (dmin < rd) in index order, neighbours as positions in it
-    size_t tb = o.scan_bytes;
-    HIPCHK(overlap_compact(o.scan_tmp, &tb, n, o.nn, o.flag, o.pos, o.cidx, o.cnn, h->stream));
-    int32_t last[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&last[0], o.pos + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&last[1], o.flag + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const int64_t m = (int64_t)last[0] + last[1];
-    std::vector<int32_t> cidx((size_t)m), cnn((size_t)m);
-    if (m) {
-        HIPCHK(hipMemcpyAsync(cidx.data(), o.cidx, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(cnn.data(), o.cnn, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    // stage 3: the reference's scan (util.py:536-556) over the close set in index order; a buoy dropped at krec loses its
-    // records >= krec (zmsk[krec:,j2c] = 0), so its count becomes nrec_before; on equal counts the neighbour goes
-    std::vector<uint8_t> dead((size_t)m, 0);
-    for (int64_t p = 0; p < m; p++) {
-        if (dead[p]) continue;
-        const int32_t q = cnn[p];
-        if (q < 0 || q >= m) return fail(h, SITRK_EHIP, "%s: nearest neighbour of buoy %d outside the close set", fn, cidx[p]);
-        const int32_t i = cidx[p], k = cidx[q];
-        const int64_t ci = nrec_all[i], ck = dead[q] ? nrec_before[k] : nrec_all[k];
-        dead[ci < ck ? p : q] = 1;
-    }
-    int64_t nk = 0;
-    for (int64_t i = 0; i < n; i++) {
-        keep[i] = (valid == nullptr || valid[i] != 0) ? 1 : 0;
-    }
-    for (int64_t p = 0; p < m; p++)
-        if (dead[p]) keep[cidx[p]] = 0;
-    for (int64_t i = 0; i < n; i++) nk += keep[i];
-    *nkeep = nk;
-    if (nclose) *nclose = m;
     return SITRK_OK;
 }
 

@@ -1,9 +1,10 @@
-// sitrk_internal.h -- context layout shared by the translation units of libsitrk.so
+// sitrk_internal.h -- context layout and host-side helpers shared by the translation units of libsitrk.so
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
 
+#include "../../include/sitrk.h"
 #include "sitrk_geom.h"
 
 namespace sitrk {
@@ -31,13 +32,10 @@ struct SubResolveArgs {
     uint8_t *done = nullptr;            // per workgroup: all its points decided
     unsigned long long *undecided = nullptr;   // optional: += points still undecided at each workgroup's exit
 };
-hipError_t subsample_bbox(int64_t n, const pt *yx, unsigned long long *red, hipStream_t s);
 double subsample_key_to_double(unsigned long long k);
-hipError_t subsample_bin_keys(const SubGrid &g, int64_t n, const pt *yx, uint32_t *key, int32_t *val, hipStream_t s);
-hipError_t subsample_bin_gather(int64_t n, const pt *yx, const uint32_t *key_sorted, const int32_t *perm, pt *yx_s, int32_t *cstart,
-                                int32_t *cend, hipStream_t s);
-hipError_t subsample_resolve(const SubResolveArgs &a, hipStream_t s);
-hipError_t subsample_emit(int64_t n, const int32_t *perm, const uint8_t *state, int8_t *keep, unsigned long long *nkeep, hipStream_t s);
+// cells of side `side` over the extents hi[c] - lo[c], c < dims: the side is doubled while the grid exceeds max_cells cells or 2^20
+// cells a side (a coarser grid is only slower).  false: no grid fits; else *inv_h = 1 / side and ncell[c] cells along c
+bool fit_cell_grid(int dims, const double *lo, const double *hi, double side, int64_t max_cells, double *inv_h, int64_t *ncell);
 
 // Overlap cleaning of a tracked cloud (sitrk_overlap.hip): cubic cells of side 1/inv_h over the unit vectors' bounding box,
 // nx x ny x nz of them from (x0, y0, z0); key = (cz * ny + cy) * nx + cx, ncells = nx * ny * nz (the key of an invalid buoy)
@@ -47,16 +45,6 @@ struct OvGrid {
     int nx = 1, ny = 1, nz = 1;
     uint32_t ncells = 1;
 };
-hipError_t overlap_bbox(int64_t n, const double *lat, const double *lon, const int8_t *valid, unsigned long long *red, hipStream_t s);
-hipError_t overlap_bin_keys(const OvGrid &g, int64_t n, const double *lat, const double *lon, const int8_t *valid, uint32_t *key,
-                            int32_t *val, hipStream_t s);
-hipError_t overlap_bin_gather(const OvGrid &g, int64_t n, const double *lat, const double *lon, const uint32_t *key_sorted,
-                              const int32_t *perm, V3 *uv_s, ll *ll_s, int32_t *cstart, int32_t *cend, hipStream_t s);
-hipError_t overlap_nearest(const OvGrid &g, int64_t n, double rd_km, double cut2, const uint32_t *key_sorted, const int32_t *perm,
-                           const V3 *uv_s, const ll *ll_s, const int32_t *cstart, const int32_t *cend, int32_t *nn, double *dmin,
-                           hipStream_t s);
-hipError_t overlap_compact(void *tmp, size_t *tmp_bytes, int64_t n, const int32_t *nn, int32_t *flag, int32_t *pos, int32_t *cidx,
-                           int32_t *cnn, hipStream_t s);
 
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
 // perm[s] = index of slot s in the caller's order.
@@ -185,3 +173,78 @@ struct sitrk_ctx {
     size_t scratch_bytes = 0;
     unsigned long long *counter = nullptr;   // device scalar for reductions
 };
+
+// --------------------------------------------------------------------------- host side shared by the translation units
+#define SITRK_API extern "C" __attribute__((visibility("default")))
+
+namespace sitrk {
+
+int fail(sitrk_ctx *h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+int ensure_scratch(sitrk_ctx *h, size_t bytes);
+
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace sitrk
+
+#define HIPCHK(call)                                                                          \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess) return sitrk::fail(h, SITRK_EHIP, "%s -> %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+#define NEED(cond, msg)                                \
+    do {                                               \
+        if (!(cond)) return sitrk::fail(h, SITRK_EINVAL, msg); \
+    } while (0)
+
+// a step of the library's own that returns a SITRK_* code
+#define RCCHK(call)              \
+    do {                         \
+        int rc_ = (call);        \
+        if (rc_) return rc_;     \
+    } while (0)
+
+namespace sitrk {
+
+// Scratch carver: hands out typed pieces of one allocation in order, each rounded up to 256 bytes.  A layout is a callable that
+// takes its pieces from the Carver it is given; carve_scratch() runs it twice -- over a null base, where only the offsets add up,
+// to size h->scratch, then over h->scratch to place the pointers -- so the total requested and the placement come out of the
+// same statements and cannot disagree.  Every entry point that stages arrays in h->scratch goes through it.
+struct Carver {
+    char *base = nullptr;
+    size_t off = 0;
+    template <typename T>
+    void take(T *&p, size_t count, size_t round = 256)
+    {
+        p = base ? (T *)(base + off) : nullptr;
+        off += (count * sizeof(T) + round - 1) / round * round;
+    }
+};
+
+template <typename Layout>
+static int carve_scratch(sitrk_ctx *h, Layout &&layout)
+{
+    Carver size;
+    layout(size);
+    RCCHK(ensure_scratch(h, size.off));
+    Carver place;
+    place.base = (char *)h->scratch;
+    layout(place);
+    return SITRK_OK;
+}
+
+// Copies on the compute stream between a host array and a typed device array of `count` elements: the device pointer's type
+// gives the element size (the host side of the ABI is plain double / int arrays, e.g. 2 doubles per pt)
+template <typename T>
+static hipError_t upload(sitrk_ctx *h, T *dst_dev, const void *src_host, size_t count)
+{
+    return hipMemcpyAsync(dst_dev, src_host, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
+}
+
+template <typename T>
+static hipError_t download(sitrk_ctx *h, void *dst_host, const T *src_dev, size_t count)
+{
+    return hipMemcpyAsync(dst_host, src_dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream);
+}
+
+}  // namespace sitrk

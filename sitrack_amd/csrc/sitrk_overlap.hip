@@ -2,7 +2,7 @@
 // util.CancelTooClose (sitrack/util.py:520-565).  Kept in its own translation unit so that the device code of sitrk.hip
 // stays as it is.
 //
-// Stage 1 (nearest other valid buoy within rd, per valid buoy), driven by sitrk.hip:
+// Stage 1 (nearest other valid buoy within rd, per valid buoy), driven by overlap_stage1() at the end of this file:
 //   1. unit_bbox_kernel  bounding box of the valid buoys' unit vectors and the first valid index with a non-finite coordinate
 //   2. bin_key_kernel    cubic cells of side h >= chord(rd) (padded) over that box; key = cell (invalid buoys: ncells, sorted
 //                        last); the rocPRIM radix sort of sitrk_sort.hip orders the buoys by cell
@@ -12,7 +12,9 @@
 //                        the smallest distance, lowest index on ties (the bound is in DESIGN.md section 3.6)
 // Stage 2 (close set, dmin < rd, in index order): flag_kernel, the rocPRIM exclusive scan below, close_scatter_kernel, with the
 // neighbour remapped to its position in the compact list.  Stage 3, the sequential scan of the reference, runs on the host.
+#include <algorithm>
 #include <cmath>
+#include <vector>
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
@@ -233,49 +235,164 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kOvThreads - 1) / kOvTh
 
 }  // namespace
 
-hipError_t overlap_bbox(int64_t n, const double *lat, const double *lon, const int8_t *valid, unsigned long long *red, hipStream_t s)
-{
-    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, s, red);
-    const unsigned g = nblk(n) < 2048u ? nblk(n) : 2048u;
-    hipLaunchKernelGGL(unit_bbox_kernel, dim3(g), dim3(kOvThreads), 0, s, n, lat, lon, valid, red);
-    return hipGetLastError();
-}
-
-hipError_t overlap_bin_keys(const OvGrid &g, int64_t n, const double *lat, const double *lon, const int8_t *valid, uint32_t *key,
-                            int32_t *val, hipStream_t s)
-{
-    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, lat, lon, valid, key, val);
-    return hipGetLastError();
-}
-
-hipError_t overlap_bin_gather(const OvGrid &g, int64_t n, const double *lat, const double *lon, const uint32_t *key_sorted,
-                              const int32_t *perm, V3 *uv_s, ll *ll_s, int32_t *cstart, int32_t *cend, hipStream_t s)
-{
-    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, lat, lon, key_sorted, perm, uv_s, ll_s, cstart,
-                       cend);
-    return hipGetLastError();
-}
-
-hipError_t overlap_nearest(const OvGrid &g, int64_t n, double rd_km, double cut2, const uint32_t *key_sorted, const int32_t *perm,
-                           const V3 *uv_s, const ll *ll_s, const int32_t *cstart, const int32_t *cend, int32_t *nn, double *dmin,
-                           hipStream_t s)
-{
-    hipLaunchKernelGGL(nearest_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, g, n, rd_km, cut2, key_sorted, perm, uv_s, ll_s, cstart,
-                       cend, nn, dmin);
-    return hipGetLastError();
-}
-
-// two-call protocol like sort_pairs_u32: tmp == nullptr -> only *tmp_bytes is written
-hipError_t overlap_compact(void *tmp, size_t *tmp_bytes, int64_t n, const int32_t *nn, int32_t *flag, int32_t *pos, int32_t *cidx,
-                           int32_t *cnn, hipStream_t s)
-{
-    if (tmp == nullptr)
-        return rocprim::exclusive_scan(tmp, *tmp_bytes, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s);
-    hipLaunchKernelGGL(flag_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, n, nn, flag);
-    hipError_t e = rocprim::exclusive_scan(tmp, *tmp_bytes, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(close_scatter_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, s, n, nn, pos, cidx, cnn);
-    return hipGetLastError();
-}
-
 }  // namespace sitrk
+
+using namespace sitrk;
+
+// Bounds in DESIGN.md section 3.6.  Everything lives in h->scratch, which the stepping never reads.  Stage 1 leaves, in input
+// order, nn (nearest other valid buoy with Haversine < rd_km, else -1) and dmin.
+struct OverlapScratch {
+    int32_t *nn = nullptr, *flag = nullptr, *pos = nullptr, *cidx = nullptr, *cnn = nullptr;
+    double *dmin = nullptr;
+    char *scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    unsigned long long *red = nullptr;
+};
+
+static int overlap_stage1(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, const int8_t *valid,
+                          double rd_km, OverlapScratch &o)
+{
+    HIPCHK(hipSetDevice(h->device));
+    const size_t un = (size_t)n;
+    const hipStream_t st = h->stream;
+    const int64_t max_cells = n + 1024;                 // the grid is known after the bounding box: size for the largest allowed
+    size_t b_sort = 0;
+    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, st));
+    HIPCHK(rocprim::exclusive_scan(nullptr, o.scan_bytes, o.flag, o.pos, 0, un, rocprim::plus<int32_t>(), st));
+    o.scan_bytes = align256(o.scan_bytes);
+    double *d_lat, *d_lon; int8_t *d_valid; uint32_t *k0, *k1; int32_t *v0, *perm, *cstart, *cend; V3 *uv_s; ll *ll_s;
+    char *sort_tmp;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_lat, un); c.take(d_lon, un); c.take(o.dmin, un);
+        c.take(d_valid, un);
+        c.take(k0, un); c.take(k1, un);
+        c.take(v0, un); c.take(perm, un);
+        c.take(o.nn, un); c.take(o.flag, un); c.take(o.pos, un);
+        c.take(o.cidx, un); c.take(o.cnn, un);
+        c.take(uv_s, un); c.take(ll_s, un);
+        c.take(cstart, max_cells); c.take(cend, max_cells);
+        c.take(sort_tmp, b_sort); c.take(o.scan_tmp, o.scan_bytes);
+        c.take(o.red, 8);          // [0..5] bbox keys, [6] first non-finite valid index, [7] valid count (one 256-byte block)
+    }));
+
+    HIPCHK(upload(h, d_lat, lat, un));
+    HIPCHK(upload(h, d_lon, lon, un));
+    if (valid) HIPCHK(upload(h, d_valid, valid, un));
+    const int8_t *dv = valid ? d_valid : nullptr;
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, st, o.red);
+    hipLaunchKernelGGL(unit_bbox_kernel, dim3(std::min(nblk(n), 2048u)), dim3(kOvThreads), 0, st, n, d_lat, d_lon, dv, o.red);
+    HIPCHK(hipGetLastError());
+    unsigned long long bb[8];
+    HIPCHK(download(h, bb, o.red, 8));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bb[6] != ~0ull) return fail(h, SITRK_EINVAL, "%s: non-finite coordinate of valid buoy at index %llu", fn, bb[6]);
+    OvGrid g;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    if (bb[7]) {
+        for (int c = 0; c < 3; c++) { lo[c] = subsample_key_to_double(bb[c]); hi[c] = subsample_key_to_double(bb[3 + c]); }
+    }
+    g.x0 = lo[0]; g.y0 = lo[1]; g.z0 = lo[2];
+    // chord of rd (rd <= 9999 km: half-angle <= 0.79 rad, sin increasing); side h >= that chord, padded so that neither the
+    // rounding of the Haversine (~1e-15 relative) nor that of the unit vectors (~1e-16) nor that of a cell coordinate
+    // ((v - v0) * inv_h, < 2^20) can put a pair with Haversine < rd two cells apart
+    const double chord = 2.0 * std::sin(rd_km / (2.0 * 6360.0));
+    const double cut = chord * (1.0 + 1.0 / 1024.0) + 1e-12;
+    int64_t ncell[3] = {1, 1, 1};
+    if (!fit_cell_grid(3, lo, hi, cut, max_cells, &g.inv_h, ncell)) return fail(h, SITRK_EINVAL, "%s: no cell grid fits the cloud's extent", fn);
+    g.nx = (int)ncell[0]; g.ny = (int)ncell[1]; g.nz = (int)ncell[2];
+    const int64_t ncells = ncell[0] * ncell[1] * ncell[2];
+    g.ncells = (uint32_t)ncells;
+    unsigned end_bit = 1;                               // keys 0..ncells (ncells: invalid buoys)
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)ncells) end_bit++;
+
+    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, st, g, n, d_lat, d_lon, dv, k0, v0);
+    HIPCHK(hipGetLastError());
+    size_t tb = align256(b_sort);
+    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, st));
+    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * sizeof(*cstart), st));
+    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * sizeof(*cend), st));
+    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, st, g, n, d_lat, d_lon, k1, perm, uv_s, ll_s, cstart, cend);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(nearest_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, st, g, n, rd_km, cut * cut, k1, perm, uv_s, ll_s, cstart,
+                       cend, o.nn, o.dmin);
+    HIPCHK(hipGetLastError());
+    return SITRK_OK;
+}
+
+static int overlap_check(sitrk_ctx *h, const char *fn, int64_t n, const double *lat, const double *lon, double rd_km)
+{
+    NEED(h, "null handle");
+    if (!(n >= 0 && n < ((int64_t)1 << 31) - 1)) return fail(h, SITRK_EINVAL, "%s: n must be in 0..2^31-2", fn);
+    if (n > 0 && !(lat && lon)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    if (!std::isfinite(rd_km) || !(rd_km > 0.0) || rd_km > 9999.0)
+        return fail(h, SITRK_EINVAL, "%s: rd_km must be finite and in (0, 9999] (got %g)", fn, rd_km);
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_nearest_buoy(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid, double rd_km,
+                                 int32_t *nn, double *dmin)
+{
+    const char *fn = "sitrk_nearest_buoy";
+    RCCHK(overlap_check(h, fn, n, lat, lon, rd_km));
+    if (n > 0 && !(nn && dmin)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    if (n == 0) return SITRK_OK;
+    OverlapScratch o;
+    RCCHK(overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o));
+    HIPCHK(download(h, nn, o.nn, n));
+    HIPCHK(download(h, dmin, o.dmin, n));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_cancel_too_close(sitrk_t *h, int64_t n, const double *lat, const double *lon, const int8_t *valid,
+                                     const int32_t *nrec_all, const int32_t *nrec_before, double rd_km, int8_t *keep, int64_t *nkeep,
+                                     int64_t *nclose)
+{
+    const char *fn = "sitrk_cancel_too_close";
+    RCCHK(overlap_check(h, fn, n, lat, lon, rd_km));
+    if (!nkeep) return fail(h, SITRK_EINVAL, "%s: null nkeep", fn);
+    if (n > 0 && !(nrec_all && nrec_before && keep)) return fail(h, SITRK_EINVAL, "%s: null array", fn);
+    *nkeep = 0;
+    if (nclose) *nclose = 0;
+    if (n == 0) return SITRK_OK;
+    OverlapScratch o;
+    RCCHK(overlap_stage1(h, fn, n, lat, lon, valid, rd_km, o));
+    // stage 2: the close set (dmin < rd) in index order, neighbours as positions in it
+    size_t tb = o.scan_bytes;
+    hipLaunchKernelGGL(flag_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, h->stream, n, o.nn, o.flag);
+    HIPCHK(rocprim::exclusive_scan(o.scan_tmp, tb, o.flag, o.pos, 0, (size_t)n, rocprim::plus<int32_t>(), h->stream));
+    hipLaunchKernelGGL(close_scatter_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, h->stream, n, o.nn, o.pos, o.cidx, o.cnn);
+    HIPCHK(hipGetLastError());
+    int32_t last[2] = {0, 0};
+    HIPCHK(download(h, &last[0], o.pos + (n - 1), 1));
+    HIPCHK(download(h, &last[1], o.flag + (n - 1), 1));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t m = (int64_t)last[0] + last[1];
+    std::vector<int32_t> cidx((size_t)m), cnn((size_t)m);
+    if (m) {
+        HIPCHK(download(h, cidx.data(), o.cidx, m));
+        HIPCHK(download(h, cnn.data(), o.cnn, m));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    // stage 3: the reference's scan (util.py:536-556) over the close set in index order; a buoy dropped at krec loses its
+    // records >= krec (zmsk[krec:,j2c] = 0), so its count becomes nrec_before; on equal counts the neighbour goes
+    std::vector<uint8_t> dead((size_t)m, 0);
+    for (int64_t p = 0; p < m; p++) {
+        if (dead[p]) continue;
+        const int32_t q = cnn[p];
+        if (q < 0 || q >= m) return fail(h, SITRK_EHIP, "%s: nearest neighbour of buoy %d outside the close set", fn, cidx[p]);
+        const int32_t i = cidx[p], k = cidx[q];
+        const int64_t ci = nrec_all[i], ck = dead[q] ? nrec_before[k] : nrec_all[k];
+        dead[ci < ck ? p : q] = 1;
+    }
+    int64_t nk = 0;
+    for (int64_t i = 0; i < n; i++) {
+        keep[i] = (valid == nullptr || valid[i] != 0) ? 1 : 0;
+    }
+    for (int64_t p = 0; p < m; p++)
+        if (dead[p]) keep[cidx[p]] = 0;
+    for (int64_t i = 0; i < n; i++) nk += keep[i];
+    *nkeep = nk;
+    if (nclose) *nclose = m;
+    return SITRK_OK;
+}

@@ -3,7 +3,7 @@
 // the lexicographically-first maximal independent set of the graph with edges where d2 < r2.  Kept in its own
 // translation unit so that the device code of sitrk.hip stays as it is.
 //
-// Steps (driven by sitrk.hip):
+// Steps (driven by sitrk_subsample_cloud() at the end of this file):
 //   1. bbox_kernel      bounding box of the cloud and the first non-finite coordinate
 //   2. bin_key_kernel   square cells of side h >= rd (padded); key = cell, value = index; the rocPRIM radix sort of
 //                       sitrk_sort.hip orders the points by cell, stably, so each cell holds its points in index order
@@ -20,6 +20,8 @@
 // is a hint (a stale "undecided" only delays a decision).  No workgroup ever waits for another.  The lowest-index
 // undecided point at a launch's start has all its earlier neighbours decided and visible (kernel boundary), so its
 // workgroup decides it in its first sweep: every launch decides at least one point.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -240,14 +242,6 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kSubThreads - 1) / kSub
 
 }  // namespace
 
-hipError_t subsample_bbox(int64_t n, const pt *yx, unsigned long long *red, hipStream_t s)
-{
-    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, s, red);
-    const unsigned g = nblk(n) < 2048u ? nblk(n) : 2048u;
-    hipLaunchKernelGGL(bbox_kernel, dim3(g), dim3(kSubThreads), 0, s, n, yx, red);
-    return hipGetLastError();
-}
-
 double subsample_key_to_double(unsigned long long k)
 {
     const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
@@ -256,31 +250,133 @@ double subsample_key_to_double(unsigned long long k)
     return d;
 }
 
-hipError_t subsample_bin_keys(const SubGrid &g, int64_t n, const pt *yx, uint32_t *key, int32_t *val, hipStream_t s)
+bool fit_cell_grid(int dims, const double *lo, const double *hi, double side, int64_t max_cells, double *inv_h, int64_t *ncell)
 {
-    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, g, n, yx, key, val);
-    return hipGetLastError();
-}
-
-hipError_t subsample_bin_gather(int64_t n, const pt *yx, const uint32_t *key_sorted, const int32_t *perm, pt *yx_s, int32_t *cstart,
-                                int32_t *cend, hipStream_t s)
-{
-    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, n, yx, key_sorted, perm, yx_s, cstart, cend);
-    return hipGetLastError();
-}
-
-hipError_t subsample_resolve(const SubResolveArgs &a, hipStream_t s)
-{
-    const int64_t per_wg = (int64_t)kSubThreads * a.ppt;
-    const unsigned g = (unsigned)((a.n + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(resolve_kernel, dim3(g), dim3(kSubThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t subsample_emit(int64_t n, const int32_t *perm, const uint8_t *state, int8_t *keep, unsigned long long *nkeep, hipStream_t s)
-{
-    hipLaunchKernelGGL(emit_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, s, n, perm, state, keep, nkeep);
-    return hipGetLastError();
+    for (int it = 0; it < 2100; it++, side *= 2.0) {
+        *inv_h = 1.0 / side;
+        bool ok = true;
+        int64_t cells = 1;
+        for (int c = 0; c < dims && ok; c++) {
+            const double t = (hi[c] - lo[c]) * *inv_h;
+            if (!(t < 1048576.0)) ok = false;
+            else cells *= (ncell[c] = (int64_t)std::floor(t) + 1);
+        }
+        if (ok && cells <= max_cells) return *inv_h > 0.0;
+    }
+    return false;
 }
 
 }  // namespace sitrk
+
+using namespace sitrk;
+
+// Everything lives in h->scratch, which the stepping never reads.
+SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, double rd_km, int8_t *keep, int64_t *nkeep,
+                                    int32_t *launches)
+{
+    NEED(h, "null handle");
+    NEED(n >= 0 && n < ((int64_t)1 << 31) - 1, "sitrk_subsample_cloud: n must be in 0..2^31-2");
+    NEED(nkeep, "sitrk_subsample_cloud: null nkeep");
+    NEED(n == 0 || (yx && keep), "sitrk_subsample_cloud: null array");
+    if (!std::isfinite(rd_km) || !(rd_km > 0.0))
+        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: rd_km must be finite and > 0 (got %g)", rd_km);
+    *nkeep = 0;
+    if (launches) *launches = 0;
+    if (n == 0) return SITRK_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t un = (size_t)n;
+    // the cell grid is known after the bounding box; size the scratch for the largest grid allowed (cells <= n + 1024)
+    const int64_t max_cells = n + 1024;
+    size_t b_sort = 0;
+    HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, un, 32, h->stream));
+    const hipStream_t st = h->stream;
+    const int64_t nwg = (n + h->subsample_block - 1) / h->subsample_block;
+    pt *d_yx, *d_yxs; uint32_t *k0, *k1; int32_t *v0, *perm, *cur_q, *cstart, *cend; uint8_t *state, *cur_k, *done;
+    int8_t *d_keep; char *sort_tmp; unsigned long long *red;
+    RCCHK(carve_scratch(h, [&](Carver &c) {
+        c.take(d_yx, un); c.take(d_yxs, un);
+        c.take(k0, un); c.take(k1, un);
+        c.take(v0, un); c.take(perm, un); c.take(cur_q, un);
+        c.take(state, un); c.take(cur_k, un); c.take(d_keep, un);
+        c.take(cstart, max_cells); c.take(cend, max_cells);
+        c.take(sort_tmp, b_sort);
+        c.take(red, 7);            // [0..4] bbox + first non-finite, [5] undecided, [6] kept (one 256-byte block)
+        c.take(done, nwg);
+    }));
+
+    HIPCHK(upload(h, d_yx, yx, un));
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, st, red);
+    hipLaunchKernelGGL(bbox_kernel, dim3(std::min(nblk(n), 2048u)), dim3(kSubThreads), 0, st, n, d_yx, red);
+    HIPCHK(hipGetLastError());
+    unsigned long long bb[5];
+    HIPCHK(download(h, bb, red, 5));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bb[4] != ~0ull)
+        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: non-finite coordinate at index %llu", bb[4]);
+    const double lo[2] = {subsample_key_to_double(bb[0]), subsample_key_to_double(bb[1])};
+    const double hi[2] = {subsample_key_to_double(bb[2]), subsample_key_to_double(bb[3])};
+    // side h >= rd, padded so that the rounding of a cell coordinate ((v - v0) * inv_h, <= 2^20) can never put a pair with
+    // d2 < r2 two cells apart
+    SubGrid g;
+    g.ymin = lo[0]; g.xmin = lo[1];
+    int64_t ncell[2] = {1, 1};
+    if (!fit_cell_grid(2, lo, hi, rd_km * (1.0 + 1.0 / 1024.0), max_cells, &g.inv_h, ncell))
+        return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: no cell grid fits the cloud's extent");
+    g.ny = (int)ncell[0]; g.nx = (int)ncell[1];
+    const int64_t ncells = ncell[0] * ncell[1];
+    unsigned end_bit = 1;
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)ncells) end_bit++;
+
+    // bin: key = cell, stable radix sort (index order inside a cell), sorted coordinates, cell ranges
+    hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, st, g, n, d_yx, k0, v0);
+    HIPCHK(hipGetLastError());
+    size_t tb = align256(b_sort);
+    HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, perm, un, end_bit, st));
+    HIPCHK(hipMemsetAsync(cstart, 0, (size_t)ncells * sizeof(*cstart), st));
+    HIPCHK(hipMemsetAsync(cend, 0, (size_t)ncells * sizeof(*cend), st));
+    hipLaunchKernelGGL(bin_gather_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, st, n, d_yx, k1, perm, d_yxs, cstart, cend);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(state, 0, un, st));
+    HIPCHK(hipMemsetAsync(cur_k, 0, un, st));
+    HIPCHK(hipMemsetAsync(cur_q, 0xff, un * sizeof(*cur_q), st));
+    HIPCHK(hipMemsetAsync(done, 0, (size_t)nwg, st));
+
+    SubResolveArgs a;
+    a.g = g; a.n = n; a.r2 = rd_km * rd_km; a.ppt = h->subsample_block / 256;
+    a.yx = d_yxs; a.perm = perm; a.cstart = cstart; a.cend = cend;
+    a.state = state; a.cur_q = cur_q; a.cur_k = cur_k; a.done = done;
+    // launches in batches; the last launch of a batch counts what it leaves undecided (an over-count at worst, and always
+    // below the previous batch's count, since every launch decides the lowest undecided point): stop at 0, give up if it stalls
+    unsigned long long prev = (unsigned long long)n + 1, und = 0;
+    int64_t nl = 0;
+    int batch = 4;
+    for (;;) {
+        for (int b = 0; b < batch; b++) {
+            a.undecided = nullptr;
+            if (b == batch - 1) {
+                HIPCHK(hipMemsetAsync(red + 5, 0, sizeof(unsigned long long), st));
+                a.undecided = red + 5;
+            }
+            hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)nwg), dim3(kSubThreads), 0, st, a);
+            HIPCHK(hipGetLastError());
+        }
+        nl += batch;
+        HIPCHK(download(h, &und, red + 5, 1));
+        HIPCHK(hipStreamSynchronize(st));
+        if (und == 0) break;
+        if (und >= prev || nl > n + 64)
+            return fail(h, SITRK_EHIP, "sitrk_subsample_cloud: undecided count stalled at %llu after %lld launches", und, (long long)nl);
+        prev = und;
+        batch = std::min(2 * batch, 64);
+    }
+    HIPCHK(hipMemsetAsync(red + 6, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(emit_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, st, n, perm, state, d_keep, red + 6);
+    HIPCHK(hipGetLastError());
+    unsigned long long nk = 0;
+    HIPCHK(download(h, keep, d_keep, un));
+    HIPCHK(download(h, &nk, red + 6, 1));
+    HIPCHK(hipStreamSynchronize(st));
+    *nkeep = (int64_t)nk;
+    if (launches) *launches = (int32_t)std::min<int64_t>(nl, INT32_MAX);
+    return SITRK_OK;
+}
