@@ -270,6 +270,40 @@ int sitrk_fetch(sitrk_t *h, double *yx, int32_t *jiT, int8_t *alive, int32_t *ki
  * (:493; dead buoys' -9999 km are converted too, like the reference). */
 int sitrk_fetch_record(sitrk_t *h, int jrec, double *yx_rec, int8_t *mask, double *latlon);
 
+/* ---- model fields along the trajectories ----------------------------------
+ * An EXTRA the reference does not have (its files hold positions only): the value of a 2-D field X on the T-grid at the
+ * host cell of every buoy, for a model record jrec.
+ *   mode SITRK_SAMPLE_AFTER  valid right after the step of jrec, like sitrk_fetch_record: out[k] = X[jT_k, iT_k], the buoy's
+ *                            host cell after the step (with nsub > 1: after its last sub-step in jrec), for exactly the buoys
+ *                            for which sitrk_fetch_record(jrec) gives mask 1 -- those that stepped at jrec, a buoy killed by
+ *                            jrec included: it is sampled in the cell that killed it.  The same device code decides both.
+ *   mode SITRK_SAMPLE_ENTER  valid before the step of jrec: out[k] = X[cell_k] for the buoys that are alive and, in sets
+ *                            with record windows, have rec_first == jrec (without windows: every alive buoy) -- the seeds,
+ *                            sampled in the record they start in (row 0 of the output files).
+ * Every other buoy gets SITRK_FILL.  No interpolation and no land masking: the value is the bit pattern found in the field,
+ * whatever a land point holds (NaN payloads included).  out has the fields' element type (f4 -> f4, f8 -> f8) and the
+ * caller's buoy order.  Both calls are queued on the compute stream behind the stepping already queued and return with out
+ * filled; they wait for the compute stream only and use none of the ingest's pinned staging, so a record upload in flight
+ * (sitrk_stage_submit*, sitrk_push_record*) goes on undisturbed.
+ * A buoy that must be sampled and whose host cell lies outside the box the field covers -> SITRK_EINVAL, their number in
+ * sitrk_last_error, out unspecified.  SITRK_EINVAL also for a bad mode, field, nf or dtype, an empty or out-of-range box, no
+ * buoys, and a slot that holds no record. */
+#define SITRK_SAMPLE_AFTER 0
+#define SITRK_SAMPLE_ENTER 1
+#define SITRK_SAMPLE_MAX_FIELDS 8  /* design limit: the field pointers travel as kernel arguments */
+/* a field of a RESIDENT record: field = 0 u, 1 v, 2 siconc -- the raw slab value at [jT,iT] (u, v: the U-/V-point east /
+ * north of the T-point; not the velocity the pick chose).  Checked against the box the library remembers for the slot (box
+ * ingest): a slot is never read outside it, so stale rows and columns cannot be sampled just because they hold numbers.
+ * Waits for an upload of the slot still in flight.  out: nP elements of the records' dtype. */
+int sitrk_sample_slot(sitrk_t *h, int slot, int jrec, int mode, int field, void *out);
+/* 1 <= nf <= SITRK_SAMPLE_MAX_FIELDS host fields of `dtype` (SITRK_F32 / SITRK_F64, independent of the records') given as
+ * boxes rows [j0,j1) x columns [i0,i1): boxes[f] addresses element (j0,i0), consecutive rows are ld elements apart (ld =
+ * i1-i0 for arrays that hold exactly the box, ld = Ni for pointers into whole (Nj,Ni) fields).  One pass over the buoys
+ * samples all nf fields.  out: (nf, nP) of dtype.  The device copies of the boxes live in the context's transient scratch
+ * (never read by the stepping) and are reused by the next call: resident memory grows by no more than the boxes. */
+int sitrk_sample_fields(sitrk_t *h, int jrec, int mode, int nf, int dtype, int j0, int j1, int i0, int i1,
+                        const void *const *boxes, int64_t ld, void *out);
+
 /* ---- locate / seeding ----------------------------------------------------
  * FindContainingCell (sitrack/locate.py:280-330) for n points: from the guess
  * T-point tries centre, i+1, j+1, i-1, j-1.  found[k] 1/0; jiT_out = centre of

@@ -16,6 +16,10 @@ SO_PATH = os.environ.get("SITRK_LIB_PATH") or os.path.join(_HERE, "libsitrk.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 SITRK_F32, SITRK_F64 = 0, 1
+SAMPLE_AFTER, SAMPLE_ENTER = 0, 1            # SITRK_SAMPLE_*
+SAMPLE_MAX_FIELDS = 8
+_SAMPLE_MODES = {"after": SAMPLE_AFTER, "enter": SAMPLE_ENTER, SAMPLE_AFTER: SAMPLE_AFTER, SAMPLE_ENTER: SAMPLE_ENTER}
+_SLOT_FIELDS = {"u": 0, "u_ice": 0, "v": 1, "v_ice": 1, "siconc": 2, "sic": 2, 0: 0, 1: 1, 2: 2}
 FillValue = -9999.0
 
 _vp = C.c_void_p
@@ -65,6 +69,8 @@ _SIGNATURES = {
     "sitrk_run": (_int, [_vp, _int, _int, _int]),
     "sitrk_fetch": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "sitrk_fetch_record": (_int, [_vp, _int, _vp, _vp, _vp]),
+    "sitrk_sample_slot": (_int, [_vp, _int, _int, _int, _int, _vp]),
+    "sitrk_sample_fields": (_int, [_vp, _int, _int, _int, _int, _int, _int, _int, _int, C.POINTER(_vp), _i64, _vp]),
     "sitrk_count_alive": (_int, [_vp, C.POINTER(_i64)]),
     "sitrk_find_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "sitrk_seed_init": (_int, [_vp, _i64] + [_vp] * 9),
@@ -474,6 +480,53 @@ class Context:
         ll = np.empty((nP, 2), dtype=np.float64) if latlon else None
         self._chk(self._L.sitrk_fetch_record(self._h, int(jrec), _ptr(yx), _ptr(mask), _ptr(ll)))
         return (yx, mask, ll) if latlon else (yx, mask)
+
+    # -- model fields along the trajectories (sitrk_sample_*)
+    @staticmethod
+    def _sample_mode(mode):
+        try:
+            return _SAMPLE_MODES[mode]
+        except (KeyError, TypeError):
+            return int(mode)                 # the library refuses it with its own message
+
+    def sample_slot(self, slot, jrec, mode, field):
+        """sitrk_sample_slot: field 0/'u', 1/'v' or 2/'siconc' of the resident record in `slot` at every buoy's host cell, (nP,)
+        of the records' dtype; mode 'after' (the buoys that stepped at jrec) or 'enter' (those that start at jrec), -9999
+        elsewhere."""
+        out = np.empty(self.nP, dtype=self.field_dtype)
+        f = _SLOT_FIELDS.get(field, field) if isinstance(field, (str, int)) else field
+        self._chk(self._L.sitrk_sample_slot(self._h, int(slot), int(jrec), self._sample_mode(mode), int(f), _ptr(out)))
+        return out
+
+    def sample_fields(self, jrec, mode, fields, box=None):
+        """sitrk_sample_fields: `fields` = a list of (Nj,Ni) arrays, or of (j1-j0, i1-i0) arrays with box = (j0,j1,i0,i1), all
+        float32 or all float64 -> (nf, nP) of that dtype.  Views into whole fields (`X[j0:j1, i0:i1]`, rows contiguous, one
+        common row pitch) are handed over as they are."""
+        j0, j1, i0, i1 = (0, self.Nj, 0, self.Ni) if box is None else (int(x) for x in box)
+        shp = (j1 - j0, i1 - i0)
+        arrs = [np.asarray(x) for x in fields]
+        if not arrs:
+            raise ValueError("sample_fields: no field given")
+        dt = np.dtype(np.float64) if any(x.dtype.newbyteorder('=') == np.float64 for x in arrs) else np.dtype(np.float32)
+        for k, x in enumerate(arrs):
+            if tuple(x.shape) != shp:
+                raise ValueError("sample_fields: field %d has shape %s, expected %s" % (k, tuple(x.shape), shp))
+            if x.dtype.newbyteorder('=') != dt:
+                raise ValueError("sample_fields: the fields must all be float32 or all float64 (field %d is %s)" % (k, x.dtype))
+        es = dt.itemsize
+        pitched = all(x.dtype == dt and x.strides[1] == es and x.strides[0] % es == 0 and x.strides[0] >= shp[1] * es for x in arrs) \
+            and len({x.strides[0] for x in arrs}) == 1
+        if pitched and shp[0] > 0 and shp[1] > 0:
+            ld = arrs[0].strides[0] // es
+        else:
+            arrs = [as_c(x, dt, shp) for x in arrs]
+            ld = shp[1]
+        nf = len(arrs)
+        out = np.empty((nf, self.nP), dtype=dt)
+        ptrs = (_vp * nf)(*[x.ctypes.data for x in arrs])
+        self._chk(self._L.sitrk_sample_fields(self._h, int(jrec), self._sample_mode(mode), nf, SITRK_F64 if dt == np.float64 else SITRK_F32,
+                                              j0, j1, i0, i1, ptrs, int(ld), _ptr(out)))
+        return out
 
     def count_alive(self):
         n = _i64(0)

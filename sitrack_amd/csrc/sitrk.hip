@@ -363,6 +363,14 @@ static int slot_wait_upload(sitrk_ctx *h, int slot)
     return SITRK_OK;
 }
 
+// a reader outside this file (sitrk_sample.hip) that needs the slab only, not the Survive bytes
+int sitrk::slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev)
+{
+    RCCHK(slot_wait_upload(h, slot));
+    *field_dev = slab_of(h, slot) + (size_t)field * h->Nj * h->Ni * elem_size(h->dtype);
+    return SITRK_OK;
+}
+
 // ... and behind a Survive derivation of the slot still in flight on the ingest stream
 static int slot_wait_sv(sitrk_ctx *h, int slot)
 {

@@ -57,6 +57,16 @@ struct BuoyState {
     int32_t *perm     = nullptr;   //                                        4 B
 };
 
+// THE per-record output rule (xmask[jt+1] of si3_part_tracker.py:459-460), shared by fetch_record_kernel and
+// sample_fields_kernel: slot s, whose packed cell is c, stepped at jrec  <=>  jrec lies in its window and it was alive before
+// that record: still alive, or killed by this very record
+__device__ __forceinline__ bool stepped_at(BuoyState st, int64_t s, int32_t c, int jrec, bool windowed)
+{
+    bool in_window = true;
+    if (windowed) { const int2 w = st.win[s]; in_window = (jrec >= w.x) && (jrec <= w.y); }
+    return in_window && (c >= 0 || st.kill_rec[s] == jrec);
+}
+
 }  // namespace sitrk
 
 struct sitrk_ctx {
@@ -181,6 +191,9 @@ namespace sitrk {
 
 int fail(sitrk_ctx *h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 int ensure_scratch(sitrk_ctx *h, size_t bytes);
+// sitrk_sample.hip reads a resident slot: the compute stream ordered behind an upload of `slot` still in flight on the copy
+// stream (sitrk.hip); *field = device address of field 0 u / 1 v / 2 siconc of the slot's slab
+int slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev);
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

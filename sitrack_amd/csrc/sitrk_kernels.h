@@ -1442,10 +1442,7 @@ __global__ void fetch_record_kernel(int64_t n, int jrec, BuoyState st, bool wind
     if (s >= n) return;
     int32_t o = st.perm[s];
     int32_t c = st.cell[s];
-    bool in_window = true;
-    if (windowed) { const int2 w = st.win[s]; in_window = (jrec >= w.x) && (jrec <= w.y); }
-    // stepped at jrec  <=>  was alive before it: still alive, or killed by this very record
-    bool stepped = in_window && (c >= 0 || st.kill_rec[s] == jrec);
+    bool stepped = stepped_at(st, s, c, jrec, windowed);
     if (yx) yx[o] = stepped ? st.pos[s] : make_pt(-9999.0, -9999.0);      // sitrack/ncio.py:19 FillValue
     if (mask) mask[o] = stepped ? 1 : 0;
 }

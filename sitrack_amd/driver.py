@@ -79,7 +79,40 @@ def parse_args(argv=None):
                     help='advance every record in NSUB Euler sub-steps of rdt/NSUB, each the reference\'s full step logic (extra; '
                          'default 1 = one step per record like the reference; 1..1024): keeps a buoy within one cell per '
                          'sub-step on 6-hourly or daily output')
+    ap.add_argument('--sample', type=_sample_arg, default=[],
+                    help='NAME[,NAME...]: 2-D variables (time,y,x) of the SI3 file written next to the positions as NAME(time,buoy), '
+                         'the raw value at each buoy\'s host T-point, no interpolation (extra; default none): `siconc` comes from '
+                         'the record resident on the GPU, any other name is read from the -i file for the records that are written')
     return ap.parse_args(argv)
+
+
+def _sample_arg(text):
+    names = [n.strip() for n in text.split(',') if n.strip()]
+    if not names or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError("--sample: expected distinct variable names NAME[,NAME...], got %r" % text)
+    return names
+
+
+def output_due(jrec, kstrt, Nt, lFull, stride=1, ends=()):
+    """does the step of model record jrec produce a record that is written (the series' k-th, or some buoys' last)"""
+    k = jrec - kstrt + 1                               # the record of the series this step produces
+    return bool((lFull and (k % stride == 0 or k == Nt)) or ((not lFull) and jrec in ends))
+
+
+def plan_batches(Nt, kstrt, K, lFull, stride=1, ends=(), firsts=None):
+    """The record loop's batches [(jt, m)]: consecutive records go into one sitrk_run of up to K // 2 records, cut after every
+    record whose output is due (output_due) and -- only when fields are sampled (`firsts` = the distinct first records of the
+    buoys' windows) -- in front of every record some buoy starts in, where its seed is sampled before the step."""
+    firsts = set(firsts) if firsts is not None else set()
+    batches, jt = [], 0
+    while jt < Nt:
+        m = 1
+        while m < K // 2 and jt + m < Nt and not output_due(jt + m - 1 + kstrt, kstrt, Nt, lFull, stride, ends) \
+                and (jt + m + kstrt) not in firsts:
+            m += 1
+        batches.append((jt, m))
+        jt += m
+    return batches
 
 
 def _rdt_arg(text):
@@ -330,6 +363,18 @@ def main(argv=None):
         xYv, xXv, xYu, xXu = xYf, xXf, xYf, xXf     # never read by the cell-mean rule
     (Nj, Ni) = np.shape(imaskt)
     records = ncio.ModelRecords(cf_uv)
+    # --sample: every name must be a (time, y, x) variable of the SI3 file -- checked now, before anything is computed
+    smp_names, smp_attrs, smp_dtype = list(a.sample), {}, {}
+    for n in smp_names:
+        if not records.f.has_var(n):
+            raise ValueError("--sample: the SI3 file %s has no variable '%s'" % (cf_uv, n))
+        x0 = np.asarray(records.fields(kstrt, (n,))[0])
+        if x0.shape != (Nj, Ni):
+            raise ValueError("--sample: variable '%s' of %s is not a (time, y, x) field of the %d x %d mesh" % (n, cf_uv, Nj, Ni))
+        smp_attrs[n] = ncio.model_var_attrs(records.f, n)
+        smp_dtype[n] = np.dtype(np.float32) if x0.dtype.newbyteorder('=') == np.float32 else np.dtype(np.float64)
+        if n in ncio.SCHEMA_VARS:
+            raise ValueError("--sample: '%s' collides with a variable of the trajectory files" % n)
     tk = clk.add("read_mesh_s", tk)
 
     # ---- seeding, with the reference's intermediate cache (:205-255).  Seeds are independent: with several ranks
@@ -410,9 +455,12 @@ def main(argv=None):
     if lFull and comm.root:
         cf_series = ('./nc/' + corgn + '_tracking_' + SeedBatch + cdtbin + '_' + date_tag(vTime[0]) + '_' + date_tag(vTime[Nt]) + csfkm
                      + ('_stride%d' % stride if stride > 1 else '') + '.nc')
-        series = ncio.CloudBuoysStream(cf_series, vTime[::stride], IDs, with_mask=True, corigin=corgn)
-        # record 0: the seeds as the seeding file gave them (:331-333; in 1-D-time mode every window opens at record 0)
-        series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'))
+        series = ncio.CloudBuoysStream(cf_series, vTime[::stride], IDs, with_mask=True, corigin=corgn,
+                                       extra_names={n: smp_attrs[n] for n in smp_names} if smp_names else None)
+        # record 0: the seeds as the seeding file gave them (:331-333; in 1-D-time mode every window opens at record 0); with
+        # --sample it waits for the fields sampled in the seeds' cells, in front of the first step
+        if not smp_names:
+            series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'))
         z2XY, z2GC = np.zeros((2, nP, 2)) + FILL, np.zeros((2, nP, 2)) + FILL
         zMSK = np.zeros((2, nP), dtype='i1')
         z2XY[0], z2GC[0], zMSK[0] = xPosC0, xPosG0, 1
@@ -435,21 +483,21 @@ def main(argv=None):
     #      only (:565-571).  Records are read straight into the library's pinned staging and uploaded on its copy stream
     #      while the previous batch is stepped with; `-F` / `-p` need every record's positions: batches of one.
     def need_output(jrec):
-        k = jrec - kstrt + 1                               # the record of the series this step produces
-        return (lFull and (k % stride == 0 or k == Nt)) or (lUse2DTime and jrec in ends)
+        return output_due(jrec, kstrt, Nt, lFull, stride, ends if lUse2DTime else ())
+
+    # --sample: the two rows of the tracking12 file (root), and where seeds are sampled before the step: record kstrt with -F,
+    # every distinct first record of the windows otherwise
+    firsts = None
+    if smp_names:
+        firsts = set(np.unique(z1stModelRec).tolist()) if lUse2DTime else {kstrt}
+        zS = {n: np.full((2, nP), FILL, dtype=np.float32) for n in smp_names} if comm.root else None
 
     bcast = None
     if a.full_records and comm.multi and comm.backend == "nccl":
         from .distributed import RecordBroadcaster
         bcast = RecordBroadcaster(ctx)                 # rank 0 reads; one RCCL broadcast per record, overlapped with the stepping
-    batches, jt = [], 0
-    while jt < Nt:
-        m = 1
-        while m < K // 2 and jt + m < Nt and not need_output(jt + m - 1 + kstrt):
-            m += 1
-        batches.append((jt, m))
-        jt += m
-    band = {"box": None, "age": None, "bytes": 0}
+    batches = plan_batches(Nt, kstrt, K, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None)
+    band = {"box": None, "age": None, "bytes": 0, "boxes": {}}
     esz = np.dtype(fdt).itemsize
 
     def upload(jt0, m):
@@ -464,6 +512,7 @@ def main(argv=None):
                 band["age"] = 0
             j0, j1, i0, i1 = ctx.box_of(*band["box"], band["age"] + m - 1)
             band["age"] += m
+            band["boxes"][jt0] = (j0, j1, i0, i1)            # what the batch's slots hold: the box its records are sampled in
         for r in range(m):
             jrec, slot = jt0 + r + kstrt, (jt0 + r) % K
             if not a.full_records:
@@ -479,6 +528,29 @@ def main(argv=None):
             else:
                 comm.deliver_record(ctx, slot, records.fields(jrec) if comm.root else None)   # gloo rehearsal: host broadcast
         clk.add("read_and_stage_records_s", t_up)
+
+    def sample(jrec, jt0, mode):
+        """--sample: the fields at this rank's buoys for model record jrec of the batch that starts at jt0 -- 'enter' before its
+        step, 'after' behind it -- gathered into (nP, names) f4 in the caller's order on rank 0 (None elsewhere).  siconc comes
+        from the resident slot; the other variables are read from the file for this record only, as the box the batch's slots
+        hold (a buoy's cell stays inside it during the batch), and travel to the GPU through sitrk_sample_fields."""
+        t_s = clk.now()
+        nloc = len(part["mine"])
+        rows = np.full((nloc, len(smp_names)), FILL, dtype=np.float32)
+        box = band["boxes"].get(jt0)                         # None: whole records (--full-records)
+        if nloc and (box is None or (box[1] > box[0] and box[3] > box[2])):
+            for dt in (np.dtype(np.float32), np.dtype(np.float64)):
+                cols = [k for k, n in enumerate(smp_names) if n != 'siconc' and smp_dtype[n] == dt]
+                for b in range(0, len(cols), _lib.SAMPLE_MAX_FIELDS):
+                    grp = cols[b:b + _lib.SAMPLE_MAX_FIELDS]
+                    j0, j1, i0, i1 = box if box is not None else (0, Nj, 0, Ni)
+                    bufs = [np.empty((j1 - j0, i1 - i0), dtype=dt) for _ in grp]
+                    records.fields_box_into(jrec, j0, j1, i0, i1, bufs, names=[smp_names[k] for k in grp])
+                    rows[:, grp] = ctx.sample_fields(jrec, mode, bufs, box=(j0, j1, i0, i1)).T
+            if 'siconc' in smp_names:
+                rows[:, smp_names.index('siconc')] = ctx.sample_slot((jrec - kstrt) % K, jrec, mode, 'siconc')
+        clk.add("sample_s", t_s)
+        return to_caller_order(comm.gather_rows(rows, nP))
 
     tk = clk.add("setup_s", tk)
     t_loop = clk.now()
@@ -545,6 +617,21 @@ def main(argv=None):
         used = [(jt0 + r) % K for r in range(m)]
         if bcast is not None:
             bcast.before_run(used)
+        if smp_names and jrec0 in firsts:
+            # the seeds that start at jrec0, sampled in that record before it moves them: row 0 of the files
+            srow = sample(jrec0, jt0, 'enter')
+            if comm.root:
+                sel = np.where(z1stModelRec == jrec0)[0]
+                for kn, n in enumerate(smp_names):
+                    zS[n][0, sel] = srow[sel, kn]
+                if lFull:
+                    try:
+                        series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'),
+                                   extra={n: srow[:, kn] for kn, n in enumerate(smp_names)})
+                    except BaseException:
+                        series.abort()
+                        raise
+            t_q = clk.now()
         trk.run(jrec0, jt0 % K, m)
         if bcast is not None:
             bcast.after_run(used)
@@ -563,24 +650,33 @@ def main(argv=None):
             else:
                 pos_l, msk_l = trk.record(jrec)
             pos, msk = to_caller_order(comm.gather_rows(pos_l, nP)), to_caller_order(comm.gather_rows(msk_l, nP))
+            if smp_names:
+                t_f = clk.add("fetch_and_store_outputs_s", t_f)
+                srow = sample(jrec, jt0, 'after')
+                t_f = clk.now()
         if need and comm.root:
             stepped = msk == 1
             if lFull:
                 k = jt + 1
                 try:
                     if k % stride == 0:
-                        series.put(k // stride, pos[:, 0], pos[:, 1], ll[:, 0], ll[:, 1], msk)
+                        series.put(k // stride, pos[:, 0], pos[:, 1], ll[:, 0], ll[:, 1], msk,
+                                   extra={n: srow[:, kn] for kn, n in enumerate(smp_names)} if smp_names else None)
                 except BaseException:
                     series.abort()
                     raise
                 if k == Nt:
                     z2XY[1], z2GC[1], zMSK[1] = pos, ll, msk
+                    for kn, n in enumerate(smp_names):
+                        zS[n][1] = srow[:, kn]
             if lUse2DTime and jrec in ends:
                 sel = np.where(zLstModelRec == jrec)[0]
                 z2XY[1, sel] = pos[sel]
                 z2GC[1, sel] = ctx.cart2geo(pos[sel])
                 zMSK[1, sel] = msk[sel]
                 zTim[1, sel[stepped[sel]]] = int(itime + rdt)
+                for kn, n in enumerate(smp_names):
+                    zS[n][1, sel] = srow[sel, kn]
         clk.add("fetch_and_store_outputs_s", t_f)
         if due[ib]:
             t_r = clk.now()
@@ -616,7 +712,7 @@ def main(argv=None):
         zvt = np.array([np.mean(zTim[0, :]), np.mean(zTim[1, :])])
     cf_nc_out = './nc/' + corgn + '_tracking12_' + SeedBatch + cdtbin + '_' + date_tag(zvt[0]) + '_' + date_tag(zvt[1]) + csfkm + '.nc'
     ncio.ncSaveCloudBuoys(cf_nc_out, zvt, IDs, z2XY[:, :, 0], z2XY[:, :, 1], z2GC[:, :, 0], z2GC[:, :, 1], mask=zMSK, xtime=zTim,
-                          corigin=corgn)
+                          corigin=corgn, extra={n: (zS[n], smp_attrs[n]) for n in smp_names} if smp_names else None)
     outs.append(cf_nc_out)
 
     if a.plot > 0:

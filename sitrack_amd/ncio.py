@@ -326,10 +326,37 @@ class ModelRecords:
         self.f.close()
 
 
+SCHEMA_VARS = ('time', 'buoy', 'id_buoy', 'latitude', 'longitude', 'y_pos', 'x_pos', 'mask', 'time_pos')
+
+
+def _check_extra(extra, shape=None, who='ncSaveCloudBuoys'):
+    """`extra`: name -> (array, attrs) (or name -> attrs for a stream, shape=None): sampled model fields written next to the
+    positions as NAME(time,buoy) f4.  A name of the schema is refused."""
+    out = {}
+    for name, val in (extra or {}).items():
+        if name in SCHEMA_VARS:
+            raise ValueError("%s: extra variable '%s' collides with a variable of the trajectory schema" % (who, name))
+        if shape is None:
+            out[name] = (None, dict(val or {}))
+            continue
+        arr, attrs = val
+        if np.shape(arr) != shape:
+            raise ValueError("%s: extra variable '%s' has shape %s, expected %s" % (who, name, np.shape(arr), shape))
+        out[name] = (np.asarray(arr, dtype=np.float32), dict(attrs or {}))
+    return out
+
+
+def model_var_attrs(reader, name):
+    """units / long_name of a model-file variable, where present (what an extra variable carries over)"""
+    return {a: reader.attr(name, a) for a in ('units', 'long_name') if reader.has_attr(name, a)}
+
+
 def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[], tunits=tunits_default, fillVal=FillValue,
-                     corigin=None, cauthor='si3_part_tracker.py'):
+                     corigin=None, cauthor='si3_part_tracker.py', extra=None):
     """Reference ncio.py:131-197: dims time (unlimited), buoy; time i4, buoy i4, id_buoy i8, latitude/longitude/
-    y_pos/x_pos f4 (_FillValue -9999, zlib 9), optional mask i1 and time_pos i4; global Origin/About/Author."""
+    y_pos/x_pos f4 (_FillValue -9999, zlib 9), optional mask i1 and time_pos i4; global Origin/About/Author.
+    `extra` (not in the reference): name -> ((Nt,Nb) array, attrs), each written like y_pos -- f4, _FillValue, same deflate and
+    chunking -- with the given attributes (units, long_name); absent: the reference's file."""
     (Nt,) = np.shape(ptime)
     (Nb,) = np.shape(pIDs)
     for a in (pY, pX, pLat, pLon):
@@ -337,13 +364,14 @@ def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[],
             raise ValueError('ERROR [ncSaveCloudBuoys]: one of the 2D arrays has a wrong shape!!!')
     lSaveMask = (np.shape(mask) == (Nt, Nb))
     lSaveTime = (np.shape(xtime) == (Nt, Nb))
+    extra = _check_extra(extra, (Nt, Nb))
     os.makedirs(path.dirname(cf_out) or '.', exist_ok=True)
     about = 'Lagrangian sea-ice drift'
     author = 'Generated with `' + cauthor + '` of `sitrack` (L. Brodeau, 2023)'
     from . import h5lite
     if _nc4 is None and h5lite.writer_available():
         return _save_nc4_hdf5(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask if lSaveMask else None, xtime if lSaveTime else None,
-                              tunits, fillVal, corigin, about, author)
+                              tunits, fillVal, corigin, about, author, extra)
     if _nc4 is not None:
         f = _nc4.Dataset(cf_out, 'w', format='NETCDF4')
         f.createDimension('time', None)
@@ -360,6 +388,7 @@ def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[],
             v_mask = f.createVariable('mask', 'i1', ('time', 'buoy'), zlib=True, complevel=9)
         if lSaveTime:
             x_tim = f.createVariable('time_pos', 'i4', ('time', 'buoy'), **kw)
+        x_extra = {n: f.createVariable(n, 'f4', ('time', 'buoy'), **kw) for n in extra}
     else:
         from scipy.io import netcdf_file
         f = netcdf_file(cf_out, 'w', version=2)
@@ -383,6 +412,9 @@ def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[],
         if lSaveTime:
             x_tim = f.createVariable('time_pos', 'i4', ('time', 'buoy'))
             x_tim._FillValue = np.int32(fillVal)
+        x_extra = {n: f.createVariable(n, 'f4', ('time', 'buoy')) for n in extra}
+        for v in x_extra.values():
+            v._FillValue = np.float32(fillVal)
     v_time.units = tunits
     v_bid.units = 'ID of buoy'
     x_lat.units = 'degrees north'
@@ -403,6 +435,10 @@ def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[],
         v_mask[:, :] = np.asarray(mask, dtype='i1')
     if lSaveTime:
         x_tim[:, :] = np.asarray(xtime).astype('i4')
+    for n, (arr, attrs) in extra.items():
+        for k, val in attrs.items():
+            setattr(x_extra[n], k, val)
+        x_extra[n][:, :] = arr
     if corigin:
         f.Origin = corigin
     f.About = about
@@ -411,7 +447,7 @@ def ncSaveCloudBuoys(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask=[], xtime=[],
     return 0
 
 
-def _nc4_hdf5_create(cf_out, Nt, pIDs, with_mask, with_xtime, tunits, fillVal, corigin, about, author):
+def _nc4_hdf5_create(cf_out, Nt, pIDs, with_mask, with_xtime, tunits, fillVal, corigin, about, author, extra=None):
     """The NetCDF-4 file of ncSaveCloudBuoys without the netCDF4 package (reference ncio.py:143-195 -- dimensions, variable types,
     `_FillValue`, shuffle + deflate at level 9, units, global attributes), created at its final length of Nt records through
     libhdf5; the record variables are still to be written.  Returns the open h5lite.NC4Writer."""
@@ -432,6 +468,10 @@ def _nc4_hdf5_create(cf_out, Nt, pIDs, with_mask, with_xtime, tunits, fillVal, c
             w.createVariable('mask', 'i1', ('time', 'buoy'), zlib=True, complevel=lvl, nrec=Nt)
         if with_xtime:
             w.createVariable('time_pos', 'i4', ('time', 'buoy'), **kw)
+        for name, (_, attrs) in (extra or {}).items():
+            w.createVariable(name, 'f4', ('time', 'buoy'), **kw)
+            for k, val in attrs.items():
+                w.set_attr(name, k, val)
         w.set_attr('time', 'units', tunits)
         w.set_attr('id_buoy', 'units', 'ID of buoy')
         w.set_attr('latitude', 'units', 'degrees north')
@@ -452,9 +492,9 @@ def _nc4_hdf5_create(cf_out, Nt, pIDs, with_mask, with_xtime, tunits, fillVal, c
     return w
 
 
-def _save_nc4_hdf5(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask, xtime, tunits, fillVal, corigin, about, author):
+def _save_nc4_hdf5(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask, xtime, tunits, fillVal, corigin, about, author, extra=None):
     """ncSaveCloudBuoys without the netCDF4 package: the same NetCDF-4 file written through libhdf5, whole arrays at once."""
-    w = _nc4_hdf5_create(cf_out, len(ptime), pIDs, mask is not None, xtime is not None, tunits, fillVal, corigin, about, author)
+    w = _nc4_hdf5_create(cf_out, len(ptime), pIDs, mask is not None, xtime is not None, tunits, fillVal, corigin, about, author, extra)
     try:
         w.write('time', np.asarray(ptime).astype('i4'))
         w.write('latitude', np.asarray(pLat, dtype=np.float32))
@@ -465,6 +505,8 @@ def _save_nc4_hdf5(cf_out, ptime, pIDs, pY, pX, pLat, pLon, mask, xtime, tunits,
             w.write('mask', np.asarray(mask, dtype='i1'))
         if xtime is not None:
             w.write('time_pos', np.asarray(xtime).astype('i4'))
+        for name, (arr, _) in (extra or {}).items():
+            w.write(name, arr)
     except BaseException:
         w.abort()
         raise
@@ -481,16 +523,21 @@ class CloudBuoysStream:
     written as raw chunks, flushed every `flush_bytes`; netCDF4 or the NetCDF-3 fall-back: one record slice per variable)."""
 
     def __init__(self, cf_out, ptime, pIDs, with_mask=True, tunits=tunits_default, fillVal=FillValue, corigin=None,
-                 cauthor='si3_part_tracker.py', flush_bytes=None):
+                 cauthor='si3_part_tracker.py', flush_bytes=None, extra_names=None):
+        """`extra_names` (not in the reference): names, or name -> attrs, of extra f4 variables NAME(time,buoy) written like
+        y_pos; every put() must then carry them (`extra`)."""
         from . import h5lite
         self.path, self.Nt, self.Nb = cf_out, len(ptime), len(pIDs)
+        if extra_names is not None and not isinstance(extra_names, dict):
+            extra_names = {n: None for n in extra_names}
+        self.extra = _check_extra(extra_names, None, 'CloudBuoysStream')
         self.with_mask, self.nput = with_mask, 0
         os.makedirs(path.dirname(cf_out) or '.', exist_ok=True)
         about = 'Lagrangian sea-ice drift'
         author = 'Generated with `' + cauthor + '` of `sitrack` (L. Brodeau, 2023)'
         self.w = self.f = None
         if _nc4 is None and h5lite.writer_available():
-            self.w = _nc4_hdf5_create(cf_out, self.Nt, pIDs, with_mask, False, tunits, fillVal, corigin, about, author)
+            self.w = _nc4_hdf5_create(cf_out, self.Nt, pIDs, with_mask, False, tunits, fillVal, corigin, about, author, self.extra)
             # rows wait (as arrays + deflated blobs) until this many bytes are queued: the writer's share of the peak memory
             self.flush_bytes = int(flush_bytes if flush_bytes is not None else os.environ.get('SITRK_NC_FLUSH_BYTES', str(96 << 20)))
             self.queued = 0
@@ -513,8 +560,12 @@ class CloudBuoysStream:
         self.v = {n: f.createVariable(n, 'f4', ('time', 'buoy'), **kw) for n in ('latitude', 'longitude', 'y_pos', 'x_pos')}
         if with_mask:
             self.v['mask'] = f.createVariable('mask', 'i1', ('time', 'buoy'), **({'zlib': True, 'complevel': 9} if _nc4 is not None else {}))
+        for n, (_, attrs) in self.extra.items():
+            self.v[n] = f.createVariable(n, 'f4', ('time', 'buoy'), **kw)
+            for k_, val in attrs.items():
+                setattr(self.v[n], k_, val)
         if _nc4 is None:
-            for n in ('latitude', 'longitude', 'y_pos', 'x_pos'):
+            for n in ('latitude', 'longitude', 'y_pos', 'x_pos') + tuple(self.extra):
                 self.v[n]._FillValue = np.float32(fillVal)
         v_time.units = tunits
         v_bid.units = 'ID of buoy'
@@ -529,14 +580,18 @@ class CloudBuoysStream:
         f.Author = author
         self.f = f
 
-    def put(self, k, pY, pX, pLat, pLon, mask=None):
-        """record k of the file (0 <= k < Nt): (nP,) arrays"""
+    def put(self, k, pY, pX, pLat, pLon, mask=None, extra=None):
+        """record k of the file (0 <= k < Nt): (nP,) arrays; `extra`: name -> (nP,) array for every name of extra_names"""
         if not (0 <= k < self.Nt):
             raise IndexError("record %d outside the %d records of %s" % (k, self.Nt, self.path))
         rows = {'latitude': np.asarray(pLat, dtype=np.float32), 'longitude': np.asarray(pLon, dtype=np.float32),
                 'y_pos': np.asarray(pY, dtype=np.float32), 'x_pos': np.asarray(pX, dtype=np.float32)}
         if self.with_mask:
             rows['mask'] = np.asarray(mask, dtype='i1')
+        if set(extra or {}) != set(self.extra):
+            raise ValueError('CloudBuoysStream.put: extra variables %s given, the file has %s' % (sorted(extra or {}), sorted(self.extra)))
+        for n in self.extra:
+            rows[n] = np.asarray(extra[n], dtype=np.float32)
         for n, r in rows.items():
             if r.shape != (self.Nb,):
                 raise ValueError('CloudBuoysStream.put: %s has shape %s, expected (%d,)' % (n, r.shape, self.Nb))

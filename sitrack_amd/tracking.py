@@ -197,6 +197,34 @@ class IceTracker:
     def record(self, jrec, latlon=False):
         return self.ctx.fetch_record(jrec, latlon=latlon)
 
+    def sample(self, jrec, fields=None, slot=None, mode='after'):
+        """Model fields at every buoy's host cell (an extra the reference does not have; sitrk_sample_*): mode 'after' = right
+        after the step of jrec, for the buoys record(jrec) masks 1; 'enter' = before it, for the buoys that start at jrec;
+        -9999 elsewhere, no interpolation.  `fields`: a dict name -> (Nj,Ni) array or a list / tuple of them, all float32 or
+        all float64; the string 'siconc' (as a value or list entry) is served from the resident record in `slot`.  Returns a
+        dict under the same names, or a tuple in the order given.  fields=None: siconc of `slot` alone, as one array."""
+        if fields is None:
+            fields = 'siconc'
+        single = isinstance(fields, str) or isinstance(fields, np.ndarray)
+        if single:
+            fields = [fields]
+        names, vals = (list(fields.keys()), list(fields.values())) if isinstance(fields, dict) else (None, list(fields))
+        out = [None] * len(vals)
+        host = [k for k, x in enumerate(vals) if not isinstance(x, str)]
+        for k, x in enumerate(vals):
+            if isinstance(x, str):
+                if slot is None:
+                    raise ValueError("IceTracker.sample: '%s' is served from a resident record: give its slot" % x)
+                out[k] = self.ctx.sample_slot(slot, jrec, mode, x)
+        for b in range(0, len(host), _lib.SAMPLE_MAX_FIELDS):              # one pass over the buoys per 8 host fields
+            part = host[b:b + _lib.SAMPLE_MAX_FIELDS]
+            rows = self.ctx.sample_fields(jrec, mode, [vals[k] for k in part])
+            for k, r in zip(part, rows):
+                out[k] = r
+        if names is not None:
+            return dict(zip(names, out))
+        return out[0] if single else tuple(out)
+
     def state(self):
         s = self.ctx.fetch()
         s["vJIt"] = s.pop("jiT").astype(np.int64)
