@@ -304,6 +304,53 @@ int sitrk_sample_slot(sitrk_t *h, int slot, int jrec, int mode, int field, void 
 int sitrk_sample_fields(sitrk_t *h, int jrec, int mode, int nf, int dtype, int j0, int j1, int i0, int i1,
                         const void *const *boxes, int64_t ld, void *out);
 
+/* ---- deformation rates of buoy triangles and quadrangles ---------------------
+ * An EXTRA the reference does not have (its tracking12 file is written for the RGPS-style deformation scripts of another
+ * project): divergence, shear and vorticity of cells whose vertices are buoys, from the buoys' positions at two times.  No
+ * parity claim is made against any other code; the contract below is this library's own.
+ * A cell is nv = 3 or 4 buoy indices in the caller's buoy order, in either orientation; cells is (nC, nv) int32.
+ * Per cell, with the t0 positions (y_k, x_k) and the t1 positions (Y_k, X_k) of its vertices in km, the elapsed time T in
+ * seconds and k' = (k+1) mod nv, everything in fp64, one rounded operation per symbol, no fused multiply-add, this order:
+ *     dx_k = x_k - x_0 ; dy_k = y_k - y_0                  (t0, relative to vertex 0)
+ *     u_k  = (X_k - x_k) / T ; v_k = (Y_k - y_k) / T       [km/s]
+ *     A2 = Suy = Sux = Svy = Svx = 0.0 ; then for k = 0 .. nv-1 in this order:
+ *       A2  = A2  + (dx_k*dy_k' - dx_k'*dy_k)
+ *       Suy = Suy + (u_k' + u_k)*(dy_k' - dy_k) ;  Sux = Sux + (u_k' + u_k)*(dx_k' - dx_k)
+ *       Svy = Svy + (v_k' + v_k)*(dy_k' - dy_k) ;  Svx = Svx + (v_k' + v_k)*(dx_k' - dx_k)
+ *     u_x = Suy/A2 ; u_y = -(Sux/A2) ; v_x = Svy/A2 ; v_y = -(Svx/A2)        [1/s]
+ *     div = u_x + v_y ; vor = v_x - u_y ; shr = sqrt((u_x - v_y)*(u_x - v_y) + (u_y + v_x)*(u_y + v_x))
+ *     area0 = 0.5*|A2| ; area1 = 0.5*|A2'|   (A2' = the same shoelace sum on the t1 positions relative to (Y_0, X_0))   [km^2]
+ * This is the line-integral (Green) estimate on the t0 contour: exact for a velocity field that is linear in space, and, A2
+ * being signed, independent of the orientation.  out (5, nC) fp64 = div, shr, vor, area0, area1; valid (nC) int8.
+ * A cell is INVALID -- valid = 0 and all five values SITRK_FILL -- if a vertex is invalid at t0 or at t1, if any of its
+ * 4 nv coordinates is not finite, if A2 == 0 or if A2 is not finite.  No filter on the cells' shape: area0 and area1 are there
+ * for the caller's.  *nvalid (may be NULL) = number of valid cells.
+ * A vertex index outside [0, nP) is an error, not an invalid cell: SITRK_EINDEX with the number of offending cells in
+ * sitrk_last_error (out and valid unspecified); such an index is never dereferenced and the handle stays usable.
+ * Only + - * / are bit-reproducible from the order above; sqrt is the device's.
+ *
+ * sitrk_deform_cells: host arrays yx0, yx1 (nP,2) [y,x] km, mask0 / mask1 (nP) int8, 0 = invalid vertex at t0 / t1 (NULL:
+ * every buoy valid).  Synchronous on the handle's stream; nC == 0 is valid.  Uses the context's transient scratch only (never
+ * read by the stepping): the grid, buoys and records of a tracker on the same handle are left as they were.  SITRK_EINVAL
+ * for nv not in {3,4}, T not finite or <= 0 and missing pointers. */
+int sitrk_deform_cells(sitrk_t *h, int64_t nP, const double *yx0, const double *yx1, const int8_t *mask0, const int8_t *mask1,
+                       int64_t nC, int nv, const int32_t *cells, double T, double *out, int8_t *valid, int64_t *nvalid);
+/* The same without moving a position to the host.  sitrk_deform_mark is queued on the compute stream behind the stepping
+ * already queued and snapshots the current fp64 positions of all buoys, in the caller's order, into a device buffer of 16
+ * bytes per buoy that belongs to the context: allocated at the first mark, overwritten by the next one, freed by
+ * sitrk_set_buoys and sitrk_destroy, which both cancel the mark.  jrec0 = the model record that will be stepped next.
+ * sitrk_deform_since_mark is valid right after the step of jrec1 >= jrec0: t0 = the snapshot, t1 = the current positions,
+ * T = (jrec1 - jrec0 + 1) * rdt (one rounded product).  A buoy is a valid vertex iff it is alive now and, in sets with record
+ * windows, rec_first <= jrec0 && rec_last >= jrec1: it was stepped at every record of the span.  The snapshot is in the
+ * caller's order, so a re-sort between the two calls changes nothing.  Only cells go up and out / valid come back.
+ * SITRK_EINVAL without a mark, for jrec1 < jrec0 and for no buoys; otherwise as sitrk_deform_cells. */
+int sitrk_deform_mark(sitrk_t *h, int jrec0);
+int sitrk_deform_since_mark(sitrk_t *h, int jrec1, int64_t nC, int nv, const int32_t *cells, double *out, int8_t *valid,
+                            int64_t *nvalid);
+/* measurement: GPU time [ms] of the kernels of the last sitrk_deform_cells / sitrk_deform_since_mark on this handle, from HIP
+ * events around them -- the pass over the points, the cell kernel; either pointer may be NULL */
+int sitrk_deform_kernel_ms(sitrk_t *h, float *points_ms, float *cells_ms);
+
 /* ---- locate / seeding ----------------------------------------------------
  * FindContainingCell (sitrack/locate.py:280-330) for n points: from the guess
  * T-point tries centre, i+1, j+1, i-1, j-1.  found[k] 1/0; jiT_out = centre of

@@ -71,6 +71,10 @@ _SIGNATURES = {
     "sitrk_fetch_record": (_int, [_vp, _int, _vp, _vp, _vp]),
     "sitrk_sample_slot": (_int, [_vp, _int, _int, _int, _int, _vp]),
     "sitrk_sample_fields": (_int, [_vp, _int, _int, _int, _int, _int, _int, _int, _int, C.POINTER(_vp), _i64, _vp]),
+    "sitrk_deform_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp, _dbl, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_deform_mark": (_int, [_vp, _int]),
+    "sitrk_deform_since_mark": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_deform_kernel_ms": (_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sitrk_count_alive": (_int, [_vp, C.POINTER(_i64)]),
     "sitrk_find_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "sitrk_seed_init": (_int, [_vp, _i64] + [_vp] * 9),
@@ -527,6 +531,59 @@ class Context:
         self._chk(self._L.sitrk_sample_fields(self._h, int(jrec), self._sample_mode(mode), nf, SITRK_F64 if dt == np.float64 else SITRK_F32,
                                               j0, j1, i0, i1, ptrs, int(ld), _ptr(out)))
         return out
+
+    # -- deformation rates of buoy cells (sitrk_deform_*)
+    @staticmethod
+    def _deform_cells_arg(cells, name):
+        """(nC, 3|4) int32, C-contiguous; indices that do not fit int32 become -1 (the library reports them as out of range)"""
+        c = np.asarray(cells)
+        if c.ndim != 2 or c.shape[1] not in (3, 4):
+            raise ValueError("%s: cells must be an (nC, 3) or (nC, 4) integer array, got shape %s" % (name, c.shape))
+        if c.dtype.kind not in "iu":
+            raise ValueError("%s: cells must hold integers, got %s" % (name, c.dtype))
+        c32 = as_c(c, np.int32)
+        if c32.dtype != c.dtype:
+            c32[c32 != c] = -1
+        return c32
+
+    def deform_cells(self, yx0, yx1, cells, T, mask0=None, mask1=None):
+        """sitrk_deform_cells: (out (5, nC) = div, shr, vor, area0, area1; valid (nC,) bool; nvalid) of the cells (nC, 3|4) of
+        buoy indices, from the positions yx0, yx1 (nP,2) km that lie T seconds apart; mask0 / mask1: 0 = invalid vertex."""
+        yx0 = as_c(yx0, np.float64)
+        nP = yx0.shape[0]
+        yx0 = as_c(yx0, np.float64, (nP, 2), "yx0")
+        yx1 = as_c(yx1, np.float64, (nP, 2), "yx1")
+        m0 = None if mask0 is None else as_c(np.asarray(mask0) != 0, np.int8, (nP,), "mask0")
+        m1 = None if mask1 is None else as_c(np.asarray(mask1) != 0, np.int8, (nP,), "mask1")
+        c = self._deform_cells_arg(cells, "deform_cells")
+        nC, nv = c.shape
+        out = np.empty((5, nC), dtype=np.float64)
+        valid = np.empty(nC, dtype=np.int8)
+        nvalid = _i64(0)
+        self._chk(self._L.sitrk_deform_cells(self._h, nP, _ptr(yx0), _ptr(yx1), _ptr(m0), _ptr(m1), nC, nv, _ptr(c), float(T),
+                                             _ptr(out), _ptr(valid), C.byref(nvalid)))
+        return out, valid.astype(bool), nvalid.value
+
+    def deform_mark(self, jrec0):
+        """sitrk_deform_mark: snapshot every buoy's position on the device; jrec0 = the model record stepped next"""
+        self._chk(self._L.sitrk_deform_mark(self._h, int(jrec0)))
+
+    def deform_since_mark(self, jrec1, cells):
+        """sitrk_deform_since_mark, right after the step of jrec1: like deform_cells() between the mark and now, no position
+        leaving the device"""
+        c = self._deform_cells_arg(cells, "deform_since_mark")
+        nC, nv = c.shape
+        out = np.empty((5, nC), dtype=np.float64)
+        valid = np.empty(nC, dtype=np.int8)
+        nvalid = _i64(0)
+        self._chk(self._L.sitrk_deform_since_mark(self._h, int(jrec1), nC, nv, _ptr(c), _ptr(out), _ptr(valid), C.byref(nvalid)))
+        return out, valid.astype(bool), nvalid.value
+
+    def deform_kernel_ms(self):
+        """(points_ms, cells_ms): GPU time of the two kernels of the last deform call (sitrk_deform_kernel_ms)"""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self._L.sitrk_deform_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def count_alive(self):
         n = _i64(0)

@@ -67,6 +67,7 @@ static void free_buoys(sitrk_ctx *h)
     dev_free(h->sort_tmp);
     h->sort_tmp = nullptr; h->sort_tmp_bytes = 0;
     h->nP = 0;
+    deform_release(h, false);           // the snapshot of sitrk_deform_mark belongs to these buoys
 }
 
 static void free_records(sitrk_ctx *h);
@@ -123,6 +124,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     if (h->sv_stream) (void)hipStreamSynchronize(h->sv_stream);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_buoys(h);
+    deform_release(h, true);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);

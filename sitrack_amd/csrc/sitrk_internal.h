@@ -178,6 +178,14 @@ struct sitrk_ctx {
     int steps_since_sort = 0;
     bool sorted_once = false;
 
+    // deformation (sitrk_deform.hip): the positions of all buoys at sitrk_deform_mark, caller order, 16 B per buoy.  Allocated at
+    // the first mark, freed -- and the mark cancelled -- with the buoys (sitrk_set_buoys, sitrk_destroy)
+    sitrk::pt *deform_t0 = nullptr;
+    bool deform_marked = false;
+    int deform_jrec0 = 0;
+    hipEvent_t deform_ev[3] = {nullptr, nullptr, nullptr};   // around the scatter pass and the cell kernel of the last deform call
+    bool deform_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -194,6 +202,9 @@ int ensure_scratch(sitrk_ctx *h, size_t bytes);
 // sitrk_sample.hip reads a resident slot: the compute stream ordered behind an upload of `slot` still in flight on the copy
 // stream (sitrk.hip); *field = device address of field 0 u / 1 v / 2 siconc of the slot's slab
 int slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev);
+// sitrk_deform.hip: frees the snapshot of sitrk_deform_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timing
+// events too
+void deform_release(sitrk_ctx *h, bool destroy);
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

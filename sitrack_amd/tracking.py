@@ -225,6 +225,19 @@ class IceTracker:
             return dict(zip(names, out))
         return out[0] if single else tuple(out)
 
+    def deform_mark(self, jrec0):
+        """Snapshot every buoy's fp64 position on the device as the t0 of deform() (an extra the reference does not have;
+        sitrk_deform_mark); `jrec0` = the model record that will be stepped next."""
+        self.ctx.deform_mark(jrec0)
+
+    def deform(self, jrec1, cells):
+        """Right after the step of `jrec1`: deformation rates of the cells (nC, 3|4) of buoy indices between the mark and now,
+        computed from the device-resident positions (sitrk_deform_since_mark).  Same dict as sit.DeformCells; a cell is valid
+        where all its buoys are alive and were stepped at every record of the span."""
+        from .deformation import _as_dict
+        out, valid, _ = self.ctx.deform_since_mark(jrec1, cells)
+        return _as_dict(out, valid)
+
     def state(self):
         s = self.ctx.fetch()
         s["vJIt"] = s.pop("jiT").astype(np.int64)

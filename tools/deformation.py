@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
+2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
+
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [-o OUT.npz]
+
+CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
+positions of record K0 (Delaunay; needs scipy).  Records default to the first and the last; the elapsed time comes from
+`time`; validity from `mask` when the file has it, otherwise from the `_FillValue` of `y_pos`.  OUT (default: TRACKFILE
+with `_deform.npz` for its extension) holds div, shr, vor, tot [1/s], area0, area1 [km^2], valid, cells (the ids) and
+time0, time1.
+
+Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
+cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
+IceTracker.deform_mark() / .deform() take the rates there."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import sitrack_amd as sit                      # noqa: E402
+from sitrack_amd import ncio                   # noqa: E402
+
+CAVEAT = (' *** NOTE: the file holds positions as f4 km: at |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a\n'
+          '     10-km cell, the size of the strains of interest over a few hours; a running tracker takes the rates from its\n'
+          '     fp64 positions on the device (IceTracker.deform_mark / deform).')
+
+
+def _record(f, k, has_mask):
+    """(yx (nb,2) fp64, valid (nb,) bool) of record k"""
+    y = np.asarray(f.var('y_pos', k))
+    x = np.asarray(f.var('x_pos', k))
+    if has_mask:
+        ok = np.asarray(f.var('mask', k)) != 0
+    else:
+        ok = np.isfinite(y) & np.isfinite(x)
+        for a, nm in ((y, 'y_pos'), (x, 'x_pos')):
+            fv = f.fill_of(nm)
+            if fv is not None:
+                ok &= a != np.asarray(fv).astype(a.dtype)
+    return np.stack([y.astype(np.float64), x.astype(np.float64)], axis=1), ok
+
+
+def _auto_cells(yx, ok):
+    try:
+        from scipy.spatial import Delaunay
+    except ImportError:
+        sys.exit('ERROR: `-c auto` needs scipy (scipy.spatial.Delaunay), which cannot be imported: give the cells with -c CELLS.npy')
+    idx = np.flatnonzero(ok)
+    if len(idx) < 3:
+        sys.exit('ERROR: `-c auto`: fewer than 3 valid buoys at the first record')
+    return idx[Delaunay(yx[idx]).simplices].astype(np.int64)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='deformation rates of buoy cells from a trajectory file (MI355X build)')
+    ap.add_argument('-i', '--fin', required=True, help='trajectory file written by the tracker')
+    ap.add_argument('-c', '--cells', required=True, help='(nC,3|4) .npy array of id_buoy values, or `auto` (Delaunay, needs scipy)')
+    ap.add_argument('-k', '--k0', type=int, default=0, help='first record (default 0)')
+    ap.add_argument('-K', '--k1', type=int, default=-1, help='second record (default: the last)')
+    ap.add_argument('-o', '--fout', default=None, help='output file (default: <input>_deform.npz)')
+    ap.add_argument('--device', type=int, default=0)
+    a = ap.parse_args(argv)
+    ncio.chck4f(a.fin)
+    with ncio._Reader(a.fin) as f:
+        for cv in ('time', 'id_buoy', 'y_pos', 'x_pos'):
+            if not f.has_var(cv):
+                sys.exit('ERROR: no variable `%s` in %s' % (cv, a.fin))
+        nrec = f.dim('time')
+        ks = []
+        for opt, k in (('-k', a.k0), ('-K', a.k1)):
+            if not -nrec <= k < nrec:
+                sys.exit('ERROR: %s %d outside the %d records of %s' % (opt, k, nrec, a.fin))
+            ks.append(k % nrec)
+        k0, k1 = ks
+        vtime = np.asarray(f.var('time')).astype(np.int64)
+        T = float(vtime[k1] - vtime[k0])
+        if not T > 0.:
+            sys.exit('ERROR: record %d (time %d) is not later than record %d (time %d)' % (k1, vtime[k1], k0, vtime[k0]))
+        ids = np.asarray(f.var('id_buoy')).astype(np.int64)
+        has_mask = f.has_var('mask')
+        yx0, ok0 = _record(f, k0, has_mask)
+        yx1, ok1 = _record(f, k1, has_mask)
+    if a.cells == 'auto':
+        cols = _auto_cells(yx0, ok0 & ok1)
+        cell_ids = ids[cols]
+    else:
+        ncio.chck4f(a.cells)
+        cell_ids = np.load(a.cells, allow_pickle=False)
+        if cell_ids.ndim != 2 or cell_ids.shape[1] not in (3, 4) or cell_ids.dtype.kind not in 'iu':
+            sys.exit('ERROR: %s must hold an (nC,3) or (nC,4) integer array, got %s %s' % (a.cells, cell_ids.dtype, cell_ids.shape))
+        cell_ids = cell_ids.astype(np.int64)
+        order = np.argsort(ids, kind='stable')
+        pos = np.searchsorted(ids[order], cell_ids)
+        hit = np.take(ids[order], np.minimum(pos, len(ids) - 1)) == cell_ids if len(ids) else np.zeros(cell_ids.shape, dtype=bool)
+        if not hit.all():
+            sys.exit('ERROR: id_buoy %d of %s is not in %s' % (cell_ids[~hit][0], a.cells, a.fin))
+        cols = order[pos]
+    print(CAVEAT)
+    ctx = sit.Context(a.device)
+    try:
+        r = sit.DeformCells(yx0, yx1, cols, T, mask0=ok0, mask1=ok1, ctx=ctx)
+    finally:
+        ctx.close()
+    fout = a.fout or os.path.splitext(a.fin)[0] + '_deform.npz'
+    np.savez(fout, cells=cell_ids, time0=vtime[k0], time1=vtime[k1], **r)
+    print(' *** records %d -> %d (T = %g s): %d of %d cells valid -> %s' % (k0, k1, T, int(r['valid'].sum()), len(cell_ids), fout))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
