@@ -120,7 +120,8 @@ int sitrk_set_substeps(sitrk_t *h, int nsub);
  * fused kernel share an XCD (its L2); "step_block" (256/512/1024): workgroup size of the one-record kernel; "fuse" (1..32):
  * consecutive resident records advanced per launch by sitrk_run (loop interchange: the buoys are independent, each lane keeps
  * its buoy in registers across the records); "subsample_block" (256..4096, powers of two, default 1024): points per workgroup of
- * sitrk_subsample_cloud's resolve kernel;
+ * sitrk_subsample_cloud's resolve kernel; "coast_bin" (1..64, default 4): bin side of the next sitrk_coast_build, in quarters of
+ * sqrt(bounding-box area / segments);
  * "lanes" (1/2, default 2) / "lane_min_wg" (>= 1, default 7168): with lanes = 2, sitrk_run splits the cell-sorted buoys into two
  * contiguous lanes (cut at a multiple of 256 * 8 * xcd_group buoys) and queues each lane's fused launches on a stream of its own
  * -- lane 0 on the compute stream, lane 1 on the ingest stream, its first launch half as long, so that the lanes' launch
@@ -350,6 +351,57 @@ int sitrk_deform_since_mark(sitrk_t *h, int jrec1, int64_t nC, int nv, const int
 /* measurement: GPU time [ms] of the kernels of the last sitrk_deform_cells / sitrk_deform_since_mark on this handle, from HIP
  * events around them -- the pass over the points, the cell kernel; either pointer may be NULL */
 int sitrk_deform_kernel_ms(sitrk_t *h, float *points_ms, float *cells_ms);
+
+/* ---- distance to the model coastline ------------------------------------------
+ * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
+ * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell
+ * and a land T-cell, and the distance is exact geometry in the plane the tracker works in.  No parity claim is made against
+ * any other code; the contract below is this library's own.
+ * Coast segments.  T-cell (j,i) has the corners F(j-1,i-1), F(j-1,i), F(j,i), F(j,i-1) (tracking.vertices_of).  Edge k of it:
+ *     k = 0   shared by T(j,i) and T(j,i+1), defined for j >= 1 and i+1 < Ni:   a = F(j-1,i), b = F(j,i)
+ *     k = 1   shared by T(j,i) and T(j+1,i), defined for i >= 1 and j+1 < Nj:   a = F(j,i-1), b = F(j,i)
+ * An edge is a coast segment iff exactly one of its two cells has tmask == 0; the domain rim is no coast.  Its id is
+ * 2*(j*Ni+i) + k (int32: Nj*Ni <= 2^29).  A coast edge with a non-finite endpoint coordinate is dropped and counted.
+ * Distance of a point p to segment (a,b), [y,x] order, plane km, fp64, one rounded operation per symbol, no fused
+ * multiply-add:
+ *     ey = yb - ya ; ex = xb - xa ; py = yp - ya ; px = xp - xa
+ *     len2 = ey*ey + ex*ex ; dot = py*ey + px*ex
+ *     t = (len2 > 0) ? dot / len2 : 0 ; t = t < 0 ? 0 : (t > 1 ? 1 : t)
+ *     cy = py - t*ey ; cx = px - t*ex ; d2 = cy*cy + cx*cx
+ * d2min[p] = the minimum of d2 over ALL coast segments, seg[p] = the lowest id that attains it, dist[p] = sqrt(d2min[p]).
+ * The index behind the queries only prunes with conservative bounds: what is reported is this minimum, which does not
+ * depend on any order, so d2min and seg are reproducible bit for bit (sqrt is the device's).
+ * rmax_km: finite and > 0 bounds the search: with r2 = rmax_km*rmax_km (rounded), a point with d2min > r2 reports
+ * dist = +inf, seg = -1, every other point the unbounded answer.  rmax_km <= 0 or +inf: unbounded.  NaN: SITRK_EINVAL.
+ * No coast (every cell sea, or every cell land): every point reports +inf, -1, and the calls return SITRK_OK.
+ * A query with a non-finite coordinate reports NaN, -1 (when there is a coast) and is no error.
+ * Units: kilometres in the polar-stereographic plane of sitrk_geo2cart, true at 70 N.  Against distances on the sphere the
+ * plane's scale is (1 + sin 70) / (1 + sin lat): about +4 % at 60 N, -3 % at the pole.  It is not corrected for.
+ *
+ * sitrk_coast_build: extracts the segments on the device and builds the search index over them, from the host arrays Yf, Xf
+ * (Nj,Ni) fp64 km and tmask (Nj,Ni) int8 -- or, with all three NULL, from the device copy of the grid of sitrk_set_grid
+ * (Nj, Ni then 0 or that grid's; SITRK_EINVAL without a grid).  Segments and results are bit-identical either way.  The
+ * index lives in device buffers of its own (68 bytes per segment + 4 per bin; not the transient scratch), is replaced by the
+ * next build, freed by sitrk_destroy, and, when it was built from the context's grid, dropped by a later sitrk_set_grid.
+ * *nseg / *ndropped (either may be NULL): coast segments kept / dropped for a non-finite endpoint.  The bin side is read from
+ * the knob "coast_bin" (1..64, default 4: quarters of sqrt(bounding-box area / nseg)) at build time; results never depend
+ * on it.  Needs Nj, Ni >= 2 and Nj*Ni <= 2^29. */
+int sitrk_coast_build(sitrk_t *h, int Nj, int Ni, const double *Yf, const double *Xf, const int8_t *tmask, int64_t *nseg,
+                      int64_t *ndropped);
+/* Probe for tests and plots: *n = number of segments; when cap >= *n, ids (n) and ab (n,2,2) = [a|b][y,x] in id order (either
+ * may be NULL); with cap < *n only *n is written. */
+int sitrk_coast_segments(sitrk_t *h, int64_t cap, int32_t *ids, double *ab, int64_t *n);
+/* dist (n) fp64 km and seg (n) int32 (may be NULL) of the host points yx (n,2) [y,x] km.  Synchronous on the handle's stream;
+ * n == 0 is valid.  The points and results pass through the transient scratch only: the grid, buoys and records of a tracker
+ * on the same handle are left as they were.  SITRK_EINVAL without an index. */
+int sitrk_coast_dist(sitrk_t *h, int64_t n, const double *yx, double rmax_km, double *dist, int32_t *seg);
+/* The same for every buoy of sitrk_set_buoys, alive or not, at its current fp64 position on the device, in the caller's
+ * order: nothing but the result leaves the device; buoys, records and stepping state are only read.  SITRK_EINVAL without
+ * buoys or without an index. */
+int sitrk_coast_dist_buoys(sitrk_t *h, double rmax_km, double *dist, int32_t *seg);
+/* measurement: GPU time [ms] of the query kernel of the last sitrk_coast_dist / sitrk_coast_dist_buoys on this handle, from
+ * HIP events around it */
+int sitrk_coast_kernel_ms(sitrk_t *h, float *query_ms);
 
 /* ---- locate / seeding ----------------------------------------------------
  * FindContainingCell (sitrack/locate.py:280-330) for n points: from the guess

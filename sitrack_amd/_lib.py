@@ -75,6 +75,11 @@ _SIGNATURES = {
     "sitrk_deform_mark": (_int, [_vp, _int]),
     "sitrk_deform_since_mark": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_deform_kernel_ms": (_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
+    "sitrk_coast_dist_buoys": (_int, [_vp, _dbl, _vp, _vp]),
+    "sitrk_coast_kernel_ms": (_int, [_vp, C.POINTER(C.c_float)]),
     "sitrk_count_alive": (_int, [_vp, C.POINTER(_i64)]),
     "sitrk_find_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "sitrk_seed_init": (_int, [_vp, _i64] + [_vp] * 9),
@@ -584,6 +589,64 @@ class Context:
         a, b = C.c_float(0), C.c_float(0)
         self._chk(self._L.sitrk_deform_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- distance to the model coastline (sitrk_coast_*)
+    def coast_build(self, Yf=None, Xf=None, tmask=None):
+        """sitrk_coast_build: (nseg, ndropped).  Yf, Xf (Nj,Ni) km and tmask (Nj,Ni), or none of them: the grid of set_grid().
+        The bin side is the knob set_tuning(coast_bin=...) at this call."""
+        given = [a is not None for a in (Yf, Xf, tmask)]
+        nseg, ndrop = _i64(0), _i64(0)
+        if not any(given):
+            self._chk(self._L.sitrk_coast_build(self._h, 0, 0, None, None, None, C.byref(nseg), C.byref(ndrop)))
+        else:
+            if not all(given):
+                raise ValueError("coast_build: Yf, Xf and tmask go together")
+            Yf = as_c(Yf, np.float64)
+            if Yf.ndim != 2:
+                raise ValueError("coast_build: Yf must be (Nj,Ni)")
+            Nj, Ni = Yf.shape
+            Xf = as_c(Xf, np.float64, (Nj, Ni), "Xf")
+            tm = as_c(tmask, np.int8, (Nj, Ni), "tmask")
+            self._chk(self._L.sitrk_coast_build(self._h, Nj, Ni, _ptr(Yf), _ptr(Xf), _ptr(tm), C.byref(nseg), C.byref(ndrop)))
+        return nseg.value, ndrop.value
+
+    def coast_segments(self):
+        """sitrk_coast_segments: (ids (n,) int32, ab (n,2,2) = [a|b][y,x] km) in id order"""
+        n = _i64(0)
+        self._chk(self._L.sitrk_coast_segments(self._h, 0, None, None, C.byref(n)))
+        ids = np.empty(n.value, dtype=np.int32)
+        ab = np.empty((n.value, 2, 2), dtype=np.float64)
+        if n.value:
+            self._chk(self._L.sitrk_coast_segments(self._h, n.value, _ptr(ids), _ptr(ab), C.byref(n)))
+        return ids, ab
+
+    @staticmethod
+    def _coast_rmax(rmax_km):
+        return 0.0 if rmax_km is None else float(rmax_km)
+
+    def coast_dist(self, yx, rmax_km=None, want_seg=True):
+        """sitrk_coast_dist: (dist (n,) km, seg (n,) int32 or None) of the points yx (n,2) [y,x] km; rmax_km None = unbounded"""
+        yx = as_c(yx, np.float64)
+        if yx.ndim != 2 or yx.shape[1] != 2:
+            raise ValueError("coast_dist: yx must be (n,2)")
+        n = yx.shape[0]
+        dist = np.empty(n, dtype=np.float64)
+        seg = np.empty(n, dtype=np.int32) if want_seg else None
+        self._chk(self._L.sitrk_coast_dist(self._h, n, _ptr(yx), self._coast_rmax(rmax_km), _ptr(dist), _ptr(seg)))
+        return dist, seg
+
+    def coast_dist_buoys(self, rmax_km=None, want_seg=True):
+        """sitrk_coast_dist_buoys: the same for every buoy of set_buoys() at its current position, in the caller's order"""
+        dist = np.empty(self.nP, dtype=np.float64)
+        seg = np.empty(self.nP, dtype=np.int32) if want_seg else None
+        self._chk(self._L.sitrk_coast_dist_buoys(self._h, self._coast_rmax(rmax_km), _ptr(dist), _ptr(seg)))
+        return dist, seg
+
+    def coast_kernel_ms(self):
+        """GPU time [ms] of the query kernel of the last coast_dist / coast_dist_buoys (sitrk_coast_kernel_ms)"""
+        a = C.c_float(0)
+        self._chk(self._L.sitrk_coast_kernel_ms(self._h, C.byref(a)))
+        return a.value
 
     def count_alive(self):
         n = _i64(0)

@@ -125,6 +125,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_buoys(h);
     deform_release(h, true);
+    coast_release(h, false, true);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
@@ -179,6 +180,7 @@ SITRK_API int sitrk_set_grid(sitrk_t *h, int Nj, int Ni, const double *Yf, const
     h->geo = nullptr; h->geoF = nullptr; h->orient = nullptr; h->tmask = nullptr;
     free_records(h);
     free_buoys(h);
+    coast_release(h, true, false);      // a coast index built from the previous grid is gone with it
     const size_t n = (size_t)Nj * Ni;
     HIPCHK(dev_alloc(&h->geo, n));
     HIPCHK(dev_alloc(&h->geoF, n));
@@ -290,6 +292,11 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
         if (value < 256 || value > 256 * kSubMaxPpt || (value & (value - 1)))
             return fail(h, SITRK_EINVAL, "sitrk_set_tuning: subsample_block must be a power of two in 256..%d", 256 * kSubMaxPpt);
         h->subsample_block = value;
+        return SITRK_OK;
+    }
+    else if (!strcmp(knob, "coast_bin")) {           // bin side of the next sitrk_coast_build
+        if (value < 1 || value > 64) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: coast_bin must be 1..64");
+        h->coast_bin = value;
         return SITRK_OK;
     }
     else if (!strcmp(knob, "locate_bruteforce")) bit = TUNE_LOCATE_BRUTEFORCE;

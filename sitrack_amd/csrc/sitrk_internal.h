@@ -46,6 +46,31 @@ struct OvGrid {
     uint32_t ncells = 1;
 };
 
+// Distance to the model coastline (sitrk_coast.hip): the coast segments in id order (what sitrk_coast_segments returns) and the
+// same segments ordered by the square bin of their midpoint, with the offset of every bin's first segment.  Device buffers of their
+// own: a tracker queries again and again, so none of this lives in the transient scratch.
+struct CoastIndex {
+    int64_t nseg = 0;
+    const pt *seg = nullptr;            // (2 nseg) endpoints a, b in BIN order, id order inside a bin
+    const int32_t *sid = nullptr;       // (nseg) segment ids in bin order
+    const int32_t *start = nullptr;     // (ny*nx + 1) first segment of bin by*nx + bx; a run of bins of one row is one run of segments
+    double y0 = 0.0, x0 = 0.0, h = 1.0, inv_h = 1.0;   // bins of side h from (y0, x0), ny x nx of them
+    int ny = 1, nx = 1;
+    double pad = 0.0;                   // >= half the longest segment, plus what the index's own rounding can amount to [km]
+};
+struct CoastState {
+    bool built = false;
+    bool from_grid = false;             // built from the context's grid: a later sitrk_set_grid invalidates it
+    int64_t ndropped = 0;
+    int32_t *ids = nullptr;             // (nseg) id order
+    pt *ab = nullptr;                   // (2 nseg) id order
+    pt *seg = nullptr;                  // the arrays of CoastIndex
+    int32_t *sid = nullptr, *start = nullptr;
+    CoastIndex ix;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the query kernel of the last distance call
+    bool timed = false;
+};
+
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
 // perm[s] = index of slot s in the caller's order.
 struct BuoyState {
@@ -118,6 +143,7 @@ struct sitrk_ctx {
                                         // sv_stream and half a launch behind lane 0 (1 = one stream, one launch at a time)
     int lane_min_wg = 7168;             // ... where the shorter lane keeps that many workgroups (4 rounds of 256 CUs x 7 workgroups)
     hipEvent_t lane_fork = nullptr, lane_join = nullptr;
+    int coast_bin = 4;                  // sitrk_coast_build: bin side in quarters of sqrt(bounding-box area / segments), 1..64 (never changes results)
     int subsample_block = 1024;         // sitrk_subsample_cloud: points per workgroup of its resolve kernel (never changes results)
     int fill_threads = 8;               // host threads copying a pushed record (>= 8 MB) into the pinned staging (2 / 4 / 8: 26 / 36 / 47 GB/s on the box rows of C3)
 
@@ -186,6 +212,8 @@ struct sitrk_ctx {
     hipEvent_t deform_ev[3] = {nullptr, nullptr, nullptr};   // around the scatter pass and the cell kernel of the last deform call
     bool deform_timed = false;
 
+    sitrk::CoastState coast;            // distance to the coastline (sitrk_coast.hip)
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -205,6 +233,9 @@ int slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev);
 // sitrk_deform.hip: frees the snapshot of sitrk_deform_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timing
 // events too
 void deform_release(sitrk_ctx *h, bool destroy);
+// sitrk_coast.hip: frees the coast index (sitrk_destroy: the timing events too); grid_changed = only an index that was built from
+// the context's grid (sitrk_set_grid)
+void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy);
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

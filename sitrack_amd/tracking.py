@@ -238,6 +238,16 @@ class IceTracker:
         out, valid, _ = self.ctx.deform_since_mark(jrec1, cells)
         return _as_dict(out, valid)
 
+    def dist2coast(self, rmax_km=None, return_seg=False):
+        """Distance [km, polar-stereographic plane] of every buoy, alive or not, to the coastline of the tracker's own mesh, from
+        the device-resident positions, in the caller's order (an extra the reference does not have; sitrk_coast_dist_buoys).
+        The index is built from the tracker's grid on first use.  `rmax_km`: buoys further away report +inf."""
+        if not getattr(self, "_coast_built", False):
+            self.ctx.coast_build()
+            self._coast_built = True
+        dist, seg = self.ctx.coast_dist_buoys(rmax_km, want_seg=return_seg)
+        return (dist, seg) if return_seg else dist
+
     def state(self):
         s = self.ctx.fetch()
         s["vJIt"] = s.pop("jiT").astype(np.int64)

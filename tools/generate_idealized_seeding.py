@@ -8,7 +8,12 @@ ncio.py:131-197.  `--lsidfex 1` seeds from a text file `id lon lat` (reference t
 `SubSampCloud` (greedy sparsification at radius rd_ss, on the GPU) and the kept rows keep their IDs, lat/lon and y/x;
 C = 10 and 20 add the mesh's F-points to the T-seeds first.  rd_ss = 6.0 / 14.6 / 34.5 / 74.75 / 156. / 315.6 km for
 C = 10 / 20 / 40 / 80 / 160 / 320.  C = 640 also needs the reference's dist-to-coast file and mojito's `MaskCoastal`, and is
-refused; so is any other value.  A SIDFEx cloud is coarsened the same way, without F-points."""
+refused; so is any other value.  A SIDFEx cloud is coarsened the same way, without F-points.
+
+`--min-dist-land <KM>` (extra) is the coastal cleaning on its own, against the model's own coastline instead of a dist-to-coast
+raster: after the seeding and before the coarsening (the reference's order), seeds closer than KM km to the nearest edge
+between a sea and a land T-cell of the mesh file are removed (`Context.coast_build` on its `tmask` and F-points, then
+`MaskCoastal`; distances in the polar-stereographic plane).  It combines with any `-C`; the file name gains `_dl<KM>km`."""
 import argparse
 import os
 import sys
@@ -36,15 +41,25 @@ def main(argv=None):
     ap.add_argument('-f', '--fmsk', default=None, help='mask (on SI3 model domain) to control seeding region')
     ap.add_argument('-C', '--crsn', type=int, default=0, help='coarsening in km: 10, 20, 40, 80, 160 or 320')
     ap.add_argument('-N', '--ncnf', default='NANUK4', help='name of the horizontak NEMO config used')
+    ap.add_argument('--min-dist-land', type=float, default=None, metavar='KM',
+                    help='extra: remove the seeds closer than KM km to the coastline of the mesh (needs `-m`)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
     rd_ss, add_f = coarsening(a.crsn)
+    if a.min_dist_land is not None:
+        if not (np.isfinite(a.min_dist_land) and a.min_dist_land > 0.):
+            raise SystemExit('ERROR: `--min-dist-land` must be a finite distance > 0 km (got %r)' % a.min_dist_land)
+        if not a.fmmm:
+            raise SystemExit('ERROR: `--min-dist-land` needs the MeshMask file (`-m`): the coastline is the mesh\'s own')
     if a.ihss < 1 or a.ihss > 20:
         raise SystemExit('ERROR: chosen horizontal subsampling makes no sense iHSS=%d' % a.ihss)
     seeding_type = 'sidfex' if a.lsidfex == 1 else ('nemoTsi3' if a.fsi3 else 'nemoTmm')
     ctx = sit.Context(a.device)
     if seeding_type == 'sidfex':
         XseedGC, zIDs = SidfexSeeding(a.sidfex_file)
+        if a.min_dist_land is not None:
+            imaskt, _, _, _, _, xYf, xXf, _ = ncio.GetModelGrid(a.fmmm, ctx=ctx)
+            ctx.coast_build(xYf, xXf, imaskt)
         return write_seeding(ctx, a, seeding_type, XseedGC, zIDs, rd_ss=rd_ss)
     if not a.fmmm:
         raise SystemExit('ERROR: you have to specify a MeshMask file with `-m`')
@@ -71,6 +86,8 @@ def main(argv=None):
     XseedGC, XseedYX = nemoSeed(imaskt, xlatT, xlonT, xIC, khss=a.ihss, fmsk_rstrct=FSmask, platF=xlatF, plonF=xlonF,
                                 ctx=ctx, return_yx=True)
     zIDs = np.arange(1, XseedGC.shape[0] + 1, dtype=int)
+    if a.min_dist_land is not None:
+        ctx.coast_build(xYf, xXf, imaskt)
     return write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX, rd_ss)
 
 
@@ -97,6 +114,13 @@ def write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX=None, rd_ss=None)
         XseedYX = sit.Geo2CartNPSkm1D(XseedGC, ctx=ctx)
     cdate = datetime.fromtimestamp(t0, timezone.utc).strftime("%Y%m%d_%H")
     cextra = '_HSS' + str(a.ihss) if a.ihss > 1 else ''
+    if a.min_dist_land is not None:
+        # coastal cleaning (reference :276-306), on the coast index the caller built from the mesh
+        nP0 = XseedGC.shape[0]
+        mask = sit.MaskCoastal(XseedGC, rMinDistLand=a.min_dist_land, ctx=ctx)
+        print(' * Need to remove ' + str(nP0 - np.sum(mask)) + ' points because too close to land! (' + str(a.min_dist_land) + 'km)')
+        (idxKeep,) = np.where(mask == 1)
+        XseedGC, XseedYX, zIDs = XseedGC[idxKeep, :], XseedYX[idxKeep, :], np.asarray(zIDs)[idxKeep]
     if rd_ss is not None:
         nP0 = XseedGC.shape[0]
         print(' *** Applying spatial sub-sampling with radius: %.2fkm' % rd_ss)
@@ -105,6 +129,8 @@ def write_seeding(ctx, a, seeding_type, XseedGC, zIDs, XseedYX=None, rd_ss=None)
         zIDs = np.asarray(zIDs)[idxKeep]
         print('    ==> nP, nPss = %d %d' % (nP0, len(idxKeep)))
         cextra = '_%dkm' % a.crsn
+    if a.min_dist_land is not None:
+        cextra += '_dl%gkm' % a.min_dist_land
     nP = XseedGC.shape[0]
     foutnc = './nc/sitrack_seeding_' + seeding_type + '_' + cdate + cextra + '.nc'
     ncio.ncSaveCloudBuoys(foutnc, np.array([t0], dtype='i4'), zIDs, XseedYX[None, :, 0], XseedYX[None, :, 1],
