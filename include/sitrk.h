@@ -259,6 +259,40 @@ int sitrk_launch_stats(sitrk_t *h, int reset, int64_t *fused_launches, int64_t *
  * launches the two lanes queued for them.  Both stay 0 with lanes = 1.  Any pointer may be NULL. */
 int sitrk_lane_stats(sitrk_t *h, int reset, int64_t *lane_segments, int64_t *lane_launches);
 
+/* ---- sub-stepped advection with the fields interpolated in time -------------------
+ * An EXTRA the reference does not have.  sitrk_run advances every sub-step of a record with that record's u, v: a velocity
+ * that is piecewise constant in time.  sitrk_run_tlerp steps the same records jrec0 + k, k < nsteps, from the same slots
+ * (slot0 + k) % nslots with the current nsub = n >= 1 and dt = rdt / n (the same single rounded division), but blends the
+ * velocity candidates of every sub-step linearly in time between the record and its neighbour.
+ * `phase` in [0,1] = the fraction of its step interval at which a record is valid: 0.5 for time means centred on the interval
+ * (what NEMO writes), 0 for snapshots at its start.  For sub-step s of a record, in fp64, one rounded operation per symbol,
+ * no FMA:
+ *     tau   = (double)(2s+1) / (double)(2n)
+ *     theta = tau - phase
+ *     theta < 0 : the partner is record jrec-1 in slot (slot-1+nslots) % nslots, w = -theta
+ *     theta > 0 : the partner is record jrec+1 in slot (slot+1) % nslots,        w =  theta
+ *     theta == 0: no partner
+ * and no partner either for the record before k == 0 unless have_prev, nor for the record behind k == nsteps-1 unless
+ * have_next.  Each of the four candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] of the buoy's current host cell becomes
+ *     F = (double)f_cur + w * ((double)f_partner - (double)f_cur)
+ * and F = (double)f_cur exactly where there is no partner (no arithmetic: a non-finite value of an unused partner cannot leak
+ * in).  The sub-step is then the sub-step of sitrk_set_substeps with F in place of the record's values: uv_strategy 0 / 1 / 2
+ * (the pick of strategy 1 is geometric, so pick and blend commute), P + (F*dt)/1000., inside test, crossing, re-hosting.
+ * Never interpolated: the Survive bytes (always record jrec's own), the record-window gate (jrec) and kill_rec.
+ * Equivalently: the reference loop body run n times per record with rdt/n, the blended fields u_s, v_s and siconc of record
+ * jrec.  Bit for bit: with no partner anywhere the result is sitrk_run's with the same nsub; so it is with phase = 0.5, n = 1.
+ * sitrk_fetch_record, sitrk_sample_*, sitrk_deform_* and sitrk_coast_dist_buoys behave after it exactly as after sitrk_run.
+ * Host rules: nsteps + (have_prev?1:0) + (have_next?1:0) <= nslots.  A partner slot that the sub-steps read (a phase can
+ * leave one side unused: phase 0 never looks back) is checked like the slot of the record it serves -- the same age, hence
+ * the same D of the row-band / box rule: a box that holds record jrec-1 for its own step is nsub cells too small as a partner
+ * of jrec -- made ready like it, and counts as read by the launch: a later upload into it waits for the kernel.  The periodic
+ * re-sort is honoured as in sitrk_run; launches are counted as fused launches / fused records; one lane only
+ * (sitrk_lane_stats does not move).  One call and record-by-record calls give the same bits.
+ * SITRK_EINVAL: phase outside [0,1] (NaN included), nsteps < 0, a bad slot, missing buoys or records, too few slots, and a buoy
+ * set to which the fused kernels do not apply (buoys in the two outermost rows/columns, geometry beyond 2^32 bytes: the
+ * one-record kernel cannot blend); the handle stays usable. */
+int sitrk_run_tlerp(sitrk_t *h, int slot0, int jrec0, int nsteps, double phase, int have_prev, int have_next);
+
 /* Current state in the caller's buoy order (any pointer may be NULL):
  * yx (nP,2) current position; jiT (nP,2) = vJIt; alive (nP) = iAlive;
  * kill_rec (nP) = model record at which the buoy was killed, -1 if alive. */

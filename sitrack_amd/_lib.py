@@ -67,6 +67,7 @@ _SIGNATURES = {
     "sitrk_set_resort": (_int, [_vp, _int]),
     "sitrk_step": (_int, [_vp, _int, _int]),
     "sitrk_run": (_int, [_vp, _int, _int, _int]),
+    "sitrk_run_tlerp": (_int, [_vp, _int, _int, _int, _dbl, _int, _int]),
     "sitrk_fetch": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "sitrk_fetch_record": (_int, [_vp, _int, _vp, _vp, _vp]),
     "sitrk_sample_slot": (_int, [_vp, _int, _int, _int, _int, _vp]),
@@ -466,6 +467,13 @@ class Context:
 
     def run(self, slot0, jrec0, nsteps):
         self._chk(self._L.sitrk_run(self._h, int(slot0), int(jrec0), int(nsteps)))
+
+    def run_tlerp(self, slot0, jrec0, nsteps, phase, have_prev=False, have_next=False):
+        """sitrk_run with the velocities of every sub-step blended linearly in time between consecutive records
+        (sitrk_run_tlerp): `phase` in [0,1] = where in its step interval a record is valid (0.5 time means, 0 snapshots at the
+        start); have_prev / have_next: the slots in front of slot0 / behind the last one hold records jrec0-1 / jrec0+nsteps."""
+        self._chk(self._L.sitrk_run_tlerp(self._h, int(slot0), int(jrec0), int(nsteps), float(phase), int(bool(have_prev)),
+                                          int(bool(have_next))))
 
     def fetch(self, want=("yx", "jiT", "alive", "kill_rec")):
         nP = self.nP

@@ -127,7 +127,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     deform_release(h, true);
     coast_release(h, false, true);
     free_records(h);
-    dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter);
+    dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
     if (h->lane_fork) (void)hipEventDestroy(h->lane_fork);
     if (h->lane_join) (void)hipEventDestroy(h->lane_join);
@@ -1333,6 +1333,112 @@ SITRK_API int sitrk_run(sitrk_t *h, int slot0, int jrec0, int nsteps)
         }
         // m consecutive records, all resident in distinct slots, in one launch
         RCCHK(launch_records(h, (slot0 + k) % h->nslots, jrec0 + k, m));
+        k += m;
+    }
+    return SITRK_OK;
+}
+
+// --------------------------------------------------------------------------- fields interpolated in time
+// theta[s] of every sub-step in the contract's order (include/sitrk.h): tau = (2s+1)/(2n), theta = tau - phase, one rounded
+// fp64 operation each.  The device copy is refilled only when (nsub, phase) change; launches that read the old values are in
+// front of the copy on the compute stream.
+static int tlerp_table(sitrk_ctx *h, double phase, bool *uses_prev, bool *uses_next)
+{
+    const int n = h->nsub;
+    double th[1024];
+    for (int s = 0; s < n; s++) {
+        const double tau = (double)(2 * s + 1) / (double)(2 * n);
+        th[s] = tau - phase;
+    }
+    *uses_prev = th[0] < 0.;                             // theta grows with s
+    *uses_next = th[n - 1] > 0.;
+    if (h->tlerp_theta && h->tlerp_nsub == n && h->tlerp_phase == phase) return SITRK_OK;
+    if (!h->tlerp_theta) HIPCHK(dev_alloc(&h->tlerp_theta, (size_t)1024));
+    h->tlerp_nsub = 0;
+    HIPCHK(upload(h, h->tlerp_theta, th, (size_t)n));
+    HIPCHK(hipStreamSynchronize(h->stream));             // `th` must outlive the copy
+    h->tlerp_nsub = n; h->tlerp_phase = phase;
+    return SITRK_OK;
+}
+
+// records jrec0 .. jrec0+m-1 from slots (slot_first + r) % nslots in ONE launch of advect_tlerp_kernel.  prev / next: the
+// slot in front of the first / behind the last one holds the record before / behind them and is read as their partner.
+static int launch_tlerp(sitrk_ctx *h, int slot_first, int jrec0, int m, bool prev, bool next)
+{
+    BuoyState &s = h->st[h->cur];
+    const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
+    const double dt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;        // dt_sub: one rounded division, as launch_records
+    TlerpArgs ta;
+    ta.s.nP = h->nP; ta.s.tune = h->tune; ta.s.Nj = h->Nj; ta.s.Ni = h->Ni; ta.s.jrec = jrec0;
+    ta.s.rdt = dt; ta.s.rmin_conc = h->rmin_conc; ta.s.eps_mg = h->eps_mg; ta.s.geo = h->geo; ta.s.orient = h->orient; ta.s.kill = nullptr; ta.s.u = ta.s.v = nullptr;
+    ta.s.pos = s.pos; ta.s.cell = s.cell; ta.s.kill_rec = s.kill_rec; ta.s.win = s.win;
+    ta.nrec = m; ta.nsub = h->nsub;
+    ta.theta = h->tlerp_theta;
+    make_cross_tab(h->Ni, ta.tab, ta.dji);
+    ta.geoF = h->geoF;
+    ta.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
+    ta.patch_margin = h->patch_margin;
+    ta.xcd_group = h->xcd_group;
+    for (int q = 0; q < kMaxFuse + 2; q++) ta.u[q] = ta.v[q] = nullptr;
+    for (int q = 0; q < kMaxFuse; q++) ta.kill9[q] = nullptr;
+    int used[kMaxFuse + 2], nused = 0;
+    // q = -1 / m: the partner slots, checked like the record they serve (same age, same D) and made ready like any slot read
+    for (int q = -1; q <= m; q++) {
+        if ((q < 0 && !prev) || (q == m && !next)) continue;
+        const int slot = ((slot_first + q) % h->nslots + h->nslots) % h->nslots;
+        used[nused++] = slot;                            // the launch reads the partners too: uploads into them wait for it
+        RCCHK(check_band(h, slot, std::min(std::max(q, 0), m - 1)));
+        RCCHK(slot_make_ready(h, slot));
+        const char *slab = slab_of(h, slot);
+        ta.u[q + 1] = slab; ta.v[q + 1] = slab + n * es;
+        if (q >= 0 && q < m) ta.kill9[q] = h->kill9 + (size_t)slot * n;
+    }
+    const dim3 grid(nblocks(h->nP, kRunBlock)), block(kRunBlock);
+    const size_t lds = kRunLdsFixed + (size_t)ta.patch_cells * sizeof(pt);
+    pick_kernel(h, window_test_needed(h, jrec0, m), [&](auto ft, auto uvs, auto win) {
+        using FT = typename decltype(ft)::type;
+        constexpr int UVS = decltype(uvs)::value;
+        constexpr bool WIN = decltype(win)::value;
+        hipLaunchKernelGGL((advect_tlerp_kernel<FT, UVS, WIN>), grid, block, lds, h->stream, ta);
+    });
+    HIPCHK(hipGetLastError());
+    RCCHK(launch_mark(h, used, nused));
+    h->n_fused_launches++;
+    h->n_fused_records += m;
+    records_stepped(h, m);
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_run_tlerp(sitrk_t *h, int slot0, int jrec0, int nsteps, double phase, int have_prev, int have_next)
+{
+    NEED(h, "null handle");
+    NEED(nsteps >= 0, "sitrk_run_tlerp: nsteps must be >= 0");
+    NEED(phase >= 0.0 && phase <= 1.0, "sitrk_run_tlerp: phase must be in [0,1]");          // (a NaN fails both)
+    NEED(h->nslots > 0, "sitrk_run_tlerp: call sitrk_alloc_records first");
+    NEED(slot0 >= 0 && slot0 < h->nslots, "sitrk_run_tlerp: slot0 out of range");
+    NEED(h->st[0].pos, "sitrk_run_tlerp: call sitrk_set_buoys first");
+    if ((int64_t)nsteps + (have_prev ? 1 : 0) + (have_next ? 1 : 0) > h->nslots)
+        return fail(h, SITRK_EINVAL, "sitrk_run_tlerp: %d records and %d partner record(s) do not fit %d slots", nsteps,
+                    (have_prev ? 1 : 0) + (have_next ? 1 : 0), h->nslots);
+    if (h->nP == 0 || nsteps == 0) return SITRK_OK;
+    if (!fused_ok(h))
+        return fail(h, SITRK_EINVAL, "sitrk_run_tlerp: the fused kernels do not apply to this buoy set (buoys in the two outermost "
+                    "rows/columns, or a mesh beyond 2^32 bytes of geometry) and the one-record kernel cannot blend records");
+    HIPCHK(hipSetDevice(h->device));
+    bool uses_prev = false, uses_next = false;
+    RCCHK(tlerp_table(h, phase, &uses_prev, &uses_next));
+    // a launch holds its records and up to two partners in distinct slots
+    const int fuse = std::max(1, std::min(std::min(h->fuse, kMaxFuse), h->nslots - 2));
+    int k = 0;
+    while (k < nsteps) {
+        if (h->resort_every > 0 && h->steps_since_sort >= h->resort_every) {
+            RCCHK(sitrk_sort_buoys(h));
+        }
+        int m = std::min(fuse, nsteps - k);
+        if (h->resort_every > 0) m = std::max(1, std::min(m, h->resort_every - h->steps_since_sort));
+        // partners the sub-steps really read: the record in front of k exists inside the call, or in front of it if the caller says so
+        const bool prev = uses_prev && (k > 0 || have_prev), next = uses_next && (k + m < nsteps || have_next);
+        RCCHK(launch_tlerp(h, (slot0 + k) % h->nslots, jrec0 + k, m, prev, next));
         k += m;
     }
     return SITRK_OK;

@@ -187,6 +187,11 @@ struct sitrk_ctx {
     // launch accounting (sitrk_launch_stats)
     long long n_fused_launches = 0, n_fused_records = 0, n_step_launches = 0;
     long long n_lane_segments = 0, n_lane_launches = 0;     // (sitrk_lane_stats)
+    // sitrk_run_tlerp: theta[s] = (2s+1)/(2 nsub) - phase of every sub-step, on the device (1024 doubles, allocated at the first
+    // call), and the (nsub, phase) it was filled for
+    double *tlerp_theta = nullptr;
+    int tlerp_nsub = 0;
+    double tlerp_phase = -1.0;
 
     // buoys
     int64_t nP = 0;

@@ -1260,6 +1260,239 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
 }
 
 // ---------------------------------------------------------------------------
+// Sub-stepped advection with the velocities interpolated linearly in time between consecutive records (sitrk_run_tlerp):
+// advect_substep_kernel with every velocity candidate of sub-step s replaced by
+//     F = (double)f_cur + w * ((double)f_partner - (double)f_cur)            (three rounded fp64 operations, no FMA)
+// where theta = ta.theta[s] (filled by the host: (2s+1)/(2 nsub) - phase), w = |theta| and the partner is the record before
+// (theta < 0) or behind (theta > 0) the one being stepped; no partner (theta == 0, or a record outside what the caller
+// holds: a null pointer): F = (double)f_cur, no arithmetic.  Everything else -- pick, Euler update in the general fp64 form,
+// inside test, crossing, Survive bytes (always the record's own), record window, kill_rec -- is the sub-step kernel's.
+// A lane holds the current record's four candidates and ONE partner's four: theta grows with s, so a record has at most
+// two phases (partner before, then partner behind); the partner's candidates are loaded at the top of a record, at the phase
+// change (wave-uniform) and after a crossing (per lane), never per sub-step.
+// ---------------------------------------------------------------------------
+struct TlerpArgs {
+    StepArgs s;                         // s.u/s.v/s.kill unused; s.jrec = first record; s.rdt = dt_sub
+    int nrec, nsub;
+    const void *u[kMaxFuse + 2], *v[kMaxFuse + 2];   // [r + 1]: record r; [0] / [nrec + 1]: the record before the first / behind the
+                                                     // last one of the launch, null where the caller holds none
+    const uint8_t *kill9[kMaxFuse];     // the neighbours' Survive bits of record r
+    const double *theta;                // nsub values (device memory): signed time offset of sub-step s from its record's validity time
+    const pt *geoF;
+    CrossTab tab;
+    int dji[4][7][2];
+    int patch_cells, patch_margin;
+    int xcd_group;
+};
+
+// registers and occupancy as built: DESIGN.md 3.11
+static constexpr int kTlerpWaves = 5;
+static constexpr int kTlerpWavesWide = 4;
+
+template <typename FT, int UVS, bool WINDOW>
+__global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWavesWide : kTlerpWaves) void advect_tlerp_kernel(TlerpArgs ta)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int *s_tab = (int *)smem;
+    int *s_tabL = s_tab + 64;
+    int *s_box = s_tabL + 64;
+    const StepArgs &a = ta.s;
+    const unsigned blk = (a.tune & TUNE_XCD_REMAP) ? xcd_remap(blockIdx.x, gridDim.x)
+                         : (ta.xcd_group > 1 ? xcd_group(blockIdx.x, gridDim.x, (unsigned)ta.xcd_group) : blockIdx.x);
+    const int64_t p = (int64_t)blk * kRunBlock + threadIdx.x;
+    const bool nt = (a.tune & TUNE_NT_STATE) != 0;
+    int32_t c = -1;
+    if (p < a.nP) c = nt ? __builtin_nontemporal_load(&a.cell[p]) : a.cell[p];
+    const bool live = c >= 0;
+    if (threadIdx.x < 64) s_tab[threadIdx.x] = ((const int *)&ta.tab)[threadIdx.x];
+    if (threadIdx.x == 0) { s_box[0] = 0x7fffffff; s_box[1] = -1; s_box[2] = 0x7fffffff; s_box[3] = -1; }
+    __syncthreads();
+    {
+        int jlo = live ? cell_j(c) : 0x7fffffff, jhi = live ? cell_j(c) : -1, ilo = live ? cell_i(c) : 0x7fffffff, ihi = live ? cell_i(c) : -1;
+        for (int off = 32; off > 0; off >>= 1) {
+            jlo = min(jlo, __shfl_xor(jlo, off)); jhi = max(jhi, __shfl_xor(jhi, off));
+            ilo = min(ilo, __shfl_xor(ilo, off)); ihi = max(ihi, __shfl_xor(ihi, off));
+        }
+        if ((threadIdx.x & 63) == 0 && jhi >= 0) {
+            atomicMin(&s_box[0], jlo); atomicMax(&s_box[1], jhi); atomicMin(&s_box[2], ilo); atomicMax(&s_box[3], ihi);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int R0 = 0, C0 = 0, PR = 3, PC = 3;
+        if (s_box[1] >= 0 && ta.patch_cells > 0) {
+            const int nr = s_box[1] - s_box[0] + 1 + 3, nc = s_box[3] - s_box[2] + 1 + 3;
+            int m = -1;
+            for (int t = 0; t <= ta.patch_margin; t++)
+                if ((int64_t)(nr + 2 * t) * (nc + 2 * t) <= ta.patch_cells) m = t;
+            if (m >= 0) {
+                R0 = max(0, s_box[0] - 2 - m); C0 = max(0, s_box[2] - 2 - m);
+                PR = min(a.Nj, s_box[1] + 2 + m) - R0; PC = min(a.Ni, s_box[3] + 2 + m) - C0;
+            }
+        }
+        s_box[4] = R0; s_box[5] = C0; s_box[6] = PR; s_box[7] = PC;
+    }
+    __syncthreads();
+    Patch pa;
+    pa.R0 = s_box[4]; pa.C0 = s_box[5]; pa.PR = s_box[6]; pa.PC = s_box[7];
+    char *s_geo = smem + kRunLdsFixed;
+    if (threadIdx.x < 28) {
+        const int e = threadIdx.x / 7, q = threadIdx.x % 7;
+        s_tabL[16 * e + q] = (ta.dji[e][q][0] * pa.PC + ta.dji[e][q][1]) * (int)sizeof(pt) + (q < 4 ? kLdsBias : 0);
+    }
+    const char *__restrict__ gb = (const char *)a.geo;
+    if (pa.PR > 3) {
+        const int ncell = pa.PR * pa.PC;
+        for (int t = threadIdx.x; t < ncell; t += kRunBlock) {
+            const int r = t / pa.PC, cc = t - r * pa.PC;
+            *(v2d *)(s_geo + (size_t)t * sizeof(pt)) = *(const v2d *)(ta.geoF + ((size_t)(pa.R0 + r) * a.Ni + pa.C0 + cc));
+        }
+    }
+    __syncthreads();                                     // last barrier: from here on lanes may leave
+    if (!live) return;
+    int first = 0, last = 0x7fffffff;
+    if (WINDOW) { const int2 w = a.win[p]; first = w.x; last = w.y; }
+    pt P = nt ? load_pt_nt(&a.pos[p]) : a.pos[p];
+    bool moved = false, recelled = false;
+    CellCtx x;
+    const int porg = (pa.R0 << 16) | pa.C0;
+    int crel = c - porg;
+    const unsigned geo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)s_geo - (unsigned)kLdsBias;
+    unsigned lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+    bool inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+    {
+        const unsigned kcell = (unsigned)(cell_j(c) * a.Ni + cell_i(c));
+        if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell, lo, x);
+        else load_ctx<sizeof(FT)>(a, gb, kcell, x);
+    }
+    const double *__restrict__ theta = ta.theta;
+    const int nsub = ta.nsub;
+    double k1000 = 1000.;
+    asm volatile("" : "+s"(k1000));
+    bool killed = false;
+#pragma unroll 1
+    for (int r = 0; r < ta.nrec; r++) {
+        const int jrec = a.jrec + r;
+        if (WINDOW) {
+            if (jrec < first) continue;
+            if (jrec > last) break;
+        }
+        // the record's own fields and those of its two neighbours in time (scalar loads from the kernel arguments)
+        const char *ub = (const char *)ta.u[r + 1], *vb = (const char *)ta.v[r + 1], *kb = (const char *)ta.kill9[r];
+        const char *ub_m = (const char *)ta.u[r], *vb_m = (const char *)ta.v[r];
+        const char *ub_p = (const char *)ta.u[r + 2], *vb_p = (const char *)ta.v[r + 2];
+        // the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] and the neighbours' Survive byte of the host
+        // cell for this record; reloaded below after every crossing
+        __builtin_amdgcn_s_setprio(kPrioLoads);
+        FT fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)), fu1 = *(const FT *)(ub + x.o1);
+        FT fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))), fv1 = *(const FT *)(vb + x.o1);
+        unsigned k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+        __builtin_amdgcn_s_setprio(kPrioBase);
+        // the partner's candidates of the same cell: `held` = the partner they belong to (wave-uniform), `stale` = this lane
+        // has changed cell since they were loaded
+        FT gu0 = 0, gu1 = 0, gv0 = 0, gv1 = 0;
+        const char *held = nullptr;
+        bool stale = true;
+#pragma unroll 1
+        for (int s = 0; s < nsub; s++) {
+            const double th = theta[s];                  // wave-uniform
+            const char *ubq = th < 0. ? ub_m : (th > 0. ? ub_p : nullptr);
+            const char *vbq = th < 0. ? vb_m : vb_p;
+            const double w = fabs(th);
+            if (ubq != held) { held = ubq; stale = true; }            // the phase change of the record
+            if (ubq != nullptr && stale) {
+                __builtin_amdgcn_s_setprio(kPrioLoads);
+                gu0 = *(const FT *)(ubq + x.o1 - sizeof(FT)); gu1 = *(const FT *)(ubq + x.o1);
+                gv0 = *(const FT *)(vbq + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); gv1 = *(const FT *)(vbq + x.o1);
+                __builtin_amdgcn_s_setprio(kPrioBase);
+                stale = false;
+            }
+            double zU, zV;
+            if (UVS == 1) {                              // :427-441, at the sub-step's position: the pick is geometric, so it is
+                                                         // taken first and only the two picked candidates are blended
+                const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
+                const bool llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
+                const bool llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
+                pin_load(fu0); pin_load(fv0);
+                zU = (double)(llum1 ? fu0 : fu1);
+                zV = (double)(llvm1 ? fv0 : fv1);
+                if (ubq != nullptr) {
+                    zU = zU + w * ((double)(llum1 ? gu0 : gu1) - zU);
+                    zV = zV + w * ((double)(llvm1 ? gv0 : gv1) - zV);
+                }
+            } else {
+                double Fu0 = (double)fu0, Fu1 = (double)fu1, Fv0 = (double)fv0, Fv1 = (double)fv1;
+                if (ubq != nullptr) {
+                    Fu0 = Fu0 + w * ((double)gu0 - Fu0); Fu1 = Fu1 + w * ((double)gu1 - Fu1);
+                    Fv0 = Fv0 + w * ((double)gv0 - Fv0); Fv1 = Fv1 + w * ((double)gv1 - Fv1);
+                }
+                if (UVS == 0) {                          // :423-425
+                    zU = 0.5 * (Fu1 + Fu0);
+                    zV = 0.5 * (Fv1 + Fv0);
+                } else {                                 // extra: linear interpolation in space (not in the reference)
+                    zU = lerp_on_segment(P, x.U10, x.U11, Fu0, Fu1);
+                    zV = lerp_on_segment(P, x.V01, x.V11, Fv0, Fv1);
+                }
+            }
+            const double dx = zU * a.rdt;                // :452-458 with dt_sub
+            const double dy = zV * a.rdt;
+            pt Pn;
+            Pn.x = P.x + div1000(dx, k1000);
+            Pn.y = P.y + div1000(dy, k1000);
+            moved = true;
+            const bool still_in = inside_quad_hot(Pn.y, Pn.x, x.F00, x.F01, x.F11, x.F10, a.eps_mg);
+            if (!still_in) {      // :466-484
+                __builtin_amdgcn_s_setprio(kPrioCross);
+                const unsigned kcell = x.o1 / (unsigned)sizeof(FT);
+                int dcell, dk, dlo = 0;
+                pin_load(k9);
+                if (inl) {
+                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, s_tab, s_tabL, dcell, dk, dlo, killed);
+                } else {
+                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, s_tab, dcell, dk, killed);
+                }
+                c += dcell;
+                recelled = true;
+                const int crel = c - porg;
+                if (inl) {
+                    lo += (unsigned)dlo;
+                } else {
+                    lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+                }
+                inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+                if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell + (unsigned)dk, lo, x);
+                else load_ctx<sizeof(FT)>(a, gb, kcell + (unsigned)dk, x);
+                if (!killed && s + 1 < nsub) {           // the new cell's candidates and Survive byte, same record; the partner's
+                                                         // follow at the top of the next sub-step (its phase decides whose)
+                    fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)); fu1 = *(const FT *)(ub + x.o1);
+                    fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); fv1 = *(const FT *)(vb + x.o1);
+                    k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+                    stale = true;
+                }
+                __builtin_amdgcn_s_setprio(kPrioBase);
+            }
+            P = Pn;
+            if (killed) break;
+        }
+        if (killed) {
+            c |= SITRK_DEAD_BIT;
+            unsigned tk = threadIdx.x;
+            asm volatile("" : "+v"(tk));
+            a.kill_rec[(int64_t)blk * kRunBlock + tk] = jrec;
+            break;                                       // dead buoys never step again
+        }
+    }
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int64_t pe = (int64_t)blk * kRunBlock + tid;
+    if (moved) {
+        if (nt) store_pt_nt(&a.pos[pe], P);
+        else a.pos[pe] = P;
+    }
+    if (recelled) a.cell[pe] = c;
+}
+
+// ---------------------------------------------------------------------------
 // Predicate probes:the device functions of the hot path evaluated on plain arrays, so that the parity
 // tests can hold them against the reference's golden vectors one predicate at a time (sitrk_eval_*).
 // ---------------------------------------------------------------------------

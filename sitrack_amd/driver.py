@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib, ncio
 from .distributed import Comm, all_ranges
-from .tracking import GetTimeSpan, IceTracker, SeedInit
+from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
 rdt = 3600.          # time step [s] = model output period (reference :31); the default of --rdt
 FILL = ncio.FillValue
@@ -83,6 +83,11 @@ def parse_args(argv=None):
                     help='NAME[,NAME...]: 2-D variables (time,y,x) of the SI3 file written next to the positions as NAME(time,buoy), '
                          'the raw value at each buoy\'s host T-point, no interpolation (extra; default none): `siconc` comes from '
                          'the record resident on the GPU, any other name is read from the -i file for the records that are written')
+    ap.add_argument('--tinterp', choices=('off', 'centre', 'start'), default='off',
+                    help='interpolate u_ice, v_ice linearly in time between consecutive records for the sub-steps of --nsub (extra; '
+                         'default off = every sub-step of a record uses that record\'s fields): `centre` = records are time means '
+                         'centred on their step interval (what NEMO writes), `start` = snapshots at its start.  Partners are taken '
+                         'among the records the run reads; siconc and the Survive test are never interpolated')
     return ap.parse_args(argv)
 
 
@@ -113,6 +118,42 @@ def plan_batches(Nt, kstrt, K, lFull, stride=1, ends=(), firsts=None):
         batches.append((jt, m))
         jt += m
     return batches
+
+
+def tinterp_slots(K):
+    """--tinterp: the slot ring (at least 3: a record and its two partners) and the `K` plan_batches is given, so that a batch
+    of m records, its two partners and the look-ahead of the batch before it (m'' + m + 2 records) sit in distinct slots."""
+    K = max(3, int(K))
+    return K, 2 * max(1, (K - 2) // 2)
+
+
+def plan_tinterp(batches, Nt, K):
+    """--tinterp: what every batch (jt0, m) of plan_batches needs around its launch, as a list of dicts.
+      slot0, have_prev, have_next      arguments of sitrk_run_tlerp: partners are records of the run only, so the first record
+                                       has none before it and the last none behind it
+      prev_slot, next_slot             the slots of records jt0 - 1 / jt0 + m (None: no such partner)
+      ahead                            the record (first of the next batch = the partner behind this one) that must be uploaded
+                                       IN FRONT of this batch's launch, None for the last batch
+      behind                           the rest of the next batch, uploaded behind the launch, while it runs
+    Record jt0 - 1 is still resident from the batch before.  ValueError where m + 2 records do not fit the ring."""
+    plan = []
+    for ib, (jt0, m) in enumerate(batches):
+        if m + 2 > K:
+            raise ValueError('--tinterp: a batch of %d records and its two partners do not fit %d slots' % (m, K))
+        nxt = batches[ib + 1] if ib + 1 < len(batches) else None
+        have_prev, have_next = jt0 > 0, jt0 + m < Nt
+        plan.append({"jt0": jt0, "m": m, "slot0": jt0 % K, "have_prev": have_prev, "have_next": have_next,
+                     "prev_slot": (jt0 - 1) % K if have_prev else None, "next_slot": (jt0 + m) % K if have_next else None,
+                     "ahead": nxt[0] if nxt else None,
+                     "behind": list(range(nxt[0] + 1, nxt[0] + nxt[1])) if nxt else []})
+    return plan
+
+
+def batch_box_age(age, m, tinterp=False):
+    """The `age` Context.box_of is given for a batch of m records planned `age` records after the buoys' box was evaluated:
+    its last record is age + m - 1 records away.  With --tinterp the box is one record wider: the batch's last record is the
+    partner of the next batch's first one, whose sub-steps start up to nsub cells further out."""
+    return age + m - 1 + (1 if tinterp else 0)
 
 
 def _rdt_arg(text):
@@ -437,6 +478,10 @@ def main(argv=None):
     (u0,) = records.fields(kstrt, ('u_ice',))
     fdt = np.float64 if np.asarray(u0).dtype == np.float64 else np.float32
     K = int(max(2, min(a.slots, 64)))
+    tphase = None if a.tinterp == 'off' else tinterp_phase(a.tinterp)
+    K_plan = K
+    if tphase is not None:
+        K, K_plan = tinterp_slots(K)
     trk = IceTracker(xYf, xXf, xYu, xXu, xYv, xXv, imaskt, rdt=rdt, iUVstrategy=iUVstrategy, nslots=K, field_dtype=fdt, ctx=ctx,
                      nsub=nsub)
     trk.set_buoys(xPosC0[mine], vJIt[mine], z1stModelRec[mine] if lUse2DTime else None, zLstModelRec[mine] if lUse2DTime else None)
@@ -495,26 +540,40 @@ def main(argv=None):
     bcast = None
     if a.full_records and comm.multi and comm.backend == "nccl":
         from .distributed import RecordBroadcaster
+        if tphase is not None:
+            raise ValueError('--tinterp is not available together with --full-records under an RCCL launch (the record broadcaster '
+                             'hands a slot back before its partner has been stepped with): drop --full-records')
         bcast = RecordBroadcaster(ctx)                 # rank 0 reads; one RCCL broadcast per record, overlapped with the stepping
-    batches = plan_batches(Nt, kstrt, K, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None)
+    batches = plan_batches(Nt, kstrt, K_plan, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None)
+    tplan = plan_tinterp(batches, Nt, K) if tphase is not None else None
     band = {"box": None, "age": None, "bytes": 0, "boxes": {}}
     esz = np.dtype(fdt).itemsize
 
-    def upload(jt0, m):
-        """records jt0..jt0+m-1 -> slots (jt0+r) % K, asynchronously"""
-        t_up = clk.now()
+    def batch_box(jt0, m, not_queued=0):
+        """the box of the batch jt0..jt0+m-1; not_queued: records planned in front of it that the GPU has not been given yet"""
         if not a.full_records:
             # the box (rows x columns, round 4; rows only before) this rank's buoys can touch during those records: their host
             # cells at the last evaluation, widened by one cell per record stepped or queued since (sitrk_buoy_box waits for
             # the GPU: only every so often).  Only that hyperslab of the record is read from the file and uploaded.
             if band["age"] is None or band["age"] + m > 96:
                 band["box"] = ctx.buoy_box()
-                band["age"] = 0
-            j0, j1, i0, i1 = ctx.box_of(*band["box"], band["age"] + m - 1)
+                band["age"] = not_queued
+            j0, j1, i0, i1 = ctx.box_of(*band["box"], batch_box_age(band["age"], m, tphase is not None))
             band["age"] += m
             band["boxes"][jt0] = (j0, j1, i0, i1)            # what the batch's slots hold: the box its records are sampled in
-        for r in range(m):
-            jrec, slot = jt0 + r + kstrt, (jt0 + r) % K
+
+    def upload(jt0, m):
+        """records jt0..jt0+m-1 -> slots (jt0+r) % K, asynchronously"""
+        batch_box(jt0, m)
+        upload_recs(jt0, range(jt0, jt0 + m))
+
+    def upload_recs(jt0, jts):
+        """records jts of (or, as a partner, next to) the batch that starts at jt0 -> slots jt % K, over that batch's box"""
+        t_up = clk.now()
+        if not a.full_records:
+            j0, j1, i0, i1 = band["boxes"][jt0]
+        for jt_r in jts:
+            jrec, slot = jt_r + kstrt, jt_r % K
             if not a.full_records:
                 if j1 > j0:
                     ctx.stage_fill(slot, j0, j1 - j0, lambda *outs: records.fields_box_into(jrec, j0, j1, i0, i1, outs), i0=i0, ncols=i1 - i0)
@@ -632,12 +691,24 @@ def main(argv=None):
                         series.abort()
                         raise
             t_q = clk.now()
-        trk.run(jrec0, jt0 % K, m)
+        if tplan is None:
+            trk.run(jrec0, jt0 % K, m)
+        else:
+            # --tinterp: the first record of the next batch is this batch's last partner: it travels in front of the launch
+            # (the GPU has not been given this batch's m records yet when its box is worked out)
+            if tplan[ib]["ahead"] is not None:
+                batch_box(*batches[ib + 1], not_queued=m)
+                upload_recs(batches[ib + 1][0], [tplan[ib]["ahead"]])
+                t_q = clk.now()
+            trk.run(jrec0, jt0 % K, m, tinterp=tphase, have_prev=tplan[ib]["have_prev"], have_next=tplan[ib]["have_next"])
         if bcast is not None:
             bcast.after_run(used)
         clk.add("enqueue_stepping_s", t_q)
         if ib + 1 < len(batches) and not due[ib]:
-            upload(*batches[ib + 1])               # travels while the launch above runs
+            if tplan is None:
+                upload(*batches[ib + 1])           # travels while the launch above runs
+            else:
+                upload_recs(batches[ib + 1][0], tplan[ib]["behind"])
         jt, jrec, itime = jt0 + m - 1, jrecN, vTime[jt0 + m - 1]
         need = need_output(jrec)
         t_f = clk.now()
@@ -683,6 +754,9 @@ def main(argv=None):
             rebalance()
             clk.add("rebalance_s", t_r)
             upload(*batches[ib + 1])
+            if tplan is not None:
+                # the next batch's first partner was uploaded over the box of this rank's former buoys: once more, over the new one
+                upload_recs(batches[ib + 1][0], [jt0 + m - 1])
     ctx.sync()
     if bcast is not None:
         bcast.close()

@@ -134,6 +134,20 @@ def ConvertCartesianNPSkm2Geo(pY, pX, lat0=70., lon0=-45., ctx=None):
     return np.ascontiguousarray(ll[:, 0].reshape(shp)), np.ascontiguousarray(ll[:, 1].reshape(shp))
 
 
+def tinterp_phase(tinterp):
+    """The `phase` of sitrk_run_tlerp from what IceTracker.run / --tinterp take: 'centre' = 0.5 (records are time means centred
+    on their step interval, what NEMO writes), 'start' = 0 (snapshots at its start), or the number itself."""
+    if isinstance(tinterp, str):
+        try:
+            return {'centre': 0.5, 'center': 0.5, 'start': 0.0}[tinterp]
+        except KeyError:
+            raise ValueError("tinterp: expected 'centre', 'start' or a number in [0,1], got %r" % tinterp)
+    ph = float(tinterp)
+    if not 0.0 <= ph <= 1.0:
+        raise ValueError("tinterp: the phase must be in [0,1], got %r" % tinterp)
+    return ph
+
+
 class IceTracker:
     """The record loop body of the reference driver (si3_part_tracker.py:361-496) as an object.
 
@@ -186,10 +200,16 @@ class IceTracker:
     def step(self, jrec, slot=0):
         self.ctx.step(slot, jrec)
 
-    def run(self, jrec0, slot0, nrec):
+    def run(self, jrec0, slot0, nrec, tinterp=None, have_prev=False, have_next=False):
         """records jrec0 .. jrec0+nrec-1 from slots (slot0+k) % nslots: one fused launch where the library can
-        (sitrk_run), same results as nrec calls of step()"""
-        if nrec == 1:
+        (sitrk_run), same results as nrec calls of step().
+        `tinterp` (extra): None = every sub-step of a record uses that record's velocities; a number in [0,1], 'centre' (0.5)
+        or 'start' (0) = the velocities are interpolated linearly in time between consecutive records (sitrk_run_tlerp), the
+        value being where in its step interval a record is valid; have_prev / have_next: records jrec0-1 / jrec0+nrec are
+        resident in the slots in front of slot0 / behind the last one and are blended with."""
+        if tinterp is not None:
+            self.ctx.run_tlerp(slot0, jrec0, nrec, tinterp_phase(tinterp), have_prev, have_next)
+        elif nrec == 1:
             self.ctx.step(slot0, jrec0)
         else:
             self.ctx.run(slot0, jrec0, nrec)
