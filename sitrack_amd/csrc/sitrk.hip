@@ -1154,12 +1154,32 @@ static int f32_class_for(double rdt)
     return (ar >= 0x1p-700 && ar <= 0x1p700) ? kClassFiniteNonzeroF32 : 0;
 }
 
+// What RunArgs and TlerpArgs have in common (the field names agree): the StepArgs part from the handle for the buoys
+// [off, off + cnt) and the sub-step dt_sub = rdt / nsub (one rounded division), the records' count, crossing table and patch
+template <typename Args>
+static void fill_fused_args(const sitrk_ctx *h, Args &ra, int64_t off, int64_t cnt, int jrec0, int nrec)
+{
+    const BuoyState &s = h->st[h->cur];
+    ra.s.nP = cnt; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0;
+    ra.s.rdt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;
+    ra.s.rmin_conc = h->rmin_conc; ra.s.eps_mg = h->eps_mg; ra.s.geo = h->geo; ra.s.orient = h->orient; ra.s.kill = nullptr; ra.s.u = ra.s.v = nullptr;
+    ra.s.pos = s.pos + off; ra.s.cell = s.cell + off; ra.s.kill_rec = s.kill_rec + off; ra.s.win = s.win ? s.win + off : nullptr;
+    ra.nrec = nrec;
+    make_cross_tab(h->Ni, ra.tab, ra.dji);
+    ra.geoF = h->geoF;
+    ra.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
+    ra.patch_margin = h->patch_margin;
+    ra.xcd_group = h->xcd_group;
+}
+
+// dynamic LDS of the fused kernels: tables + the patch's F-points
+static size_t fused_lds_bytes(int patch_cells) { return kRunLdsFixed + (size_t)patch_cells * sizeof(pt); }
+
 // advect_run_kernel (nsub == 1) or advect_substep_kernel (nsub > 1) over the records of `ra`
 static void launch_run(sitrk_ctx *h, const RunArgs &ra, int nsub, hipStream_t stream)
 {
     const dim3 grid(nblocks(ra.s.nP, kRunBlock)), block(kRunBlock);
-    // dynamic LDS: tables + the patch's F-points
-    const size_t lds = kRunLdsFixed + (size_t)ra.patch_cells * sizeof(pt);
+    const size_t lds = fused_lds_bytes(ra.patch_cells);
     pick_kernel(h, window_test_needed(h, ra.s.jrec, ra.nrec), [&](auto ft, auto uvs, auto win) {
         using FT = typename decltype(ft)::type;
         constexpr int UVS = decltype(uvs)::value;
@@ -1177,22 +1197,12 @@ static void launch_run(sitrk_ctx *h, const RunArgs &ra, int nsub, hipStream_t st
 // slots ready before its fork and marks and counts behind its join.
 static int launch_records(sitrk_ctx *h, int slot_first, int jrec0, int m, int64_t off, int64_t cnt, hipStream_t lane)
 {
-    BuoyState &s = h->st[h->cur];
     const hipStream_t stream = lane ? lane : h->stream;
     if (cnt < 0) cnt = h->nP - off;
     const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
-    const double dt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;        // dt_sub: one rounded division
     RunArgs ra;
-    ra.s.nP = cnt; ra.s.tune = h->tune; ra.s.Nj = h->Nj; ra.s.Ni = h->Ni; ra.s.jrec = jrec0;
-    ra.s.rdt = dt; ra.s.rmin_conc = h->rmin_conc; ra.s.eps_mg = h->eps_mg; ra.s.geo = h->geo; ra.s.orient = h->orient; ra.s.kill = nullptr; ra.s.u = ra.s.v = nullptr;
-    ra.s.pos = s.pos + off; ra.s.cell = s.cell + off; ra.s.kill_rec = s.kill_rec + off; ra.s.win = s.win ? s.win + off : nullptr;
-    ra.nrec = m;
-    make_cross_tab(h->Ni, ra.tab, ra.dji);
-    ra.geoF = h->geoF;
-    ra.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
-    ra.patch_margin = h->patch_margin;
-    ra.xcd_group = h->xcd_group;
-    ra.f32_class = f32_class_for(dt);
+    fill_fused_args(h, ra, off, cnt, jrec0, m);
+    ra.f32_class = f32_class_for(ra.s.rdt);
     int used[kMaxFuse];
     for (int r = 0; r < m; r++) {
         const int slot = (slot_first + r) % h->nslots;
@@ -1365,20 +1375,11 @@ static int tlerp_table(sitrk_ctx *h, double phase, bool *uses_prev, bool *uses_n
 // slot in front of the first / behind the last one holds the record before / behind them and is read as their partner.
 static int launch_tlerp(sitrk_ctx *h, int slot_first, int jrec0, int m, bool prev, bool next)
 {
-    BuoyState &s = h->st[h->cur];
     const size_t n = (size_t)h->Nj * h->Ni, es = elem_size(h->dtype);
-    const double dt = h->nsub > 1 ? h->rdt / h->nsub : h->rdt;        // dt_sub: one rounded division, as launch_records
     TlerpArgs ta;
-    ta.s.nP = h->nP; ta.s.tune = h->tune; ta.s.Nj = h->Nj; ta.s.Ni = h->Ni; ta.s.jrec = jrec0;
-    ta.s.rdt = dt; ta.s.rmin_conc = h->rmin_conc; ta.s.eps_mg = h->eps_mg; ta.s.geo = h->geo; ta.s.orient = h->orient; ta.s.kill = nullptr; ta.s.u = ta.s.v = nullptr;
-    ta.s.pos = s.pos; ta.s.cell = s.cell; ta.s.kill_rec = s.kill_rec; ta.s.win = s.win;
-    ta.nrec = m; ta.nsub = h->nsub;
+    fill_fused_args(h, ta, 0, h->nP, jrec0, m);
+    ta.nsub = h->nsub;
     ta.theta = h->tlerp_theta;
-    make_cross_tab(h->Ni, ta.tab, ta.dji);
-    ta.geoF = h->geoF;
-    ta.patch_cells = (int)((size_t)h->patch_kb * 1024 / sizeof(pt));
-    ta.patch_margin = h->patch_margin;
-    ta.xcd_group = h->xcd_group;
     for (int q = 0; q < kMaxFuse + 2; q++) ta.u[q] = ta.v[q] = nullptr;
     for (int q = 0; q < kMaxFuse; q++) ta.kill9[q] = nullptr;
     int used[kMaxFuse + 2], nused = 0;
@@ -1394,7 +1395,7 @@ static int launch_tlerp(sitrk_ctx *h, int slot_first, int jrec0, int m, bool pre
         if (q >= 0 && q < m) ta.kill9[q] = h->kill9 + (size_t)slot * n;
     }
     const dim3 grid(nblocks(h->nP, kRunBlock)), block(kRunBlock);
-    const size_t lds = kRunLdsFixed + (size_t)ta.patch_cells * sizeof(pt);
+    const size_t lds = fused_lds_bytes(ta.patch_cells);
     pick_kernel(h, window_test_needed(h, jrec0, m), [&](auto ft, auto uvs, auto win) {
         using FT = typename decltype(ft)::type;
         constexpr int UVS = decltype(uvs)::value;

@@ -883,6 +883,9 @@ static constexpr int kRunWaves = 7;     // 72 VGPRs, no scratch (the cell is sto
 static constexpr int kRunWavesWindow = 6;   // the form with per-buoy record windows carries two more registers: 9 spilled at 7 waves
                                             // (13-25 with the window packed into one register, as a single test, or as a predicate on the body)
 
+// TWINS: the sub-step and time-blend kernels run this kernel's prologue, lane set-up, re-cell step, kill write and epilogue
+// from fused_prologue, lane_setup, recell, record_kill and store_state below (this kernel cannot call them: its ISA is
+// pinned, see there).  A change to one of those stretches here goes into the function of that name, and back.
 template <typename FT, int UVS, bool WINDOW>
 __global__ __launch_bounds__(kRunBlock, WINDOW ? kRunWavesWindow : kRunWaves) void advect_run_kernel(RunArgs ra)
 {
@@ -1066,28 +1069,30 @@ __global__ __launch_bounds__(kRunBlock, WINDOW ? kRunWavesWindow : kRunWaves) vo
 }
 
 // ---------------------------------------------------------------------------
-// Sub-stepped advection (sitrk_set_substeps, nsub > 1): the fused loop with an inner loop of `nsub` Euler sub-steps per
-// record.  ra.s.rdt and ra.f32_class are those of the sub-step dt_sub = rdt / nsub (the host divides once).  Every sub-step
-// is the reference's per-buoy body with dt_sub and the record's fields: velocity pick at the current position, Euler update,
-// inside test, crossing + Survive.  The four velocity candidates and the Survive byte of the host cell are loaded at the top
-// of a record and again only after a crossing (a cell change): while the buoy stays in its cell they are the same values.
-// A buoy killed in sub-step s takes no further sub-step; all sub-steps of a record are gated by the same record window.
-// Same operations on the same operands in the same order as advect_run_kernel, sub-step by sub-step.  The LDS patch is the
-// same: a buoy now moves up to nsub cells per record, so it leaves the patch sooner and then reads global memory
-// (patch_covers is tested at every crossing, as there).
+// Pieces shared by advect_substep_kernel and advect_tlerp_kernel.  advect_run_kernel keeps its own text of each: its ISA is
+// pinned by tests/test_lanes_build.py and profiles/traffic.json, and moving any part of it into a function changes it.  A
+// function marked TWIN repeats a stretch of that kernel operation for operation: a change to one goes into the other.
+// What is passed by value and what stays at the call sites is what keeps the registers, occupancy and scratch of all 24
+// instances (profiles/fused_helpers_resources.md).
 // ---------------------------------------------------------------------------
-// the candidates and k9 live across the sub-step loop: 80 VGPRs at 6 waves/SIMD for binary32 records without the window test
-// (7 waves would spill), 5 waves (up to 96 VGPRs) for fp64 records (16 B/lane of scratch at 6) and for the window form
-static constexpr int kSubWaves = 6;
-static constexpr int kSubWavesWide = 5;
+struct FusedWg {                        // what a lane keeps of the workgroup prologue
+    unsigned blk;                       // workgroup index after the XCD remap
+    int32_t c;                          // the lane's cell (-1 beyond the set)
+    bool nt;
+    Patch pa;
+    int *s_tab, *s_tabL;
+    char *s_geo;
+};
 
-template <typename FT, int UVS, bool WINDOW>
-__global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesWide : kSubWaves) void advect_substep_kernel(RunArgs ra, int nsub)
+// Workgroup prologue: XCD remap, cell load, crossing table to LDS, bounding box of the live buoys, patch choice, the table's
+// LDS twin, patch fill; returns behind the last barrier.  TWIN of advect_run_kernel from its first line to that barrier.
+template <typename Args>
+__device__ __forceinline__ FusedWg fused_prologue(const Args &ra, char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int *s_tab = (int *)smem;
-    int *s_tabL = s_tab + 64;
-    int *s_box = s_tabL + 64;
+    FusedWg w;
+    int *s_tab = (int *)smem;                            // CrossTab, 64 ints
+    int *s_tabL = s_tab + 64;                            // 4 rows of 16 ints (7 used)
+    int *s_box = s_tabL + 64;                            // [0..3] jmin jmax imin imax of the live buoys; [4..7] R0 C0 PR PC
     const StepArgs &a = ra.s;
     const unsigned blk = (a.tune & TUNE_XCD_REMAP) ? xcd_remap(blockIdx.x, gridDim.x)
                          : (ra.xcd_group > 1 ? xcd_group(blockIdx.x, gridDim.x, (unsigned)ra.xcd_group) : blockIdx.x);
@@ -1111,9 +1116,9 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int R0 = 0, C0 = 0, PR = 3, PC = 3;
+        int R0 = 0, C0 = 0, PR = 3, PC = 3;              // "no patch": patch_covers() is false for every cell
         if (s_box[1] >= 0 && ra.patch_cells > 0) {
-            const int nr = s_box[1] - s_box[0] + 1 + 3, nc = s_box[3] - s_box[2] + 1 + 3;
+            const int nr = s_box[1] - s_box[0] + 1 + 3, nc = s_box[3] - s_box[2] + 1 + 3;      // rows jmin-2 .. jmax+1
             int m = -1;
             for (int t = 0; t <= ra.patch_margin; t++)
                 if ((int64_t)(nr + 2 * t) * (nc + 2 * t) <= ra.patch_cells) m = t;
@@ -1132,8 +1137,8 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
         const int e = threadIdx.x / 7, q = threadIdx.x % 7;
         s_tabL[16 * e + q] = (ra.dji[e][q][0] * pa.PC + ra.dji[e][q][1]) * (int)sizeof(pt) + (q < 4 ? kLdsBias : 0);
     }
-    const char *__restrict__ gb = (const char *)a.geo;
     if (pa.PR > 3) {
+        // a row of the patch is contiguous in the F-only copy of the geometry
         const int ncell = pa.PR * pa.PC;
         for (int t = threadIdx.x; t < ncell; t += kRunBlock) {
             const int r = t / pa.PC, cc = t - r * pa.PC;
@@ -1141,20 +1146,133 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
         }
     }
     __syncthreads();                                     // last barrier: from here on lanes may leave
-    if (!live) return;
-    int first = 0, last = 0x7fffffff;
+    w.blk = blk; w.c = c; w.nt = nt; w.pa = pa; w.s_tab = s_tab; w.s_tabL = s_tabL; w.s_geo = s_geo;
+    return w;
+}
+
+// Lane set-up of the live buoy p in cell c: record window, position, and the place of its host cell in the patch (porg: the
+// patch's origin packed like a cell; geo_la, lo: LDS addresses of the patch and of the cell's record; inl: the patch covers
+// it).  TWIN of advect_run_kernel behind its last barrier.  The first context load stays with the kernels: inside this
+// function one instance changes its occupancy.
+template <bool WINDOW>
+__device__ __forceinline__ void lane_setup(const StepArgs &a, const Patch &pa, char *s_geo, int64_t p, bool nt, int32_t c,
+                                      int &first, int &last, pt &P, int &porg, unsigned &geo_la, unsigned &lo, bool &inl)
+{
+    first = 0; last = 0x7fffffff;
     if (WINDOW) { const int2 w = a.win[p]; first = w.x; last = w.y; }
-    pt P = nt ? load_pt_nt(&a.pos[p]) : a.pos[p];
+    P = nt ? load_pt_nt(&a.pos[p]) : a.pos[p];
+    porg = (pa.R0 << 16) | pa.C0;
+    int crel = c - porg;
+    geo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)s_geo - (unsigned)kLdsBias;
+    lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+    inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+}
+
+// the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] of the cell at byte offset o1 in the record (ub, vb)
+template <typename FT>
+__device__ __forceinline__ void load_candidates(const StepArgs &a, const char *ub, const char *vb, unsigned o1,
+                                                FT &fu0, FT &fu1, FT &fv0, FT &fv1)
+{
+    fu0 = *(const FT *)(ub + o1 - sizeof(FT)); fu1 = *(const FT *)(ub + o1);
+    fv0 = *(const FT *)(vb + (o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); fv1 = *(const FT *)(vb + o1);
+}
+
+// the Survive byte of that cell's 8 neighbours in the record kb (used only if the buoy leaves the cell)
+template <typename FT>
+__device__ __forceinline__ unsigned load_k9(const char *kb, unsigned o1)
+{
+    return *(const uint8_t *)(kb + (o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+}
+
+// the nearest-point pick (:427-441) at P: take u[jT,iT-1] / v[jT-1,iT] instead of u[jT,iT] / v[jT,iT] ?
+// intersect2Seg(P,F,C,D) = (ccw(P,C,D) != ccw(F,C,D)) and (ccw(P,F,C) != ccw(P,F,D)); ccw(F,C,D) is per cell (x.ori)
+__device__ __forceinline__ void pick_nearest(pt P, const CellCtx &x, bool &llum1, bool &llvm1)
+{
+    const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
+    llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
+    llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
+}
+
+// The crossing step (:466-484) behind the choice of resolve_crossing_lds / resolve_crossing_tab and `c += dcell`, which stay
+// at the call sites (inside this function the forms with record window gain registers): the place of the new cell c
+// (geometry index kcell) in the patch, and its context.  TWIN of the end of `if (!still_in)` in advect_run_kernel.  A
+// killed buoy's destination is inside the mesh too: its context is loaded unconditionally, which keeps the loads out of the
+// shadow of the Survive test.
+template <typename FT>
+__device__ __forceinline__ void recell(const StepArgs &a, const Patch &pa, const char *__restrict__ gb, int porg, unsigned geo_la,
+                                        unsigned kcell, int dlo, int32_t c, unsigned &lo, bool &inl, CellCtx &x)
+{
+    const int crel = c - porg;
+    if (inl) {
+        lo += (unsigned)dlo;
+    } else {
+        lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
+    }
+    inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+    if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell, lo, x);
+    else load_ctx<sizeof(FT)>(a, gb, kcell, x);
+}
+
+// The record in which a buoy was killed; returns its cell with the dead bit (by value: with the cell passed by reference
+// the forms without record window gain registers or spill).  TWIN of advect_run_kernel's kill write.
+__device__ __forceinline__ int32_t record_kill(const StepArgs &a, unsigned blk, int jrec, int32_t c)
+{
+    unsigned tk = threadIdx.x;
+    asm volatile("" : "+v"(tk));
+    a.kill_rec[(int64_t)blk * kRunBlock + tk] = jrec;
+    return c | SITRK_DEAD_BIT;
+}
+
+// Epilogue: the position if the buoy moved, the cell if it changed.  TWIN of advect_run_kernel's epilogue.
+// (the buoy's index is recomputed here rather than kept: 16 bytes of state addresses per lane would be spilled to
+// scratch across the loop, i.e. written and read back through HBM)
+__device__ __forceinline__ void store_state(const StepArgs &a, unsigned blk, bool nt, bool moved, bool recelled, pt P, int32_t c)
+{
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int64_t pe = (int64_t)blk * kRunBlock + tid;
+    if (moved) {
+        if (nt) store_pt_nt(&a.pos[pe], P);
+        else a.pos[pe] = P;
+    }
+    if (recelled) a.cell[pe] = c;
+}
+
+// ---------------------------------------------------------------------------
+// Sub-stepped advection (sitrk_set_substeps, nsub > 1): the fused loop with an inner loop of `nsub` Euler sub-steps per
+// record.  ra.s.rdt and ra.f32_class are those of the sub-step dt_sub = rdt / nsub (the host divides once).  Every sub-step
+// is the reference's per-buoy body with dt_sub and the record's fields: velocity pick at the current position, Euler update,
+// inside test, crossing + Survive.  The four velocity candidates and the Survive byte of the host cell are loaded at the top
+// of a record and again only after a crossing (a cell change): while the buoy stays in its cell they are the same values.
+// A buoy killed in sub-step s takes no further sub-step; all sub-steps of a record are gated by the same record window.
+// Same operations on the same operands in the same order as advect_run_kernel, sub-step by sub-step.  The LDS patch is the
+// same: a buoy now moves up to nsub cells per record, so it leaves the patch sooner and then reads global memory
+// (patch_covers is tested at every crossing, as there).
+// ---------------------------------------------------------------------------
+// the candidates and k9 live across the sub-step loop: 80 VGPRs at 6 waves/SIMD for binary32 records without the window test
+// (7 waves would spill), 5 waves (up to 96 VGPRs) for fp64 records (16 B/lane of scratch at 6) and for the window form
+static constexpr int kSubWaves = 6;
+static constexpr int kSubWavesWide = 5;
+
+template <typename FT, int UVS, bool WINDOW>
+__global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesWide : kSubWaves) void advect_substep_kernel(RunArgs ra, int nsub)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const StepArgs &a = ra.s;
+    const FusedWg wg = fused_prologue(ra, smem);
+    int32_t c = wg.c;
+    const char *__restrict__ gb = (const char *)a.geo;
+    if (c < 0) return;                                   // not a live buoy (iAlive == 1, :380)
+    int first, last, porg;
+    pt P;
     bool moved = false, recelled = false;
     CellCtx x;
-    const int porg = (pa.R0 << 16) | pa.C0;
-    int crel = c - porg;
-    const unsigned geo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)s_geo - (unsigned)kLdsBias;
-    unsigned lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
-    bool inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+    unsigned geo_la, lo;
+    bool inl;
+    lane_setup<WINDOW>(a, wg.pa, wg.s_geo, (int64_t)wg.blk * kRunBlock + threadIdx.x, wg.nt, c, first, last, P, porg, geo_la, lo, inl);
     {
         const unsigned kcell = (unsigned)(cell_j(c) * a.Ni + cell_i(c));
-        if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell, lo, x);
+        if (inl) load_ctx_lds<sizeof(FT)>(a, wg.pa, gb, kcell, lo, x);
         else load_ctx<sizeof(FT)>(a, gb, kcell, x);
     }
     const char *ub_next = (const char *)ra.u[0], *vb_next = (const char *)ra.v[0], *kb_next = (const char *)ra.kill9[0];
@@ -1174,9 +1292,10 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
         // the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] and the neighbours' Survive byte of the host
         // cell for this record; reloaded below after every crossing
         __builtin_amdgcn_s_setprio(kPrioLoads);
-        FT fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)), fu1 = *(const FT *)(ub + x.o1);
-        FT fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))), fv1 = *(const FT *)(vb + x.o1);
-        unsigned k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+        FT fu0, fu1, fv0, fv1;
+        unsigned k9;
+        load_candidates<FT>(a, ub, vb, x.o1, fu0, fu1, fv0, fv1);
+        k9 = load_k9<FT>(kb, x.o1);
         __builtin_amdgcn_s_setprio(kPrioBase);
 #pragma unroll 1
         for (int s = 0; s < nsub; s++) {
@@ -1189,9 +1308,8 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
                 zU = lerp_on_segment(P, x.U10, x.U11, (double)fu0, (double)fu1);
                 zV = lerp_on_segment(P, x.V01, x.V11, (double)fv0, (double)fv1);
             } else {                                     // :427-441, at the sub-step's position
-                const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
-                const bool llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
-                const bool llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
+                bool llum1, llvm1;
+                pick_nearest(P, x, llum1, llvm1);
                 pin_load(fu0); pin_load(fv0);
                 su = llum1 ? fu0 : fu1;
                 sv = llvm1 ? fv0 : fv1;
@@ -1216,25 +1334,16 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
                 int dcell, dk, dlo = 0;
                 pin_load(k9);
                 if (inl) {
-                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, s_tab, s_tabL, dcell, dk, dlo, killed);
+                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, wg.s_tab, wg.s_tabL, dcell, dk, dlo, killed);
                 } else {
-                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, s_tab, dcell, dk, killed);
+                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, wg.s_tab, dcell, dk, killed);
                 }
                 c += dcell;
                 recelled = true;
-                const int crel = c - porg;
-                if (inl) {
-                    lo += (unsigned)dlo;
-                } else {
-                    lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
-                }
-                inl = patch_covers(pa, crel >> 16, crel & 0xffff);
-                if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell + (unsigned)dk, lo, x);
-                else load_ctx<sizeof(FT)>(a, gb, kcell + (unsigned)dk, x);
+                recell<FT>(a, wg.pa, gb, porg, geo_la, kcell + (unsigned)dk, dlo, c, lo, inl, x);
                 if (!killed && s + 1 < nsub) {           // the new cell's candidates and Survive byte, same record
-                    fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)); fu1 = *(const FT *)(ub + x.o1);
-                    fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); fv1 = *(const FT *)(vb + x.o1);
-                    k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+                    load_candidates<FT>(a, ub, vb, x.o1, fu0, fu1, fv0, fv1);
+                    k9 = load_k9<FT>(kb, x.o1);
                 }
                 __builtin_amdgcn_s_setprio(kPrioBase);
             }
@@ -1242,21 +1351,11 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kSubWavesW
             if (killed) break;
         }
         if (killed) {
-            c |= SITRK_DEAD_BIT;
-            unsigned tk = threadIdx.x;
-            asm volatile("" : "+v"(tk));
-            a.kill_rec[(int64_t)blk * kRunBlock + tk] = jrec;
+            c = record_kill(a, wg.blk, jrec, c);
             break;                                       // dead buoys never step again
         }
     }
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int64_t pe = (int64_t)blk * kRunBlock + tid;
-    if (moved) {
-        if (nt) store_pt_nt(&a.pos[pe], P);
-        else a.pos[pe] = P;
-    }
-    if (recelled) a.cell[pe] = c;
+    store_state(a, wg.blk, wg.nt, moved, recelled, P, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1293,76 +1392,21 @@ template <typename FT, int UVS, bool WINDOW>
 __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWavesWide : kTlerpWaves) void advect_tlerp_kernel(TlerpArgs ta)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int *s_tab = (int *)smem;
-    int *s_tabL = s_tab + 64;
-    int *s_box = s_tabL + 64;
     const StepArgs &a = ta.s;
-    const unsigned blk = (a.tune & TUNE_XCD_REMAP) ? xcd_remap(blockIdx.x, gridDim.x)
-                         : (ta.xcd_group > 1 ? xcd_group(blockIdx.x, gridDim.x, (unsigned)ta.xcd_group) : blockIdx.x);
-    const int64_t p = (int64_t)blk * kRunBlock + threadIdx.x;
-    const bool nt = (a.tune & TUNE_NT_STATE) != 0;
-    int32_t c = -1;
-    if (p < a.nP) c = nt ? __builtin_nontemporal_load(&a.cell[p]) : a.cell[p];
-    const bool live = c >= 0;
-    if (threadIdx.x < 64) s_tab[threadIdx.x] = ((const int *)&ta.tab)[threadIdx.x];
-    if (threadIdx.x == 0) { s_box[0] = 0x7fffffff; s_box[1] = -1; s_box[2] = 0x7fffffff; s_box[3] = -1; }
-    __syncthreads();
-    {
-        int jlo = live ? cell_j(c) : 0x7fffffff, jhi = live ? cell_j(c) : -1, ilo = live ? cell_i(c) : 0x7fffffff, ihi = live ? cell_i(c) : -1;
-        for (int off = 32; off > 0; off >>= 1) {
-            jlo = min(jlo, __shfl_xor(jlo, off)); jhi = max(jhi, __shfl_xor(jhi, off));
-            ilo = min(ilo, __shfl_xor(ilo, off)); ihi = max(ihi, __shfl_xor(ihi, off));
-        }
-        if ((threadIdx.x & 63) == 0 && jhi >= 0) {
-            atomicMin(&s_box[0], jlo); atomicMax(&s_box[1], jhi); atomicMin(&s_box[2], ilo); atomicMax(&s_box[3], ihi);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int R0 = 0, C0 = 0, PR = 3, PC = 3;
-        if (s_box[1] >= 0 && ta.patch_cells > 0) {
-            const int nr = s_box[1] - s_box[0] + 1 + 3, nc = s_box[3] - s_box[2] + 1 + 3;
-            int m = -1;
-            for (int t = 0; t <= ta.patch_margin; t++)
-                if ((int64_t)(nr + 2 * t) * (nc + 2 * t) <= ta.patch_cells) m = t;
-            if (m >= 0) {
-                R0 = max(0, s_box[0] - 2 - m); C0 = max(0, s_box[2] - 2 - m);
-                PR = min(a.Nj, s_box[1] + 2 + m) - R0; PC = min(a.Ni, s_box[3] + 2 + m) - C0;
-            }
-        }
-        s_box[4] = R0; s_box[5] = C0; s_box[6] = PR; s_box[7] = PC;
-    }
-    __syncthreads();
-    Patch pa;
-    pa.R0 = s_box[4]; pa.C0 = s_box[5]; pa.PR = s_box[6]; pa.PC = s_box[7];
-    char *s_geo = smem + kRunLdsFixed;
-    if (threadIdx.x < 28) {
-        const int e = threadIdx.x / 7, q = threadIdx.x % 7;
-        s_tabL[16 * e + q] = (ta.dji[e][q][0] * pa.PC + ta.dji[e][q][1]) * (int)sizeof(pt) + (q < 4 ? kLdsBias : 0);
-    }
+    const FusedWg wg = fused_prologue(ta, smem);
+    int32_t c = wg.c;
     const char *__restrict__ gb = (const char *)a.geo;
-    if (pa.PR > 3) {
-        const int ncell = pa.PR * pa.PC;
-        for (int t = threadIdx.x; t < ncell; t += kRunBlock) {
-            const int r = t / pa.PC, cc = t - r * pa.PC;
-            *(v2d *)(s_geo + (size_t)t * sizeof(pt)) = *(const v2d *)(ta.geoF + ((size_t)(pa.R0 + r) * a.Ni + pa.C0 + cc));
-        }
-    }
-    __syncthreads();                                     // last barrier: from here on lanes may leave
-    if (!live) return;
-    int first = 0, last = 0x7fffffff;
-    if (WINDOW) { const int2 w = a.win[p]; first = w.x; last = w.y; }
-    pt P = nt ? load_pt_nt(&a.pos[p]) : a.pos[p];
+    if (c < 0) return;                                   // not a live buoy (iAlive == 1, :380)
+    int first, last, porg;
+    pt P;
     bool moved = false, recelled = false;
     CellCtx x;
-    const int porg = (pa.R0 << 16) | pa.C0;
-    int crel = c - porg;
-    const unsigned geo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)s_geo - (unsigned)kLdsBias;
-    unsigned lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
-    bool inl = patch_covers(pa, crel >> 16, crel & 0xffff);
+    unsigned geo_la, lo;
+    bool inl;
+    lane_setup<WINDOW>(a, wg.pa, wg.s_geo, (int64_t)wg.blk * kRunBlock + threadIdx.x, wg.nt, c, first, last, P, porg, geo_la, lo, inl);
     {
         const unsigned kcell = (unsigned)(cell_j(c) * a.Ni + cell_i(c));
-        if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell, lo, x);
+        if (inl) load_ctx_lds<sizeof(FT)>(a, wg.pa, gb, kcell, lo, x);
         else load_ctx<sizeof(FT)>(a, gb, kcell, x);
     }
     const double *__restrict__ theta = ta.theta;
@@ -1384,9 +1428,10 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWave
         // the four velocity candidates u[jT,iT-1], u[jT,iT], v[jT-1,iT], v[jT,iT] and the neighbours' Survive byte of the host
         // cell for this record; reloaded below after every crossing
         __builtin_amdgcn_s_setprio(kPrioLoads);
-        FT fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)), fu1 = *(const FT *)(ub + x.o1);
-        FT fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))), fv1 = *(const FT *)(vb + x.o1);
-        unsigned k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+        FT fu0, fu1, fv0, fv1;
+        unsigned k9;
+        load_candidates<FT>(a, ub, vb, x.o1, fu0, fu1, fv0, fv1);
+        k9 = load_k9<FT>(kb, x.o1);
         __builtin_amdgcn_s_setprio(kPrioBase);
         // the partner's candidates of the same cell: `held` = the partner they belong to (wave-uniform), `stale` = this lane
         // has changed cell since they were loaded
@@ -1402,17 +1447,15 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWave
             if (ubq != held) { held = ubq; stale = true; }            // the phase change of the record
             if (ubq != nullptr && stale) {
                 __builtin_amdgcn_s_setprio(kPrioLoads);
-                gu0 = *(const FT *)(ubq + x.o1 - sizeof(FT)); gu1 = *(const FT *)(ubq + x.o1);
-                gv0 = *(const FT *)(vbq + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); gv1 = *(const FT *)(vbq + x.o1);
+                load_candidates<FT>(a, ubq, vbq, x.o1, gu0, gu1, gv0, gv1);
                 __builtin_amdgcn_s_setprio(kPrioBase);
                 stale = false;
             }
             double zU, zV;
             if (UVS == 1) {                              // :427-441, at the sub-step's position: the pick is geometric, so it is
                                                          // taken first and only the two picked candidates are blended
-                const bool sFV = (x.ori & 1u) != 0, sFU = (x.ori & 2u) != 0;
-                const bool llum1 = (ccw(P, x.V01, x.V11) != sFV) && (ccw(P, x.F11, x.V01) != ccw(P, x.F11, x.V11));
-                const bool llvm1 = (ccw(P, x.U10, x.U11) != sFU) && (ccw(P, x.F11, x.U10) != ccw(P, x.F11, x.U11));
+                bool llum1, llvm1;
+                pick_nearest(P, x, llum1, llvm1);
                 pin_load(fu0); pin_load(fv0);
                 zU = (double)(llum1 ? fu0 : fu1);
                 zV = (double)(llvm1 ? fv0 : fv1);
@@ -1447,26 +1490,17 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWave
                 int dcell, dk, dlo = 0;
                 pin_load(k9);
                 if (inl) {
-                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, s_tab, s_tabL, dcell, dk, dlo, killed);
+                    resolve_crossing_lds(P, Pn, x.F00, x.F01, x.F11, x.F10, lo, k9, wg.s_tab, wg.s_tabL, dcell, dk, dlo, killed);
                 } else {
-                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, s_tab, dcell, dk, killed);
+                    resolve_crossing_tab(P, Pn, x.F00, x.F01, x.F11, x.F10, kcell * (unsigned)sizeof(CellGeo), k9, gb, wg.s_tab, dcell, dk, killed);
                 }
                 c += dcell;
                 recelled = true;
-                const int crel = c - porg;
-                if (inl) {
-                    lo += (unsigned)dlo;
-                } else {
-                    lo = geo_la + patch_off(pa, crel >> 16, crel & 0xffff);
-                }
-                inl = patch_covers(pa, crel >> 16, crel & 0xffff);
-                if (inl) load_ctx_lds<sizeof(FT)>(a, pa, gb, kcell + (unsigned)dk, lo, x);
-                else load_ctx<sizeof(FT)>(a, gb, kcell + (unsigned)dk, x);
+                recell<FT>(a, wg.pa, gb, porg, geo_la, kcell + (unsigned)dk, dlo, c, lo, inl, x);
                 if (!killed && s + 1 < nsub) {           // the new cell's candidates and Survive byte, same record; the partner's
                                                          // follow at the top of the next sub-step (its phase decides whose)
-                    fu0 = *(const FT *)(ub + x.o1 - sizeof(FT)); fu1 = *(const FT *)(ub + x.o1);
-                    fv0 = *(const FT *)(vb + (x.o1 - (unsigned)a.Ni * (unsigned)sizeof(FT))); fv1 = *(const FT *)(vb + x.o1);
-                    k9 = *(const uint8_t *)(kb + (x.o1 >> (sizeof(FT) == 4 ? 2 : 3)));
+                    load_candidates<FT>(a, ub, vb, x.o1, fu0, fu1, fv0, fv1);
+                    k9 = load_k9<FT>(kb, x.o1);
                     stale = true;
                 }
                 __builtin_amdgcn_s_setprio(kPrioBase);
@@ -1475,21 +1509,11 @@ __global__ __launch_bounds__(kRunBlock, (WINDOW || sizeof(FT) == 8) ? kTlerpWave
             if (killed) break;
         }
         if (killed) {
-            c |= SITRK_DEAD_BIT;
-            unsigned tk = threadIdx.x;
-            asm volatile("" : "+v"(tk));
-            a.kill_rec[(int64_t)blk * kRunBlock + tk] = jrec;
+            c = record_kill(a, wg.blk, jrec, c);
             break;                                       // dead buoys never step again
         }
     }
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int64_t pe = (int64_t)blk * kRunBlock + tid;
-    if (moved) {
-        if (nt) store_pt_nt(&a.pos[pe], P);
-        else a.pos[pe] = P;
-    }
-    if (recelled) a.cell[pe] = c;
+    store_state(a, wg.blk, wg.nt, moved, recelled, P, c);
 }
 
 // ---------------------------------------------------------------------------
