@@ -386,6 +386,61 @@ int sitrk_deform_since_mark(sitrk_t *h, int jrec1, int64_t nC, int nv, const int
  * events around them -- the pass over the points, the cell kernel; either pointer may be NULL */
 int sitrk_deform_kernel_ms(sitrk_t *h, float *points_ms, float *cells_ms);
 
+/* ---- quadrangles from a triangulated buoy cloud --------------------------------
+ * An EXTRA the reference does not have: adjacent triangles of a triangulation (scipy's Delaunay on the host, or any (nT,3)
+ * list) are paired into strictly convex, near-rectangular quadrangles, the cells sitrk_deform_* takes with nv = 4.  The pairing
+ * is a deterministic greedy matching of maximum quality.  No parity claim is made against any other code; the contract below
+ * is this library's own.  Everything in fp64, one rounded operation per symbol in the order written, no fused
+ * multiply-add, no square root and no trigonometry.
+ * Points are (nP,2) [y,x] km; a point is a VALID vertex iff it is not masked and both coordinates are finite.  tris is (nT,3)
+ * int32 in either orientation.  A triangle is DEAD if a vertex is not valid, if two of its indices are equal, or if its signed
+ * shoelace sum A2 (the expression of sitrk_deform_cells, nv = 3) is 0 or not finite.  A vertex index outside [0, nP) is an
+ * error, not a dead triangle: SITRK_EINDEX with the number of offending triangles in sitrk_last_error (outputs unspecified);
+ * such an index is never dereferenced and the handle stays usable.
+ * A CANDIDATE is an undirected edge (p,q), p < q, that belongs to exactly two live triangles; an edge of three or more live
+ * triangles is no candidate.  With r and s the two apexes (r == s, the same triangle listed twice: no candidate) its quadrangle
+ * is the cycle r,p,s,q in CANONICAL form: started at its smallest index with the smaller of that vertex's two neighbours
+ * second, A2 evaluated (sitrk_deform_cells' expression, nv = 4, relative to vertex 0), and where A2 < 0 the second and fourth
+ * vertex exchanged and A2 evaluated again.  No candidate unless this A2 is > 0 and finite: the form is counter-clockwise with
+ * x to the right and y up.  Both triangles of a pair get the same form, so everything below has the same bits for both.
+ * With v_0..v_3 the canonical vertices, e_k = v_{k+1} - v_k (indices mod 4), L_k = e_k.x*e_k.x + e_k.y*e_k.y and at corner k
+ *     cr_k = e_{k-1}.x*e_k.y - e_{k-1}.y*e_k.x ;  d_k = (-e_{k-1}.x)*e_k.x + (-e_{k-1}.y)*e_k.y ;  n_k = L_{k-1}*L_k
+ *     s_k = d_k*|d_k| ;  q_k = (d_k*d_k)/n_k
+ * a candidate is ACCEPTABLE iff
+ *   1. cr_k > 0 at all four corners (strictly convex and simple),
+ *   2. s_k <= (cos_lo*|cos_lo|)*n_k and s_k >= (cos_hi*|cos_hi|)*n_k at all four corners (the signed square of the cosine is
+ *      monotone, so no root is needed; cos_lo >= cos_hi are the cosines of the smallest and the largest interior angle allowed),
+ *   3. min_k L_k >= (ratio_min*ratio_min) * max_k L_k,
+ *   4. area_min <= 0.5*A2 <= area_max  [km^2],
+ *   5. its score is finite.
+ * The SCORE is q = max_k q_k (q_0, then replaced by every q_k that compares greater): 0 for a rectangle, lower is better.
+ * MATCHING: the acceptable candidates are taken in ascending order of (q, p, q-index); a candidate is taken iff neither of its
+ * triangles has been taken.  The device reaches the same result in rounds: every untaken triangle picks the best remaining
+ * candidate among its edges whose other triangle is untaken, and a candidate picked from both sides is taken; the first round
+ * that takes nothing ends the matching (the globally best remaining candidate is always mutual).
+ * OUTPUT: quads (nQ,4) int32 in canonical form, ordered by the smaller triangle id of each pair; tri_quad (nT) int32 = the row
+ * of the quadrangle a triangle went into, -1 if it stayed single, -2 if it is dead; *nQ; *rounds = rounds run, the last, empty
+ * one included (0 for nT == 0).  quads has room for cap rows; cap < nT/2 -> SITRK_EINVAL before any device work, as are
+ * cosines outside [-1,1] or cos_lo < cos_hi, ratio_min outside [0,1], area_min > area_max (NaN included) and missing
+ * pointers.  More than nT/2 + 1 rounds cannot happen and would be SITRK_EINVAL.
+ *
+ * sitrk_tri2quad: host arrays yx (nP,2), mask (nP) int8 with 0 = no valid vertex (NULL: none masked).  Synchronous on the
+ * handle's stream; nT == 0 is valid.  Uses the context's transient scratch only: the grid, buoys and records of a tracker on
+ * the same handle are left as they were. */
+int sitrk_tri2quad(sitrk_t *h, int64_t nP, const double *yx, const int8_t *mask, int64_t nT, const int32_t *tris, double cos_lo,
+                   double cos_hi, double ratio_min, double area_min, double area_max, int64_t cap, int32_t *quads,
+                   int32_t *tri_quad, int64_t *nQ, int *rounds);
+/* The same on the device-resident buoys of sitrk_set_buoys at their current positions, indices in the caller's buoy order; a
+ * buoy is a valid vertex iff it is alive now.  Only tris go up and the result comes back; a re-sort changes nothing.
+ * SITRK_EINVAL without buoys. */
+int sitrk_tri2quad_buoys(sitrk_t *h, int64_t nT, const int32_t *tris, double cos_lo, double cos_hi, double ratio_min,
+                         double area_min, double area_max, int64_t cap, int32_t *quads, int32_t *tri_quad, int64_t *nQ,
+                         int *rounds);
+/* measurement: GPU time [ms] of the phases of the last sitrk_tri2quad / sitrk_tri2quad_buoys that ran to its end on this
+ * handle, from HIP events -- the triangle pass with the adjacency table, the scores, the rounds (their host read-backs
+ * included), the compaction; any pointer may be NULL */
+int sitrk_tri2quad_kernel_ms(sitrk_t *h, float *adjacency_ms, float *score_ms, float *rounds_ms, float *compact_ms);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

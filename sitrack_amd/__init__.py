@@ -14,5 +14,6 @@ from .ncio import (GetModelGrid, GetModelUVGrid, LoadNCtime, LoadNCdata, SeedFil
 from .seeding import SubSampCloud                                            # noqa: F401
 from .overlap import CancelTooClose                                          # noqa: F401
 from .deformation import DeformCells, lattice_cells                          # noqa: F401
+from .quadmesh import Tri2Quad                                                # noqa: F401
 from .coast import DistToCoast, MaskCoastal                                  # noqa: F401
 from . import synthetic                                                      # noqa: F401

@@ -76,6 +76,9 @@ _SIGNATURES = {
     "sitrk_deform_mark": (_int, [_vp, _int]),
     "sitrk_deform_since_mark": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_deform_kernel_ms": (_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sitrk_tri2quad": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_int)]),
+    "sitrk_tri2quad_buoys": (_int, [_vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_int)]),
+    "sitrk_tri2quad_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 4),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -597,6 +600,57 @@ class Context:
         a, b = C.c_float(0), C.c_float(0)
         self._chk(self._L.sitrk_deform_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- quadrangles from triangles (sitrk_tri2quad*)
+    @staticmethod
+    def _tris_arg(tris, name):
+        """(nT, 3) int32, C-contiguous; indices that do not fit int32 become -1 (the library reports them as out of range)"""
+        t = np.asarray(tris)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("%s: tris must be an (nT, 3) integer array, got shape %s" % (name, t.shape))
+        if t.dtype.kind not in "iu":
+            raise ValueError("%s: tris must hold integers, got %s" % (name, t.dtype))
+        t32 = as_c(t, np.int32)
+        if t32.dtype != t.dtype:
+            t32[t32 != t] = -1
+        return t32
+
+    def tri2quad(self, yx, tris, mask=None, cos_lo=0.5, cos_hi=-0.5, ratio_min=0.5, area_min=0., area_max=float("inf"), cap=None):
+        """sitrk_tri2quad: (quads (nQ,4) int32, tri_quad (nT,) int32, rounds) of the triangles tris (nT,3) over the points yx
+        (nP,2) km; mask: 0 = no valid vertex; cap: rows of room for quads (default nT // 2, the least the library takes)."""
+        yx = as_c(yx, np.float64)
+        nP = yx.shape[0]
+        yx = as_c(yx, np.float64, (nP, 2), "yx")
+        m = None if mask is None else as_c(np.asarray(mask) != 0, np.int8, (nP,), "mask")
+        t = self._tris_arg(tris, "tri2quad")
+        nT = t.shape[0]
+        cap = nT // 2 if cap is None else int(cap)
+        quads = np.empty((max(cap, 0), 4), dtype=np.int32)
+        tri_quad = np.empty(nT, dtype=np.int32)
+        nQ, rounds = _i64(0), _int(0)
+        self._chk(self._L.sitrk_tri2quad(self._h, nP, _ptr(yx), _ptr(m), nT, _ptr(t), float(cos_lo), float(cos_hi), float(ratio_min),
+                                         float(area_min), float(area_max), cap, _ptr(quads), _ptr(tri_quad), C.byref(nQ),
+                                         C.byref(rounds)))
+        return quads[:nQ.value].copy(), tri_quad, rounds.value
+
+    def tri2quad_buoys(self, tris, cos_lo=0.5, cos_hi=-0.5, ratio_min=0.5, area_min=0., area_max=float("inf"), cap=None):
+        """sitrk_tri2quad_buoys: the same on the buoys of set_buoys() at their current positions (alive = valid vertex), no
+        position leaving the device"""
+        t = self._tris_arg(tris, "tri2quad_buoys")
+        nT = t.shape[0]
+        cap = nT // 2 if cap is None else int(cap)
+        quads = np.empty((max(cap, 0), 4), dtype=np.int32)
+        tri_quad = np.empty(nT, dtype=np.int32)
+        nQ, rounds = _i64(0), _int(0)
+        self._chk(self._L.sitrk_tri2quad_buoys(self._h, nT, _ptr(t), float(cos_lo), float(cos_hi), float(ratio_min), float(area_min),
+                                               float(area_max), cap, _ptr(quads), _ptr(tri_quad), C.byref(nQ), C.byref(rounds)))
+        return quads[:nQ.value].copy(), tri_quad, rounds.value
+
+    def tri2quad_kernel_ms(self):
+        """(adjacency_ms, score_ms, rounds_ms, compact_ms): GPU time of the phases of the last tri2quad call (sitrk_tri2quad_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(4)]
+        self._chk(self._L.sitrk_tri2quad_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

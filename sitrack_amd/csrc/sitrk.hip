@@ -126,6 +126,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     free_buoys(h);
     deform_release(h, true);
     coast_release(h, false, true);
+    quadmesh_release(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);

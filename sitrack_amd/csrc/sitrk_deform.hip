@@ -125,6 +125,13 @@ void deform_release(sitrk_ctx *h, bool destroy)
         }
 }
 
+int deform_points_now(sitrk_ctx *h, pt *out)
+{
+    hipLaunchKernelGGL(deform_points_kernel, dim3(nblk(h->nP)), dim3(kDefThreads), 0, h->stream, h->nP, h->st[h->cur], false, true, 0, 0, out);
+    HIPCHK(hipGetLastError());
+    return SITRK_OK;
+}
+
 }  // namespace sitrk
 
 using namespace sitrk;

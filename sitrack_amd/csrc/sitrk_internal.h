@@ -219,6 +219,10 @@ struct sitrk_ctx {
 
     sitrk::CoastState coast;            // distance to the coastline (sitrk_coast.hip)
 
+    // quadrangles from triangles (sitrk_quadmesh.hip): events around the phases of the last call -- adjacency, scores, rounds, compaction
+    hipEvent_t quad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool quad_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -238,6 +242,11 @@ int slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev);
 // sitrk_deform.hip: frees the snapshot of sitrk_deform_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timing
 // events too
 void deform_release(sitrk_ctx *h, bool destroy);
+// ... and queues its pass over the buoys on the compute stream: out (nP) = every buoy's position in the caller's order, NaN in y
+// for a buoy that is not alive now (sitrk_quadmesh.hip)
+int deform_points_now(sitrk_ctx *h, pt *out);
+// sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
+void quadmesh_release(sitrk_ctx *h);
 // sitrk_coast.hip: frees the coast index (sitrk_destroy: the timing events too); grid_changed = only an index that was built from
 // the context's grid (sitrk_set_grid)
 void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy);

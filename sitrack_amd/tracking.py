@@ -258,6 +258,14 @@ class IceTracker:
         out, valid, _ = self.ctx.deform_since_mark(jrec1, cells)
         return _as_dict(out, valid)
 
+    def quads(self, tris, angles=(60., 120.), ratio_min=0.5, area=(0., float("inf"))):
+        """Quadrangles (nQ,4) of buoy indices and tri_quad (nT,) from the triangles `tris` (nT,3) of buoy indices, at the buoys'
+        current device-resident positions; a buoy that is not alive is no vertex (an extra the reference does not have;
+        sitrk_tri2quad_buoys).  Arguments and result as sit.Tri2Quad; the rows go into deform() as they are."""
+        from .quadmesh import _params
+        quads, tri_quad, _ = self.ctx.tri2quad_buoys(tris, **_params('ERROR [IceTracker.quads()]: ', tris, angles, ratio_min, area))
+        return quads, tri_quad
+
     def dist2coast(self, rmax_km=None, return_seg=False):
         """Distance [km, polar-stereographic plane] of every buoy, alive or not, to the coastline of the tracker's own mesh, from
         the device-resident positions, in the caller's order (an extra the reference does not have; sitrk_coast_dist_buoys).
