@@ -715,6 +715,107 @@ def test_row_band_ingest_equals_full_ingest(fdt):
         assert np.array_equal(res["band"][key], res["full"][key]), key
     assert not np.isnan(res["band"]["yx"]).any() and 0 < res["band"]["iAlive"].sum() < len(res["band"]["iAlive"])
 
+def _write_slab(ctx, slot, u, v, sic, fdt):
+    """a record written in place into the slot's device memory, as an RCCL broadcast does"""
+    import torch
+    from sitrack_amd import distributed as sd
+    ctx.sync()
+    sd.slot_tensor(ctx, slot).copy_(torch.from_numpy(sd.pack_slab(u, v, sic, fdt)))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("fdt", [np.float32, np.float64])
+@pytest.mark.parametrize("mode", ["commit", "commit_rows", "dev"])
+def test_records_that_arrive_in_device_memory_equal_full_ingest(fdt, mode):
+    """The set-up of test_row_band_ingest_equals_full_ingest with the record delivered in device memory: the whole slab written
+    in place and committed (`sitrk_commit_record`), the slab written with everything outside the buoys' band poisoned and only
+    the band committed (`sitrk_commit_record_rows`), a [u|v|sic] slab elsewhere on the device handed over by pointer
+    (`sitrk_push_record_dev`).  Trajectories equal those of full host uploads bit for bit."""
+    import torch
+    from sitrack_amd import distributed as sd
+    Nj, Ni = 200, 96
+    grid = syn.make_grid(Nj, Ni, dkm=4.0, warp=1.0)
+    K, Nt = 6, 45
+    u, v, sic = syn.make_fields(grid, K=K, seed=21, umax=1.1, drift=0.7, ripple=0.1, dtype=fdt)   # fast: ~1 cell per record
+    tmask = grid["tmask"].copy(); tmask[88:92, 30:50] = 0
+    sic[:, 60:70, 10:30] = 0.03
+    _, yx = syn.make_buoys(grid, 15000, seed=12, frac=0.9)
+    yx = yx[np.abs(yx[:, 0]) < 120.]                         # a band of rows in the middle of the mesh
+    res = {}
+    for ingest in ("full", mode):
+        trk = make_tracker(grid, tmask, 1, field_dtype=fdt)
+        ctx = trk.ctx
+        found, ji, _ = sit.FindContainingCell(yx, syn.nearest_t_plane(grid, yx), ctx=ctx)
+        trk.set_buoys(yx[found], ji[found])
+        bands = []
+        for s in range(Nt):
+            k = s % K
+            if ingest == "full":
+                ctx.push_record(0, u[k], v[k], sic[k])
+            elif ingest == "commit":
+                _write_slab(ctx, 0, u[k], v[k], sic[k], fdt)
+                ctx.commit_record(0)
+            elif ingest == "commit_rows":
+                j0, j1 = ctx.band()
+                bands.append((j0, j1))
+                comp = [np.full((Nj, Ni), np.nan, dtype=fdt), np.full((Nj, Ni), np.nan, dtype=fdt), np.zeros((Nj, Ni), dtype=fdt)]
+                for dst, src in zip(comp, (u[k], v[k], sic[k])):
+                    dst[j0:j1] = src[j0:j1]
+                _write_slab(ctx, 0, *comp, fdt)
+                ctx.commit_record_rows(0, j0, j1)
+            else:
+                t = torch.from_numpy(sd.pack_slab(u[k], v[k], sic[k], fdt)).to("cuda:0")
+                torch.cuda.synchronize()
+                ctx.push_record_dev(0, t.data_ptr())
+            trk.step(s, 0)
+            if ingest == "dev":
+                ctx.sync()                                   # the library's copy out of `t` is done before torch may reuse it
+                del t
+        res[ingest] = trk.state()
+        if ingest == "commit_rows":
+            assert max(b[1] - b[0] for b in bands) < 0.8 * Nj and bands[0] != bands[-1]      # a real band, and it moved
+        trk.close()
+    for key in ("yx", "vJIt", "iAlive", "kill_rec"):
+        assert np.array_equal(res[mode][key], res["full"][key]), key
+    assert not np.isnan(res[mode]["yx"]).any() and 0 < res[mode]["iAlive"].sum() < len(res[mode]["iAlive"])
+
+
+def test_committed_rows_are_checked_against_the_buoys_band():
+    """test_partly_uploaded_slot_is_checked_against_the_buoys_band for a band committed in device memory
+    (`sitrk_commit_record_rows`): a step whose buoys can reach outside it fails with SITRK_EINVAL and the handle stays usable."""
+    Nj, Ni = 120, 64
+    grid = syn.make_grid(Nj, Ni, dkm=4.0, warp=0.0)
+    u, v, sic = syn.make_fields(grid, K=2, seed=2, umax=0.5)
+    _, yx = syn.make_buoys(grid, 5000, seed=4, frac=0.5)
+    trk, ref = make_tracker(grid, grid["tmask"], 1), make_tracker(grid, grid["tmask"], 1)
+    try:
+        found, ji, _ = sit.FindContainingCell(yx, syn.nearest_t_plane(grid, yx), ctx=trk.ctx)
+        for t in (trk, ref):
+            t.set_buoys(yx[found], ji[found])
+        ctx = trk.ctx
+        jlo, jhi = int(ji[found][:, 0].min()), int(ji[found][:, 0].max())
+        _write_slab(ctx, 0, u[0], v[0], sic[0], np.float32)
+        ctx.commit_record_rows(0, jlo - 2, jhi + 3)
+        assert ctx._L.sitrk_step(ctx._h, 0, 0) == -1 and b"sitrk_buoy_rows" in ctx._L.sitrk_last_error(ctx._h)   # band never evaluated
+        assert ctx.buoy_rows() == (jlo, jhi)
+        ctx.step(0, 0)                                       # exactly the band: fine
+        _write_slab(ctx, 0, u[1], v[1], sic[1], np.float32)
+        ctx.commit_record_rows(0, jlo - 2, jhi + 3)
+        assert ctx._L.sitrk_step(ctx._h, 0, 1) == -1 and b"can touch rows" in ctx._L.sitrk_last_error(ctx._h)    # SITRK_EINVAL: one row short
+        with pytest.raises(sit.SitrkError, match="rows out of range"):
+            ctx.commit_record_rows(0, 0, Nj + 1)
+        ctx.commit_record_rows(0, jlo - 3, jhi + 4)          # the handle goes on: the band one row wider, and the step runs
+        ctx.step(0, 1)
+        for k in range(2):
+            ref.ctx.push_record(0, u[k], v[k], sic[k])
+            ref.step(k, 0)
+        a, b = trk.state(), ref.state()
+        for key in ("yx", "vJIt", "iAlive", "kill_rec"):
+            assert np.array_equal(a[key], b[key]), key
+    finally:
+        trk.close(); ref.close()
+
+
 @pytest.mark.parametrize("fdt", [np.float32, np.float64])
 @pytest.mark.parametrize("Ni,tile", [(160, 0), (160, 1), (158, 0)])
 @pytest.mark.parametrize("mode", ["step", "run", "commit", "commit_run", "commit_run_async"])
@@ -1071,6 +1172,96 @@ def test_tuning_knobs_do_not_change_results():
             assert np.array_equal(r[key], res[0][key])
     with pytest.raises(sit.SitrkError):
         sit.Context(0).set_tuning(bogus=1)
+
+
+@pytest.mark.parametrize("strat", [1, 0, 2])
+@pytest.mark.parametrize("windowed", [False, True])
+@pytest.mark.parametrize("fdt", [np.float32, np.float64])
+def test_step_block_sizes_do_not_change_results(fdt, windowed, strat):
+    """The knob `step_block` picks the workgroup size of the one-record kernel: 256 and 1024 against the default 512, record by
+    record, bit for bit; one combination against the oracle as well.  (The set-up of test_tuning_knobs_do_not_change_results, with a
+    hole in the mask and a patch of open water so that buoys die.)"""
+    grid = syn.make_grid(128, 160, dkm=4.0, warp=1.0)
+    K, Nt = 3, 14
+    u, v, sic = syn.make_fields(grid, K=K, seed=8, umax=0.7, drift=0.2, ripple=0.1, dtype=fdt)
+    tmask = grid["tmask"].copy(); tmask[60:66, 70:84] = 0
+    sic[:, 30:40, 40:70] = 0.02
+    _, yx = syn.make_buoys(grid, 30011, seed=21, frac=0.7)
+    rng = np.random.default_rng(5)
+    res, first, last = [], None, None
+    for bs in (512, 256, 1024):
+        trk = make_tracker(grid, tmask, K, field_dtype=fdt, iUVstrategy=strat)
+        if bs != 512:
+            trk.ctx.set_tuning(step_block=bs)
+        if not res:
+            found, ji, _ = sit.FindContainingCell(yx, syn.nearest_t_plane(grid, yx), ctx=trk.ctx)
+            yx, ji = yx[found], ji[found]
+            n = len(yx)
+            assert n > 29000 and n % 256 != 0 and n % 1024 != 0 and n > 1024
+            if windowed:
+                first, last = rng.integers(0, 4, n), Nt - 1 - rng.integers(0, 4, n)
+        trk.set_buoys(yx, ji, first, last)
+        trk.ctx.set_resort(6)
+        for k in range(K):
+            trk.load_record(k, u[k], v[k], sic[k])
+        trk.ctx.launch_stats(reset=True)
+        for jrec in range(Nt):
+            trk.step(jrec, jrec % K)
+        assert trk.ctx.launch_stats() == {"fused_launches": 0, "fused_records": 0, "step_launches": Nt}
+        res.append(trk.state())
+        trk.close()
+    for r in res[1:]:
+        for key in ("yx", "vJIt", "iAlive", "kill_rec"):
+            assert np.array_equal(r[key], res[0][key]), key
+    assert 0 < res[0]["iAlive"].sum() < len(yx)
+    if fdt == np.float32 and windowed and strat == 1:
+        g2 = dict(grid); g2["tmask"] = tmask
+        ref = orc.Tracker(g2, yx, ji, rec_first=first, rec_last=last, uv_strategy=strat, nthreads=8)
+        for jrec in range(Nt):
+            ref.step(jrec, u[jrec % K], v[jrec % K], sic[jrec % K], want_out=False)
+        for r in res:
+            assert np.array_equal(r["yx"], ref.pos) and np.array_equal(r["vJIt"], ref.jiT) and np.array_equal(r["iAlive"], ref.alive)
+        assert ref.ncross > len(yx) // 2
+
+
+def test_step_block_sizes_on_the_one_record_fallback_of_sub_stepping():
+    """Buoys set in the two outermost rows and columns (the rim set of test_rim_cells_and_negative_index_wrap plus an interior
+    cloud of more than one workgroup) with nsub = 3: the fused kernels do not apply, every record is three launches of the
+    one-record kernel -- at all three block sizes, with the same bits."""
+    Nj, Ni, nsub, Nt = 24, 26, 3, 5
+    grid = syn.make_grid(Nj, Ni, dkm=4.0, warp=1.0)
+    tmask = np.ones((Nj, Ni), dtype=np.int8)
+    u = np.full((Nj, Ni), -0.55, dtype=np.float32); v = np.full((Nj, Ni), -0.7, dtype=np.float32)
+    u[:, ::3] = 0.4; v[::4, :] = 0.3
+    sic = np.ones((Nj, Ni), dtype=np.float32)
+    ji = np.array([[1, i] for i in range(1, Ni - 1)] + [[j, 1] for j in range(2, Nj - 1)] + [[Nj - 2, i] for i in range(2, Ni - 1)]
+                  + [[j, Ni - 2] for j in range(2, Nj - 2)], dtype=np.int64)
+    yx = np.stack([grid["Yt"][ji[:, 0], ji[:, 1]], grid["Xt"][ji[:, 0], ji[:, 1]]], axis=1)
+    _, yin = syn.make_buoys(grid, 3001, seed=6, frac=0.6)
+    res = []
+    for bs in (512, 256, 1024):
+        trk = make_tracker(grid, tmask, 1, rdt=3600. * nsub, nsub=nsub)
+        if bs != 512:
+            trk.ctx.set_tuning(step_block=bs)
+        if not res:
+            ok, ji2, _ = sit.FindContainingCell(yx, ji, ctx=trk.ctx)
+            ok &= np.all(ji2 == ji, axis=1)                 # the rim points that lie in the cell of their own T-point
+            fin, jin, _ = sit.FindContainingCell(yin, syn.nearest_t_plane(grid, yin), ctx=trk.ctx)
+            yx, ji = np.concatenate([yx[ok], yin[fin]]), np.concatenate([ji[ok], jin[fin]])
+            rim = (ji[:, 0] < 2) | (ji[:, 0] > Nj - 3) | (ji[:, 1] < 2) | (ji[:, 1] > Ni - 3)
+            assert rim.sum() > 40 and len(yx) > 2 * 1024 and len(yx) % 256 != 0
+        trk.set_buoys(yx, ji)
+        trk.load_record(0, u, v, sic)
+        trk.ctx.launch_stats(reset=True)
+        for jrec in range(Nt):
+            trk.step(jrec, 0)
+        assert trk.ctx.launch_stats() == {"fused_launches": 0, "fused_records": 0, "step_launches": Nt * nsub}
+        res.append(trk.state())
+        trk.close()
+    for r in res[1:]:
+        for key in ("yx", "vJIt", "iAlive", "kill_rec"):
+            assert np.array_equal(r[key], res[0][key]), key
+    assert 10 < (res[0]["iAlive"] == 0).sum() < len(yx)
 
 
 def test_find_cells_matches_golden(golden, ctx):
