@@ -121,7 +121,7 @@ int sitrk_set_substeps(sitrk_t *h, int nsub);
  * consecutive resident records advanced per launch by sitrk_run (loop interchange: the buoys are independent, each lane keeps
  * its buoy in registers across the records); "subsample_block" (256..4096, powers of two, default 1024): points per workgroup of
  * sitrk_subsample_cloud's resolve kernel; "coast_bin" (1..64, default 4): bin side of the next sitrk_coast_build, in quarters of
- * sqrt(bounding-box area / segments);
+ * sqrt(bounding-box area / segments); "delaunay_bin" (1..4, default 3): cells per reach of the next sitrk_delaunay;
  * "lanes" (1/2, default 2) / "lane_min_wg" (>= 1, default 7168): with lanes = 2, sitrk_run splits the cell-sorted buoys into two
  * contiguous lanes (cut at a multiple of 256 * 8 * xcd_group buoys) and queues each lane's fused launches on a stream of its own
  * -- lane 0 on the compute stream, lane 1 on the ingest stream, its first launch half as long, so that the lanes' launch
@@ -387,8 +387,8 @@ int sitrk_deform_since_mark(sitrk_t *h, int jrec1, int64_t nC, int nv, const int
 int sitrk_deform_kernel_ms(sitrk_t *h, float *points_ms, float *cells_ms);
 
 /* ---- quadrangles from a triangulated buoy cloud --------------------------------
- * An EXTRA the reference does not have: adjacent triangles of a triangulation (scipy's Delaunay on the host, or any (nT,3)
- * list) are paired into strictly convex, near-rectangular quadrangles, the cells sitrk_deform_* takes with nv = 4.  The pairing
+ * An EXTRA the reference does not have: adjacent triangles of a triangulation (sitrk_delaunay below, scipy's Delaunay on the
+ * host, or any (nT,3) list) are paired into strictly convex, near-rectangular quadrangles, the cells sitrk_deform_* takes with nv = 4.  The pairing
  * is a deterministic greedy matching of maximum quality.  No parity claim is made against any other code; the contract below
  * is this library's own.  Everything in fp64, one rounded operation per symbol in the order written, no fused
  * multiply-add, no square root and no trigonometry.
@@ -440,6 +440,52 @@ int sitrk_tri2quad_buoys(sitrk_t *h, int64_t nT, const int32_t *tris, double cos
  * handle, from HIP events -- the triangle pass with the adjacency table, the scores, the rounds (their host read-backs
  * included), the compaction; any pointer may be NULL */
 int sitrk_tri2quad_kernel_ms(sitrk_t *h, float *adjacency_ms, float *score_ms, float *rounds_ms, float *compact_ms);
+
+/* ---- bounded Delaunay triangulation of a buoy cloud ------------------------------
+ * An EXTRA the reference does not have: the triangles sitrk_tri2quad pairs, made on the device.  Every Delaunay triangle of the
+ * cloud whose circumradius is at most rmax_km -- the full triangulation without the hull triangles that span open water and
+ * land.  Such a triangle is decided by the points within 2*rmax_km of its vertices, so there is no global structure.  No parity
+ * claim is made against any other code; the contract below is this library's own, pure integer mathematics.
+ * Points are (nP,2) [y,x] km.  A point is a VERTEX iff it is not masked, both coordinates are finite, and no lower-indexed
+ * vertex has the same integer coordinates Y = rint(y*2^20), X = rint(x*2^20) (int64; the scaling is exact, the rounding to
+ * nearest-even).  |coordinate| > 2^30 km on an unmasked finite point is SITRK_EINVAL, the first such index named in
+ * sitrk_last_error.  All predicates act on integer differences and are evaluated EXACTLY:
+ *     orient(a,b,c)     = (Xb-Xa)*(Yc-Ya) - (Yb-Ya)*(Xc-Xa)        > 0: counter-clockwise with x to the right and y up
+ *     incircle(a,b,c,d) = the 3x3 determinant of the rows (dx, dy, dx*dx+dy*dy) of a, b, c relative to d
+ *                                                                   > 0: d strictly inside the circle of the ccw triangle abc
+ * A row (p,q,r) of vertices is a triangle of the result iff
+ *   1. p < q, p < r and orient(p,q,r) > 0;
+ *   2. SIZE: with ux,uy = q-p, vx,vy = r-p, wx,wy = r-q (int64), la, lb, lc the three dx*dx+dy*dy, each exact in int64 and then
+ *      converted to fp64 once, A2 = (double)orient(p,q,r), ru = rmax_km*1048576.0 and R4 = 4.0*(ru*ru):
+ *      (la*lb)*lc <= (R4*A2)*A2, one rounded fp64 operation per symbol, no fused multiply-add (circumradius <= rmax_km without
+ *      a root or a division);
+ *   3. REACH: la <= R4, lb <= R4 and lc <= R4 (implied by 2 up to rounding; stated so that the candidates are exactly bounded);
+ *   4. EMPTY CIRCLE: no vertex s has incircle(p,q,r,s) > 0;
+ *   5. TIES: every vertex s outside {p,q,r} with incircle(p,q,r,s) == 0 has p < s and orient(q,r,s) > 0: a cocircular empty
+ *      polygon is triangulated as the fan from its lowest index, and q->r is an edge of that polygon.
+ * OUTPUT: tris (nT,3) int32, rows as above in ascending order of (p,q) -- a pair (p,q) has at most one r; *nT; vertex (nP)
+ * int8, may be NULL: 1 for a vertex, 0 for a masked or non-finite point, 2 for a duplicate of a lower index.
+ * nT <= max(0, 2*nV - 5) with nV the number of vertices.  tris has room for cap rows: cap < *nT writes only *nT (and vertex)
+ * and returns SITRK_OK, the convention of sitrk_coast_segments.  rmax_km must be finite and in (0, 500], which keeps every
+ * difference the predicates see below 2^30; NaN and values outside are SITRK_EINVAL before any device work, as are a missing
+ * nT, a missing tris with cap > 0 and a missing yx.  The result never depends on the knob "delaunay_bin" (1..4, default 3:
+ * square cells of side reach/delaunay_bin, 2*delaunay_bin+1 cells a side searched).
+ *
+ * sitrk_delaunay: host arrays yx (nP,2), mask (nP) int8 with 0 = masked (NULL: none).  Synchronous on the handle's stream;
+ * nP == 0 is valid.  Uses the context's transient scratch only: the grid, buoys and records of a tracker on the same handle are
+ * left as they were. */
+int sitrk_delaunay(sitrk_t *h, int64_t nP, const double *yx, const int8_t *mask, double rmax_km, int64_t cap, int32_t *tris,
+                   int64_t *nT, int8_t *vertex);
+/* The same on the device-resident buoys of sitrk_set_buoys at their current fp64 positions, indices in the caller's buoy order;
+ * a buoy can be a vertex iff it is alive now.  Nothing but the result comes down; a re-sort changes nothing.  SITRK_EINVAL
+ * without buoys. */
+int sitrk_delaunay_buoys(sitrk_t *h, double rmax_km, int64_t cap, int32_t *tris, int64_t *nT, int8_t *vertex);
+/* measurement: GPU time [ms] of the phases of the last sitrk_delaunay / sitrk_delaunay_buoys that ran its kernels on this
+ * handle, from HIP events -- binning (quantisation with the host's read of the bounding box, keys, sort, duplicates), the
+ * triangle kernel, the compaction (sort of the rows by (p,q)); any pointer may be NULL */
+int sitrk_delaunay_kernel_ms(sitrk_t *h, float *bin_ms, float *tri_ms, float *compact_ms);
+/* ... and the in-circle tests of that call: all of them, and those whose sign the fp64 filter left to the 128-bit form */
+int sitrk_delaunay_stats(sitrk_t *h, int64_t *incircle_tests, int64_t *exact_tests);
 
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,

@@ -15,5 +15,6 @@ from .seeding import SubSampCloud                                            # n
 from .overlap import CancelTooClose                                          # noqa: F401
 from .deformation import DeformCells, lattice_cells                          # noqa: F401
 from .quadmesh import Tri2Quad                                                # noqa: F401
+from .delaunay import DelaunayTris                                           # noqa: F401
 from .coast import DistToCoast, MaskCoastal                                  # noqa: F401
 from . import synthetic                                                      # noqa: F401

@@ -79,6 +79,10 @@ _SIGNATURES = {
     "sitrk_tri2quad": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_int)]),
     "sitrk_tri2quad_buoys": (_int, [_vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_int)]),
     "sitrk_tri2quad_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 4),
+    "sitrk_delaunay": (_int, [_vp, _i64, _vp, _vp, _dbl, _i64, _vp, C.POINTER(_i64), _vp]),
+    "sitrk_delaunay_buoys": (_int, [_vp, _dbl, _i64, _vp, C.POINTER(_i64), _vp]),
+    "sitrk_delaunay_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_delaunay_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -651,6 +655,46 @@ class Context:
         v = [C.c_float(0) for _ in range(4)]
         self._chk(self._L.sitrk_tri2quad_kernel_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # -- bounded Delaunay triangulation (sitrk_delaunay*)
+    def _delaunay_call(self, call, nP, cap):
+        """runs call(cap, tris, nT, vertex) with room for cap rows (default: the bound 2 nP, cut to what came back)"""
+        rows = max(0, 2 * nP - 5) if cap is None else int(cap)
+        tris = np.empty((max(rows, 0), 3), dtype=np.int32)
+        vertex = np.zeros(nP, dtype=np.int8)
+        nT = _i64(0)
+        self._chk(call(rows, _ptr(tris), C.byref(nT), _ptr(vertex)))
+        if nT.value > rows:
+            return None, nT.value, vertex
+        return tris[:nT.value].copy(), nT.value, vertex
+
+    def delaunay(self, yx, rmax_km, mask=None, cap=None):
+        """sitrk_delaunay: (tris (nT,3) int32, nT, vertex (nP,) int8) of the points yx (nP,2) km: every Delaunay triangle of
+        circumradius <= rmax_km, rows (p,q,r) counter-clockwise, p lowest, in ascending (p,q); mask: 0 = no vertex; cap: rows of
+        room (default 2 nP - 5, the most there can be); with cap < nT tris is None."""
+        yx = as_c(yx, np.float64)
+        nP = yx.shape[0]
+        yx = as_c(yx, np.float64, (nP, 2), "yx")
+        m = None if mask is None else as_c(np.asarray(mask) != 0, np.int8, (nP,), "mask")
+        return self._delaunay_call(lambda cap_, t, n, v: self._L.sitrk_delaunay(self._h, nP, _ptr(yx), _ptr(m), float(rmax_km), cap_, t, n, v),
+                                   nP, cap)
+
+    def delaunay_buoys(self, rmax_km, cap=None):
+        """sitrk_delaunay_buoys: the same on the buoys of set_buoys() at their current positions (alive = can be a vertex), no
+        position leaving the device"""
+        return self._delaunay_call(lambda cap_, t, n, v: self._L.sitrk_delaunay_buoys(self._h, float(rmax_km), cap_, t, n, v), self.nP, cap)
+
+    def delaunay_kernel_ms(self):
+        """(bin_ms, tri_ms, compact_ms): GPU time of the phases of the last delaunay call (sitrk_delaunay_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_delaunay_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def delaunay_stats(self):
+        """(in-circle tests, those that took the 128-bit path) of the last delaunay call (sitrk_delaunay_stats)"""
+        a, b = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_delaunay_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

@@ -127,6 +127,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     deform_release(h, true);
     coast_release(h, false, true);
     quadmesh_release(h);
+    delaunay_release(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
@@ -298,6 +299,11 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
     else if (!strcmp(knob, "coast_bin")) {           // bin side of the next sitrk_coast_build
         if (value < 1 || value > 64) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: coast_bin must be 1..64");
         h->coast_bin = value;
+        return SITRK_OK;
+    }
+    else if (!strcmp(knob, "delaunay_bin")) {        // cells per reach of the next sitrk_delaunay
+        if (value < 1 || value > 4) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: delaunay_bin must be 1..4");
+        h->delaunay_bin = value;
         return SITRK_OK;
     }
     else if (!strcmp(knob, "locate_bruteforce")) bit = TUNE_LOCATE_BRUTEFORCE;

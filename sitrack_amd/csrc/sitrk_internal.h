@@ -144,6 +144,7 @@ struct sitrk_ctx {
     int lane_min_wg = 7168;             // ... where the shorter lane keeps that many workgroups (4 rounds of 256 CUs x 7 workgroups)
     hipEvent_t lane_fork = nullptr, lane_join = nullptr;
     int coast_bin = 4;                  // sitrk_coast_build: bin side in quarters of sqrt(bounding-box area / segments), 1..64 (never changes results)
+    int delaunay_bin = 3;               // sitrk_delaunay: cells per reach (side = reach / delaunay_bin, 2*delaunay_bin+1 cells a side searched), 1..4 (never changes results)
     int subsample_block = 1024;         // sitrk_subsample_cloud: points per workgroup of its resolve kernel (never changes results)
     int fill_threads = 8;               // host threads copying a pushed record (>= 8 MB) into the pinned staging (2 / 4 / 8: 26 / 36 / 47 GB/s on the box rows of C3)
 
@@ -223,6 +224,12 @@ struct sitrk_ctx {
     hipEvent_t quad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool quad_timed = false;
 
+    // bounded Delaunay triangulation (sitrk_delaunay.hip): events around the phases of the last call -- binning, triangles,
+    // compaction -- and its in-circle tests, all of them / those that took the 128-bit path
+    hipEvent_t dl_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool dl_timed = false;
+    unsigned long long dl_tests = 0, dl_exact = 0;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -247,6 +254,8 @@ void deform_release(sitrk_ctx *h, bool destroy);
 int deform_points_now(sitrk_ctx *h, pt *out);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
 void quadmesh_release(sitrk_ctx *h);
+// sitrk_delaunay.hip: destroys the timing events (sitrk_destroy)
+void delaunay_release(sitrk_ctx *h);
 // sitrk_coast.hip: frees the coast index (sitrk_destroy: the timing events too); grid_changed = only an index that was built from
 // the context's grid (sitrk_set_grid)
 void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy);

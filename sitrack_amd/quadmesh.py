@@ -1,6 +1,6 @@
 """Quadrangles from a triangulated buoy cloud: host side of `sitrk_tri2quad` (sitrack_amd/csrc/sitrk_quadmesh.hip).
 
-An extra the reference does not have.  Adjacent triangles -- scipy's Delaunay of the cloud, or any (nT, 3) list -- are paired
+An extra the reference does not have.  Adjacent triangles -- `DelaunayTris` of the cloud, scipy's Delaunay, or any (nT, 3) list -- are paired
 into strictly convex, near-rectangular quadrangles by a deterministic greedy matching on the GPU; the quadrangles are the
 cells `DeformCells` takes.  The contract (canonical form, acceptance tests, score, order) is in include/sitrk.h and
 DESIGN.md 3.12.  There is no host version."""

@@ -266,6 +266,14 @@ class IceTracker:
         quads, tri_quad, _ = self.ctx.tri2quad_buoys(tris, **_params('ERROR [IceTracker.quads()]: ', tris, angles, ratio_min, area))
         return quads, tri_quad
 
+    def tris(self, rmax_km):
+        """Triangles (nT,3) of buoy indices: every Delaunay triangle of circumradius <= rmax_km of the buoys alive now, at their
+        current device-resident positions (an extra the reference does not have; sitrk_delaunay_buoys).  Rows as
+        sit.DelaunayTris; they go into quads() and deform() as they are."""
+        from .delaunay import _rmax
+        tris, _, _ = self.ctx.delaunay_buoys(_rmax('ERROR [IceTracker.tris()]: ', rmax_km))
+        return tris
+
     def dist2coast(self, rmax_km=None, return_seg=False):
         """Distance [km, polar-stereographic plane] of every buoy, alive or not, to the coastline of the tracker's own mesh, from
         the device-resident positions, in the caller's order (an extra the reference does not have; sitrk_coast_dist_buoys).

@@ -2,11 +2,12 @@
 """Quadrangles of buoys from a triangulation of one record of a trajectory file the tracker wrote, on the GPU (sitrk_tri2quad;
 contract in include/sitrk.h).
 
-    python tools/generate_quad_mesh.py -i TRACKFILE [-k K0] -t TRIS.npy|auto [--angles LO,HI --ratio R --area MIN,MAX] -o CELLS.npy
+    python tools/generate_quad_mesh.py -i TRACKFILE [-k K0] -t TRIS.npy|auto|gpu [--rmax KM] [--angles LO,HI --ratio R --area MIN,MAX] -o CELLS.npy
 
 TRIS.npy is an (nT, 3) integer array of `id_buoy` values, either orientation.  `-t auto` triangulates the valid positions of
-record K0 (Delaunay; needs scipy).  Adjacent triangles are paired into strictly convex quadrangles whose interior angles lie
-in [LO, HI] degrees (default 60,120), whose shortest side is at least R times the longest (default 0.5) and whose area lies in
+record K0 (Delaunay; needs scipy).  `-t gpu --rmax KM` triangulates them on the device: every Delaunay triangle whose
+circumradius is at most KM km (sitrk_delaunay), so no triangle spans open water or land wider than that.
+Adjacent triangles are paired into strictly convex quadrangles whose interior angles lie in [LO, HI] degrees (default 60,120), whose shortest side is at least R times the longest (default 0.5) and whose area lies in
 [MIN, MAX] km^2 (default: any), best pairs first.  CELLS.npy holds the (nQ, 4) `id_buoy` values of the quadrangles,
 counter-clockwise: what `tools/deformation.py -c CELLS.npy` takes as it is.  Validity comes from `mask` when the file has it,
 otherwise from the `_FillValue` of `y_pos`; a triangle with a buoy that is not valid at K0 pairs with nothing."""
@@ -22,6 +23,7 @@ sys.path.insert(0, ROOT)
 import sitrack_amd as sit                      # noqa: E402
 from sitrack_amd import ncio                   # noqa: E402
 from sitrack_amd.quadmesh import _params       # noqa: E402
+from sitrack_amd.delaunay import _rmax         # noqa: E402
 
 
 def _record(f, k, has_mask):
@@ -62,7 +64,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description='quadrangles of buoys from a triangulated record of a trajectory file (MI355X build)')
     ap.add_argument('-i', '--fin', required=True, help='trajectory file written by the tracker')
     ap.add_argument('-k', '--k0', type=int, default=0, help='record whose positions are meshed (default 0)')
-    ap.add_argument('-t', '--tris', required=True, help='(nT,3) .npy array of id_buoy values, or `auto` (Delaunay, needs scipy)')
+    ap.add_argument('-t', '--tris', required=True,
+                    help='(nT,3) .npy array of id_buoy values, `auto` (Delaunay on the host, needs scipy) or `gpu` (bounded Delaunay on the device, needs --rmax)')
+    ap.add_argument('--rmax', type=float, default=None, help='with `-t gpu`: largest circumradius of a triangle [km], in (0, 500]')
     ap.add_argument('--angles', default='60,120', help='smallest,largest interior angle [degrees] (default 60,120)')
     ap.add_argument('--ratio', type=float, default=0.5, help='shortest / longest side, at least (default 0.5)')
     ap.add_argument('--area', default='0,inf', help='smallest,largest area [km^2] (default 0,inf)')
@@ -75,6 +79,15 @@ def main(argv=None):
             _params('', np.zeros((0, 3), dtype=np.int32), **dict(dict(angles=(60., 120.), ratio_min=0.5, area=(0., float('inf'))), **kw))
         except ValueError as e:
             sys.exit('ERROR: %s: %s' % (opt, e))
+    if a.tris == 'gpu':
+        if a.rmax is None:
+            sys.exit('ERROR: `-t gpu` needs --rmax KM, the largest circumradius of a triangle')
+        try:
+            _rmax('', a.rmax)
+        except ValueError as e:
+            sys.exit('ERROR: --rmax: %s' % e)
+    elif a.rmax is not None:
+        sys.exit('ERROR: --rmax goes with `-t gpu` only')
     ncio.chck4f(a.fin)
     with ncio._Reader(a.fin) as f:
         for cv in ('time', 'id_buoy', 'y_pos', 'x_pos'):
@@ -86,8 +99,12 @@ def main(argv=None):
         k0 = a.k0 % nrec
         ids = np.asarray(f.var('id_buoy')).astype(np.int64)
         yx, ok = _record(f, k0, f.has_var('mask'))
+    ctx = None
     if a.tris == 'auto':
         cols = _auto_tris(yx, ok)
+    elif a.tris == 'gpu':
+        ctx = sit.Context(a.device)
+        cols = sit.DelaunayTris(yx, a.rmax, mask=ok, ctx=ctx)
     else:
         ncio.chck4f(a.tris)
         tri_ids = np.load(a.tris, allow_pickle=False)
@@ -100,7 +117,7 @@ def main(argv=None):
         if not hit.all():
             sys.exit('ERROR: id_buoy %d of %s is not in %s' % (tri_ids[~hit][0], a.tris, a.fin))
         cols = order[pos]
-    ctx = sit.Context(a.device)
+    ctx = ctx or sit.Context(a.device)
     try:
         quads, tri_quad = sit.Tri2Quad(yx, cols, mask=ok, angles=angles, ratio_min=a.ratio, area=area, ctx=ctx)
     finally:
