@@ -487,6 +487,55 @@ int sitrk_delaunay_kernel_ms(sitrk_t *h, float *bin_ms, float *tri_ms, float *co
 /* ... and the in-circle tests of that call: all of them, and those whose sign the fp64 filter left to the 128-bit form */
 int sitrk_delaunay_stats(sitrk_t *h, int64_t *incircle_tests, int64_t *exact_tests);
 
+/* ---- device-resident quadrangle meshes ------------------------------------------
+ * An EXTRA the reference does not have: the chain sitrk_delaunay_buoys -> sitrk_tri2quad_buoys -> sitrk_deform_mark /
+ * sitrk_deform_since_mark without a triangle, a quadrangle or a position moving to the host.  A context holds
+ * up to SITRK_MESH_MAX meshes, addressed by mesh in 0 .. SITRK_MESH_MAX-1.  A mesh is nQ quadrangles of buoy indices in the
+ * caller's order, (nQ,4) int32, the t0 positions of their vertices (64 B per quadrangle, in cell order), the model record jrec0
+ * those positions belong to and the pairing parameters it was built with, all in device allocations of the context's own:
+ * neither the transient scratch nor the record slots.  sitrk_set_buoys and sitrk_destroy free every mesh (the indices belong
+ * to the buoy set), sitrk_mesh_free frees one; a re-sort, sitrk_restore_state and every stepping entry point leave them alone.
+ *
+ * sitrk_mesh_build acts on the device-resident buoys at their current fp64 positions.  mask: host array (nP) int8 in the
+ * caller's order, NULL = all; a buoy is a point of the mesh iff it is alive now and its mask byte is not 0.  The quadrangles
+ * are, as integers and in the same order, what sitrk_tri2quad returns for the rows of sitrk_delaunay on (current positions,
+ * alive and mask, rmax_km) with the same five parameters; *nT and *rounds are the values those two calls give (any of nT, nQ,
+ * rounds may be NULL).  The t0 positions are the current ones; jrec0 = the model record that will be stepped next.  It replaces
+ * whatever the slot held; nQ == 0 is a valid, empty mesh.  Argument checks are those of sitrk_delaunay_buoys and
+ * sitrk_tri2quad_buoys, made before any device work, plus mesh out of range; SITRK_EINVAL without buoys.  Only the mask goes up;
+ * only the counters come back that the two host functions read too: the bounding box, the triangle count, one word per round.
+ * A call that fails leaves the slot as it was.
+ * sitrk_mesh_cells returns the (nQ,4) rows; cells has room for cap rows, cap < nQ writes only *nQ and returns SITRK_OK.
+ * sitrk_mesh_mark takes the t0 positions again for the same cells at the current positions, with a new jrec0; a vertex that is
+ * not alive now gets NaN, and its cells are invalid from then on.
+ * sitrk_mesh_deform is valid right after the step of jrec1 >= jrec0: t1 = the current positions, T = (jrec1 - jrec0 + 1) * rdt,
+ * a buoy is a valid vertex under the rule of sitrk_deform_since_mark.  out (5,nQ) fp64 = div, shr, vor, area0, area1: the
+ * contract of sitrk_deform_cells with nv = 4, the same bits as sitrk_deform_since_mark gives for the same cells after a
+ * sitrk_deform_mark at the same moment.  status (nQ) int8: 0 = invalid in that contract's sense, all five values SITRK_FILL;
+ * 1 = valid and acceptable at t1; 2 = valid, not acceptable at t1.  ACCEPTABLE AT t1 = the tests of sitrk_tri2quad on the four
+ * vertices in their stored order at their t1 positions with the mesh's own parameters: the t1 shoelace sum relative to vertex 0
+ * is > 0 and finite, tests 1-4 hold and the score is finite.  The stored order is canonical at t0 and is not made canonical
+ * again: a cell that has turned inside out fails the first test.
+ * stats is SITRK_MESH_NSTATS fp64: n0, n1, n2 = the number of cells of each status, then over the status-1 cells only
+ * sum(area0), sum(area1), sum(area0*div), sum(area0*shr) and sum(area0*tot^q) for q = 1, 2, 3, with tot = sqrt(div*div +
+ * shr*shr) and the terms formed as a*tot, (a*tot)*tot, ((a*tot)*tot)*tot: one rounded fp64 operation per symbol, no fused
+ * multiply-add.  The order of the sums is the implementation's but fixed (no floating-point atomics): two calls on the same
+ * state return the same bits.  Any of out, status, stats may be NULL, not all three; with only stats, 80 bytes come back and
+ * nothing else.  SITRK_EINVAL for an empty slot (never built, or freed), jrec1 < jrec0 and no buoys; an empty mesh (nQ == 0)
+ * returns zeros in stats. */
+#define SITRK_MESH_MAX 8
+#define SITRK_MESH_NSTATS 10
+int sitrk_mesh_build(sitrk_t *h, int mesh, int jrec0, double rmax_km, const int8_t *mask, double cos_lo, double cos_hi,
+                     double ratio_min, double area_min, double area_max, int64_t *nT, int64_t *nQ, int *rounds);
+int sitrk_mesh_cells(sitrk_t *h, int mesh, int64_t cap, int32_t *cells, int64_t *nQ);
+int sitrk_mesh_mark(sitrk_t *h, int mesh, int jrec0);
+int sitrk_mesh_deform(sitrk_t *h, int mesh, int jrec1, double *out, int8_t *status, double *stats);
+int sitrk_mesh_free(sitrk_t *h, int mesh);
+/* measurement: GPU time [ms] from HIP events of the last sitrk_mesh_build (its whole device chain, the host's reads of the
+ * counters included) and of the last sitrk_mesh_deform -- the pass over the buoys, the cell kernel, the final sum; any pointer
+ * may be NULL, SITRK_EINVAL for a phase that has not run */
+int sitrk_mesh_kernel_ms(sitrk_t *h, float *build_ms, float *points_ms, float *cells_ms, float *stats_ms);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

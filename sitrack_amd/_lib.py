@@ -21,6 +21,9 @@ SAMPLE_MAX_FIELDS = 8
 _SAMPLE_MODES = {"after": SAMPLE_AFTER, "enter": SAMPLE_ENTER, SAMPLE_AFTER: SAMPLE_AFTER, SAMPLE_ENTER: SAMPLE_ENTER}
 _SLOT_FIELDS = {"u": 0, "u_ice": 0, "v": 1, "v_ice": 1, "siconc": 2, "sic": 2, 0: 0, 1: 1, 2: 2}
 FillValue = -9999.0
+MESH_MAX = 8                                 # SITRK_MESH_MAX
+MESH_NSTATS = 10                             # SITRK_MESH_NSTATS, in this order:
+MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -83,6 +86,12 @@ _SIGNATURES = {
     "sitrk_delaunay_buoys": (_int, [_vp, _dbl, _i64, _vp, C.POINTER(_i64), _vp]),
     "sitrk_delaunay_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
     "sitrk_delaunay_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_mesh_build": (_int, [_vp, _int, _int, _dbl, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
+    "sitrk_mesh_cells": (_int, [_vp, _int, _i64, _vp, C.POINTER(_i64)]),
+    "sitrk_mesh_mark": (_int, [_vp, _int, _int]),
+    "sitrk_mesh_deform": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "sitrk_mesh_free": (_int, [_vp, _int]),
+    "sitrk_mesh_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 4),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -695,6 +704,64 @@ class Context:
         a, b = _i64(0), _i64(0)
         self._chk(self._L.sitrk_delaunay_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- device-resident quadrangle meshes (sitrk_mesh_*)
+    def mesh_build(self, mesh, jrec0, rmax_km, mask=None, cos_lo=0.5, cos_hi=-0.5, ratio_min=0.5, area_min=0., area_max=float("inf")):
+        """sitrk_mesh_build: (nT, nQ, rounds) of the mesh built in slot `mesh` from the buoys of set_buoys() at their current
+        positions: the bounded Delaunay triangles of the buoys alive now whose mask (nP, caller's order) is not 0, paired into
+        quadrangles; jrec0 = the model record stepped next.  No triangle, quadrangle or position leaves the device."""
+        m = None if mask is None else as_c(np.asarray(mask) != 0, np.int8, (self.nP,), "mask")
+        nT, nQ, rounds = _i64(0), _i64(0), _int(0)
+        self._chk(self._L.sitrk_mesh_build(self._h, int(mesh), int(jrec0), float(rmax_km), _ptr(m), float(cos_lo), float(cos_hi),
+                                           float(ratio_min), float(area_min), float(area_max), C.byref(nT), C.byref(nQ), C.byref(rounds)))
+        return nT.value, nQ.value, rounds.value
+
+    def mesh_cells(self, mesh):
+        """sitrk_mesh_cells: the quadrangles (nQ,4) int32 of buoy indices of the mesh in slot `mesh`"""
+        nQ = _i64(0)
+        self._chk(self._L.sitrk_mesh_cells(self._h, int(mesh), 0, None, C.byref(nQ)))
+        cells = np.empty((nQ.value, 4), dtype=np.int32)
+        if nQ.value:
+            self._chk(self._L.sitrk_mesh_cells(self._h, int(mesh), nQ.value, _ptr(cells), C.byref(nQ)))
+        return cells
+
+    def mesh_mark(self, mesh, jrec0):
+        """sitrk_mesh_mark: the same cells' t0 positions taken again at the current positions; jrec0 = the record stepped next"""
+        self._chk(self._L.sitrk_mesh_mark(self._h, int(mesh), int(jrec0)))
+
+    def mesh_deform(self, mesh, jrec1, want=("out", "status", "stats")):
+        """sitrk_mesh_deform, right after the step of jrec1: a dict with those of out (5, nQ) = div, shr, vor, area0, area1,
+        status (nQ,) int8 (0 invalid, 1 valid and acceptable at t1, 2 valid, not acceptable) and stats (MESH_NSTATS,) that `want`
+        names; only they come back from the device."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in ("out", "status", "stats")]
+        if bad or not want:
+            raise ValueError("mesh_deform: want must name some of 'out', 'status', 'stats', got %r" % (want,))
+        nQ = _i64(0)
+        if "out" in want or "status" in want:
+            self._chk(self._L.sitrk_mesh_cells(self._h, int(mesh), 0, None, C.byref(nQ)))
+        res = {}
+        if "out" in want:
+            res["out"] = np.empty((5, nQ.value), dtype=np.float64)
+        if "status" in want:
+            res["status"] = np.empty(nQ.value, dtype=np.int8)
+        if "stats" in want:
+            res["stats"] = np.zeros(MESH_NSTATS, dtype=np.float64)
+        self._chk(self._L.sitrk_mesh_deform(self._h, int(mesh), int(jrec1), _ptr(res.get("out")), _ptr(res.get("status")),
+                                            _ptr(res.get("stats"))))
+        return res
+
+    def mesh_free(self, mesh):
+        """sitrk_mesh_free: empties slot `mesh`"""
+        self._chk(self._L.sitrk_mesh_free(self._h, int(mesh)))
+
+    def mesh_kernel_ms(self, build=True, deform=True):
+        """(build_ms, points_ms, cells_ms, stats_ms): GPU time of the last mesh_build (whole device chain) and of the kernels of
+        the last mesh_deform (sitrk_mesh_kernel_ms); None for the part not asked for"""
+        v = [C.c_float(0) for _ in range(4)]
+        ask = [build, deform, deform, deform]
+        self._chk(self._L.sitrk_mesh_kernel_ms(self._h, *[C.byref(x) if a else None for x, a in zip(v, ask)]))
+        return tuple(x.value if a else None for x, a in zip(v, ask))
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

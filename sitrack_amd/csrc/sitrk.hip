@@ -68,6 +68,7 @@ static void free_buoys(sitrk_ctx *h)
     h->sort_tmp = nullptr; h->sort_tmp_bytes = 0;
     h->nP = 0;
     deform_release(h, false);           // the snapshot of sitrk_deform_mark belongs to these buoys
+    mesh_release(h, false);             // ... and so do the indices of every mesh
 }
 
 static void free_records(sitrk_ctx *h);
@@ -128,6 +129,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     coast_release(h, false, true);
     quadmesh_release(h);
     delaunay_release(h);
+    mesh_release(h, true);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);

@@ -7,13 +7,15 @@
 //                          16-byte point written per buoy in the caller's order.  A buoy that is no valid vertex gets NaN in y, so
 //                          the cell kernel needs no second gather for validity.  With check = false it is the plain snapshot of
 //                          sitrk_deform_mark.
-//   deform_cells_kernel<NV>  one cell per lane: its NV indices, then all 2 NV 16-byte gathers before any arithmetic, the contract,
+//   deform_cells_kernel<NV>  one cell per lane: its NV indices, then all 2 NV 16-byte gathers before any arithmetic, the contract (deform_rates of
+//                          sitrk_cellmath.h, which the cell kernel of sitrk_mesh.hip calls too),
 //                          5 fp64 stores and 1 byte store.  A vertex index outside [0, nP) is counted through a vector atomic and
 //                          never dereferenced; the drivers turn a non-zero count into SITRK_EINDEX.
 #include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sitrk_cellmath.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -23,9 +25,6 @@ namespace sitrk {
 namespace {
 
 constexpr int kDefThreads = 256;
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ bool finite64(double a) { return fabs(a) < __longlong_as_double(0x7ff0000000000000ll); }
 
 __global__ __launch_bounds__(kDefThreads) void deform_points_kernel(int64_t n, BuoyState st, bool windowed, bool check, int jrec0, int jrec1,
                                                                     pt *__restrict__ out)
@@ -76,36 +75,11 @@ __global__ __launch_bounds__(kDefThreads) void deform_cells_kernel(int64_t nC, i
 #pragma unroll
     for (int k = 0; k < NV; k++) b[k] = p1[idx[k]];
 
-    bool ok = in_range;
-#pragma unroll
-    for (int k = 0; k < NV; k++) ok = ok && finite64(a[k].y) && finite64(a[k].x) && finite64(b[k].y) && finite64(b[k].x);
-
-    double dx[NV], dy[NV], ex[NV], ey[NV], u[NV], v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        dx[k] = a[k].x - a[0].x; dy[k] = a[k].y - a[0].y;
-        ex[k] = b[k].x - b[0].x; ey[k] = b[k].y - b[0].y;
-        u[k] = (b[k].x - a[k].x) / T; v[k] = (b[k].y - a[k].y) / T;
-    }
-    double A2 = 0.0, B2 = 0.0, Suy = 0.0, Sux = 0.0, Svy = 0.0, Svx = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        const int q = (k + 1) % NV;
-        A2 = A2 + (dx[k] * dy[q] - dx[q] * dy[k]);
-        B2 = B2 + (ex[k] * ey[q] - ex[q] * ey[k]);
-        const double us = u[q] + u[k], vs = v[q] + v[k], ddy = dy[q] - dy[k], ddx = dx[q] - dx[k];
-        Suy = Suy + us * ddy; Sux = Sux + us * ddx;
-        Svy = Svy + vs * ddy; Svx = Svx + vs * ddx;
-    }
-    ok = ok && A2 != 0.0 && finite64(A2);
-    const double ux = Suy / A2, uy = -(Sux / A2), vx = Svy / A2, vy = -(Svx / A2);
-    const double e1 = ux - vy, e2 = uy + vx;
+    double r[5];
+    const bool ok = deform_rates<NV>(a, b, T, r) && in_range;          // the contract: sitrk_cellmath.h
     const double fill = SITRK_FILL;
-    out[c]          = ok ? ux + vy : fill;
-    out[nC + c]     = ok ? sqrt(e1 * e1 + e2 * e2) : fill;
-    out[2 * nC + c] = ok ? vx - uy : fill;
-    out[3 * nC + c] = ok ? 0.5 * fabs(A2) : fill;
-    out[4 * nC + c] = ok ? 0.5 * fabs(B2) : fill;
+#pragma unroll
+    for (int k = 0; k < 5; k++) out[k * nC + c] = ok ? r[k] : fill;
     valid[c] = ok ? 1 : 0;
 }
 
@@ -128,6 +102,14 @@ void deform_release(sitrk_ctx *h, bool destroy)
 int deform_points_now(sitrk_ctx *h, pt *out)
 {
     hipLaunchKernelGGL(deform_points_kernel, dim3(nblk(h->nP)), dim3(kDefThreads), 0, h->stream, h->nP, h->st[h->cur], false, true, 0, 0, out);
+    HIPCHK(hipGetLastError());
+    return SITRK_OK;
+}
+
+int deform_points_span(sitrk_ctx *h, int jrec0, int jrec1, pt *out)
+{
+    hipLaunchKernelGGL(deform_points_kernel, dim3(nblk(h->nP)), dim3(kDefThreads), 0, h->stream, h->nP, h->st[h->cur], h->windowed, true,
+                       jrec0, jrec1, out);
     HIPCHK(hipGetLastError());
     return SITRK_OK;
 }

@@ -38,8 +38,6 @@ constexpr int64_t kDlGone = (int64_t)1 << 62;      // coordinates of a point tha
 constexpr double kDlScale = 1048576.0;             // 2^20 units per km
 constexpr double kDlMaxKm = 1073741824.0;          // 2^30 km
 
-struct __attribute__((aligned(16))) ipt { int64_t y, x; };
-
 struct DlGrid {
     int64_t y0 = 0, x0 = 0, side = 1;   // cells of `side` units from (y0, x0)
     int64_t D = 0;                      // reach box: |dy|, |dx| <= D holds for every pair that passes the reach test
@@ -371,31 +369,24 @@ void delaunay_release(sitrk_ctx *h)
 
 using namespace sitrk;
 
-static int dl_check(sitrk_ctx *h, const char *fn, double rmax_km, int64_t cap, const int32_t *tris, const int64_t *nT)
+int sitrk::dl_check_rmax(sitrk_ctx *h, const char *fn, double rmax_km)
 {
     if (!std::isfinite(rmax_km) || !(rmax_km > 0.0) || rmax_km > 500.0)
         return fail(h, SITRK_EINVAL, "%s: rmax_km must be finite and in (0, 500] (got %g)", fn, rmax_km);
+    return SITRK_OK;
+}
+
+static int dl_check(sitrk_ctx *h, const char *fn, double rmax_km, int64_t cap, const int32_t *tris, const int64_t *nT)
+{
+    RCCHK(dl_check_rmax(h, fn, rmax_km));
     if (!nT) return fail(h, SITRK_EINVAL, "%s: null nT", fn);
     if (cap < 0) return fail(h, SITRK_EINVAL, "%s: cap must be >= 0", fn);
     if (cap > 0 && !tris) return fail(h, SITRK_EINVAL, "%s: null array", fn);
     return SITRK_OK;
 }
 
-// Everything behind the points: d_pts (nP; masked by d_mask when given) is on the device and the stream is behind what made it.
 // The layout of the scratch behind d_pts / d_mask is carved by the caller through dl_carve.
-namespace {
-struct DlBuffers {
-    ipt *xy, *xys, *xyv;
-    uint32_t *k0, *k1;
-    int32_t *v0, *perm, *cbeg, *rval0, *rval1, *tris;
-    int8_t *vertex;
-    unsigned long long *rkey0, *rkey1;
-    long long *red;
-    char *sort_tmp;
-    size_t sort_bytes;
-};
-
-int dl_sort_bytes(sitrk_ctx *h, int64_t nP, size_t *bytes)
+int sitrk::dl_sort_bytes(sitrk_ctx *h, int64_t nP, size_t *bytes)
 {
     size_t b32 = 0, b64 = 0;
     HIPCHK(sort_pairs_u32(nullptr, &b32, nullptr, nullptr, nullptr, nullptr, (size_t)nP, 32, h->stream));
@@ -404,7 +395,7 @@ int dl_sort_bytes(sitrk_ctx *h, int64_t nP, size_t *bytes)
     return SITRK_OK;
 }
 
-void dl_carve(Carver &c, DlBuffers &b, int64_t nP)
+void sitrk::dl_carve(Carver &c, DlBuffers &b, int64_t nP)
 {
     const size_t n = (size_t)nP, rows = 2 * n;           // nT <= 2 nV - 5
     c.take(b.xy, n); c.take(b.xys, n); c.take(b.xyv, n);
@@ -416,10 +407,11 @@ void dl_carve(Carver &c, DlBuffers &b, int64_t nP)
     c.take(b.red, 8);
     c.take(b.sort_tmp, b.sort_bytes);
 }
-}  // namespace
 
-static int dl_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, const int8_t *d_mask, const DlBuffers &b, double rmax_km,
-                  int64_t cap, int32_t *tris, int64_t *nT, int8_t *vertex)
+// The core: everything behind the points.  d_pts (nP; masked by d_mask when given) is on the device and the stream is behind what
+// made it; the rows stay in b.tris, the vertex bytes in b.vertex.
+int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, const int8_t *d_mask, const DlBuffers &b, double rmax_km,
+                   int64_t *nT)
 {
     const hipStream_t st = h->stream;
     h->dl_timed = false;
@@ -488,9 +480,17 @@ static int dl_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, con
     h->dl_tests = cnt[1];
     h->dl_exact = cnt[2];
     *nT = (int64_t)cnt[0];
-    if (cnt[0] && cap >= (int64_t)cnt[0]) HIPCHK(download(h, tris, b.tris, (size_t)3 * cnt[0]));
+    return SITRK_OK;
+}
+
+// The host entry points: the rows and the vertex bytes come down behind the core.
+static int dl_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, const int8_t *d_mask, const DlBuffers &b, double rmax_km,
+                  int64_t cap, int32_t *tris, int64_t *nT, int8_t *vertex)
+{
+    RCCHK(dl_core(h, fn, nP, d_pts, d_mask, b, rmax_km, nT));
+    if (*nT && cap >= *nT) HIPCHK(download(h, tris, b.tris, (size_t)3 * *nT));
     if (vertex) HIPCHK(download(h, vertex, b.vertex, (size_t)nP));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }
 

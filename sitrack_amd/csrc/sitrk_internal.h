@@ -71,6 +71,24 @@ struct CoastState {
     bool timed = false;
 };
 
+// Quadrangles from triangles (sitrk_quadmesh.hip): the acceptance parameters as the kernels take them
+struct QuadParams {
+    double c_lo2, c_hi2;        // cos_lo*|cos_lo|, cos_hi*|cos_hi|
+    double ratio2;              // ratio_min*ratio_min
+    double area_min, area_max;
+};
+
+// A device-resident quadrangle mesh (sitrk_mesh.hip): allocations of their own, neither the transient scratch nor the record slots
+struct Mesh {
+    bool built = false;                 // false: the slot is empty (never built, or freed)
+    int64_t nQ = 0;
+    int32_t *quads = nullptr;           // (nQ,4) buoy indices in the caller's order, canonical at t0
+    pt *t0 = nullptr;                   // (nQ,4) t0 positions of the vertices in cell order, 64 B per quadrangle; NaN in y: no valid vertex
+    int jrec0 = 0;                      // the model record those positions belong to (stepped next when they were taken)
+    double rmax_km = 0.0;
+    QuadParams par = {0.0, 0.0, 0.0, 0.0, 0.0};
+};
+
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
 // perm[s] = index of slot s in the caller's order.
 struct BuoyState {
@@ -230,6 +248,12 @@ struct sitrk_ctx {
     bool dl_timed = false;
     unsigned long long dl_tests = 0, dl_exact = 0;
 
+    // device-resident quadrangle meshes (sitrk_mesh.hip): freed with the buoys, whose indices they hold.  Events: [0],[1] around
+    // the device chain of the last build; [2]..[5] around the pass over the buoys, the cell kernel and the final sum of the last deform
+    sitrk::Mesh mesh[SITRK_MESH_MAX];
+    hipEvent_t mesh_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool mesh_build_timed = false, mesh_deform_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -252,6 +276,10 @@ void deform_release(sitrk_ctx *h, bool destroy);
 // ... and queues its pass over the buoys on the compute stream: out (nP) = every buoy's position in the caller's order, NaN in y
 // for a buoy that is not alive now (sitrk_quadmesh.hip)
 int deform_points_now(sitrk_ctx *h, pt *out);
+// ... and the pass of sitrk_deform_since_mark: NaN in y also for a buoy whose record window does not cover [jrec0, jrec1] (sitrk_mesh.hip)
+int deform_points_span(sitrk_ctx *h, int jrec0, int jrec1, pt *out);
+// sitrk_mesh.hip: frees every mesh (free_buoys of sitrk.hip); destroy = the timing events too
+void mesh_release(sitrk_ctx *h, bool destroy);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
 void quadmesh_release(sitrk_ctx *h);
 // sitrk_delaunay.hip: destroys the timing events (sitrk_destroy)
@@ -324,5 +352,47 @@ static hipError_t download(sitrk_ctx *h, void *dst_host, const T *src_dev, size_
 {
     return hipMemcpyAsync(dst_host, src_dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream);
 }
+
+// ---- the cores of sitrk_delaunay.hip and sitrk_quadmesh.hip: everything behind the points, rows left on the device.  The entry
+// points of those files add the download; sitrk_mesh_build runs both back to back out of one scratch layout.
+struct __attribute__((aligned(16))) ipt { int64_t y, x; };     // a point snapped to 2^-20 km
+struct DlBuffers {
+    ipt *xy, *xys, *xyv;
+    uint32_t *k0, *k1;
+    int32_t *v0, *perm, *cbeg, *rval0, *rval1, *tris;          // tris: (nT,3) rows of the result
+    int8_t *vertex;
+    unsigned long long *rkey0, *rkey1;
+    long long *red;
+    char *sort_tmp;
+    size_t sort_bytes;
+};
+int dl_check_rmax(sitrk_ctx *h, const char *fn, double rmax_km);
+int dl_sort_bytes(sitrk_ctx *h, int64_t nP, size_t *bytes);
+void dl_carve(Carver &c, DlBuffers &b, int64_t nP);
+// d_pts (nP; masked by d_mask when given) is on the device and the stream is behind what made it; *nT rows in b.tris, b.vertex filled
+int dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, const int8_t *d_mask, const DlBuffers &b, double rmax_km,
+            int64_t *nT);
+
+struct EdgeTable {
+    unsigned long long *key;    // all ones or p << 32 | q
+    unsigned long long *val;    // low 32 bits: triangles on the edge; high 32 bits: sum of their ids mod 2^32
+    uint64_t mask;              // slots - 1, slots a power of two
+};
+struct QuadBuffers {
+    int32_t *tris, *nbr, *mate, *pick, *quads, *tri_quad;      // quads (nQ,4), tri_quad (nT): the result
+    int8_t *live;
+    double *score;
+    unsigned *block_count;
+    int64_t *block_off;
+    EdgeTable tab;
+    uint64_t slots;
+};
+int quad_check_params(sitrk_ctx *h, const char *fn, double cos_lo, double cos_hi, double ratio_min, double area_min, double area_max);
+QuadParams quad_params(double cos_lo, double cos_hi, double ratio_min, double area_min, double area_max);
+void quad_carve(Carver &c, QuadBuffers &b, int64_t nT);        // room for nT triangles; the core takes any count up to it
+// d_pts (nP, NaN in y = no valid vertex) and the triangles d_tris (nT,3) are on the device and the stream is behind what made
+// them; *nQ rows in b.quads, b.tri_quad filled
+int quad_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, int64_t nT, const int32_t *d_tris, const QuadBuffers &b,
+              const QuadParams &c, int64_t *nQ, int *rounds);
 
 }  // namespace sitrk

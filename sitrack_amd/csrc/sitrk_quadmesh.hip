@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sitrk_cellmath.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -34,22 +35,6 @@ namespace {
 constexpr int kQmThreads = 256;
 constexpr int kQmBlock = 1024;                      // elements per workgroup of the compaction
 constexpr unsigned long long kQmEmpty = ~0ull;      // no edge key: p < q < 2^31
-
-struct QuadParams {
-    double c_lo2, c_hi2;        // cos_lo*|cos_lo|, cos_hi*|cos_hi|
-    double ratio2;              // ratio_min*ratio_min
-    double area_min, area_max;
-};
-
-struct EdgeTable {
-    unsigned long long *key;    // kQmEmpty or p << 32 | q
-    unsigned long long *val;    // low 32 bits: triangles on the edge; high 32 bits: sum of their ids mod 2^32
-    uint64_t mask;              // slots - 1, slots a power of two
-};
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double plus_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-__device__ __forceinline__ bool finite64(double a) { return fabs(a) < plus_inf(); }
 
 __device__ __forceinline__ uint64_t edge_slot(unsigned long long k, uint64_t mask)
 {
@@ -72,20 +57,7 @@ __global__ __launch_bounds__(kQmThreads) void quad_mask_kernel(int64_t n, const 
     if (mask[k] == 0) p[k].y = quiet_nan();
 }
 
-// signed shoelace sum of DESIGN.md 3.9 on four points, relative to the first
-__device__ __forceinline__ double shoelace4(const pt (&P)[4])
-{
-    double dx[4], dy[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { dx[k] = P[k].x - P[0].x; dy[k] = P[k].y - P[0].y; }
-    double A2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int q = (k + 1) % 4;
-        A2 = A2 + (dx[k] * dy[q] - dx[q] * dy[k]);
-    }
-    return A2;
-}
+// shoelace4() and quad_score() -- the signed area, the acceptance tests 1-4 and the score -- are in sitrk_cellmath.h
 
 // The cycle r, p, s, q (p < q the shared edge, r != s the apexes) in canonical form: started at its smallest index, then
 // counter-clockwise (A2 > 0).  false: A2 is 0, not finite or not positive after the turn.
@@ -105,40 +77,6 @@ __device__ __forceinline__ bool quad_canon(int32_t r, int32_t p, int32_t s, int3
         A2 = shoelace4(P);
     }
     return A2 > 0.0 && finite64(A2);
-}
-
-// acceptance tests 1-4 and the score on a canonical quadrangle; +inf: not acceptable
-__device__ __forceinline__ double quad_score(const pt (&P)[4], double A2, const QuadParams &c)
-{
-    double ex[4], ey[4], L[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int n = (k + 1) % 4;
-        ex[k] = P[n].x - P[k].x; ey[k] = P[n].y - P[k].y;
-        L[k] = ex[k] * ex[k] + ey[k] * ey[k];
-    }
-    bool ok = true;
-    double score = 0.0, lmin = L[0], lmax = L[0];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int m = (k + 3) % 4;                                    // e_{k-1}
-        const double cr = ex[m] * ey[k] - ey[m] * ex[k];
-        ok = ok && cr > 0.0;
-        const double ax = -ex[m], ay = -ey[m];
-        const double d = ax * ex[k] + ay * ey[k];
-        const double n = L[m] * L[k];
-        const double s = d * fabs(d);
-        ok = ok && s <= c.c_lo2 * n && s >= c.c_hi2 * n;
-        const double qk = (d * d) / n;
-        if (k == 0 || qk > score) score = qk;
-        if (L[k] < lmin) lmin = L[k];
-        if (L[k] > lmax) lmax = L[k];
-    }
-    ok = ok && lmin >= c.ratio2 * lmax;
-    const double area = 0.5 * A2;
-    ok = ok && c.area_min <= area && area <= c.area_max;
-    ok = ok && score < plus_inf();                                    // a NaN or infinite score orders nothing
-    return ok ? score : plus_inf();
 }
 
 __global__ __launch_bounds__(kQmThreads) void quad_tri_kernel(int64_t nT, int64_t nP, const int32_t *__restrict__ tris,
@@ -385,39 +323,35 @@ void quadmesh_release(sitrk_ctx *h)
 
 using namespace sitrk;
 
-static int quad_check(sitrk_ctx *h, const char *fn, int64_t nT, const int32_t *tris, double cos_lo, double cos_hi, double ratio_min,
-                      double area_min, double area_max, int64_t cap, const int32_t *quads, const int32_t *tri_quad)
+// the five parameters, checked before any device work (sitrk_mesh_build makes the same checks)
+int sitrk::quad_check_params(sitrk_ctx *h, const char *fn, double cos_lo, double cos_hi, double ratio_min, double area_min, double area_max)
 {
-    if (!(nT >= 0 && nT < ((int64_t)1 << 31) - 1)) return fail(h, SITRK_EINVAL, "%s: nT must be in 0..2^31-2", fn);
     if (!(cos_lo >= -1.0 && cos_lo <= 1.0 && cos_hi >= -1.0 && cos_hi <= 1.0 && cos_lo >= cos_hi))
         return fail(h, SITRK_EINVAL, "%s: need 1 >= cos_lo >= cos_hi >= -1 (got %g, %g)", fn, cos_lo, cos_hi);
     if (!(ratio_min >= 0.0 && ratio_min <= 1.0)) return fail(h, SITRK_EINVAL, "%s: ratio_min must be in [0,1] (got %g)", fn, ratio_min);
     if (!(area_min <= area_max)) return fail(h, SITRK_EINVAL, "%s: need area_min <= area_max (got %g, %g)", fn, area_min, area_max);
+    return SITRK_OK;
+}
+
+static int quad_check(sitrk_ctx *h, const char *fn, int64_t nT, const int32_t *tris, double cos_lo, double cos_hi, double ratio_min,
+                      double area_min, double area_max, int64_t cap, const int32_t *quads, const int32_t *tri_quad)
+{
+    if (!(nT >= 0 && nT < ((int64_t)1 << 31) - 1)) return fail(h, SITRK_EINVAL, "%s: nT must be in 0..2^31-2", fn);
+    RCCHK(quad_check_params(h, fn, cos_lo, cos_hi, ratio_min, area_min, area_max));
     if (cap < nT / 2) return fail(h, SITRK_EINVAL, "%s: quads has room for %lld rows, %lld triangles need %lld", fn, (long long)cap,
                                   (long long)nT, (long long)(nT / 2));
     if (nT > 0 && !(tris && tri_quad && (quads || nT < 2))) return fail(h, SITRK_EINVAL, "%s: null array", fn);
     return SITRK_OK;
 }
 
-namespace {
-struct QuadBuffers {
-    int32_t *tris, *nbr, *mate, *pick, *quads, *tri_quad;
-    int8_t *live;
-    double *score;
-    unsigned *block_count;
-    int64_t *block_off;
-    EdgeTable tab;
-    uint64_t slots;
-};
-
-uint64_t quad_slots(int64_t nT)
+static uint64_t quad_slots(int64_t nT)
 {
     uint64_t s = 64;
     while (s < (uint64_t)6 * (uint64_t)nT) s <<= 1;                   // >= twice the 3 nT half-edges
     return s;
 }
 
-void quad_carve(Carver &c, QuadBuffers &b, int64_t nT)
+void sitrk::quad_carve(Carver &c, QuadBuffers &b, int64_t nT)
 {
     b.slots = quad_slots(nT);
     b.tab.mask = b.slots - 1;
@@ -428,20 +362,25 @@ void quad_carve(Carver &c, QuadBuffers &b, int64_t nT)
     c.take(b.block_count, nblk(nT, kQmBlock)); c.take(b.block_off, nblk(nT, kQmBlock));
     c.take(b.quads, (size_t)4 * (nT / 2)); c.take(b.tri_quad, nT);
 }
-}  // namespace
 
-// Everything behind the points: d_pts (nP, NaN in y = no valid vertex) is on the device and the stream is behind what made it.
-static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, int64_t nT, const int32_t *tris, const QuadBuffers &b,
-                    const QuadParams &c, int32_t *quads, int32_t *tri_quad, int64_t *nQ, int *rounds)
+// The core: everything behind the points and the triangles, both on the device; the rows stay in b.quads / b.tri_quad.  The
+// buffers may be carved for more triangles than nT: the adjacency table takes the slots of nT, which never changes a result.
+int sitrk::quad_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, int64_t nT, const int32_t *d_tris, const QuadBuffers &b,
+                     const QuadParams &c, int64_t *nQ, int *rounds)
 {
     h->quad_timed = false;
-    HIPCHK(upload(h, b.tris, tris, (size_t)3 * nT));
+    for (hipEvent_t &e : h->quad_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    const uint64_t slots = quad_slots(nT);
+    if (slots > b.slots) return fail(h, SITRK_EINVAL, "%s: %lld triangles do not fit the buffers", fn, (long long)nT);
+    EdgeTable tab = b.tab;
+    tab.mask = slots - 1;
     HIPCHK(hipMemsetAsync(h->counter, 0, 2 * sizeof(unsigned long long), h->stream));
     HIPCHK(hipEventRecord(h->quad_ev[0], h->stream));
-    HIPCHK(hipMemsetAsync(b.tab.key, 0xff, b.slots * sizeof(unsigned long long), h->stream));
-    HIPCHK(hipMemsetAsync(b.tab.val, 0, b.slots * sizeof(unsigned long long), h->stream));
+    HIPCHK(hipMemsetAsync(tab.key, 0xff, slots * sizeof(unsigned long long), h->stream));
+    HIPCHK(hipMemsetAsync(tab.val, 0, slots * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(b.mate, 0xff, (size_t)nT * sizeof(int32_t), h->stream));                  // -1: unmatched
-    hipLaunchKernelGGL(quad_tri_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, nP, b.tris, d_pts, b.tab, b.live, h->counter);
+    hipLaunchKernelGGL(quad_tri_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, nP, d_tris, d_pts, tab, b.live, h->counter);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->quad_ev[1], h->stream));
     unsigned long long cnt[2] = {0, 0};
@@ -449,7 +388,7 @@ static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, i
     HIPCHK(hipStreamSynchronize(h->stream));
     if (cnt[0])                                                                                     // before any kernel follows an index
         return fail(h, SITRK_EINDEX, "%s: %llu triangle(s) have a vertex index outside [0, %lld)", fn, cnt[0], (long long)nP);
-    hipLaunchKernelGGL(quad_score_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, b.tris, d_pts, b.tab, b.live, c, b.score, b.nbr);
+    hipLaunchKernelGGL(quad_score_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, d_tris, d_pts, tab, b.live, c, b.score, b.nbr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->quad_ev[2], h->stream));
     const int64_t max_rounds = nT / 2 + 1;
@@ -458,7 +397,7 @@ static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, i
     for (;;) {
         if (nround == max_rounds)
             return fail(h, SITRK_EINVAL, "%s: the matching has not come to rest after %lld rounds (%llu pairs)", fn, (long long)nround, before);
-        hipLaunchKernelGGL(quad_pick_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, b.tris, b.score, b.nbr, b.mate, b.pick);
+        hipLaunchKernelGGL(quad_pick_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, d_tris, b.score, b.nbr, b.mate, b.pick);
         hipLaunchKernelGGL(quad_match_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, b.pick, b.mate, h->counter + 1);
         HIPCHK(hipGetLastError());
         HIPCHK(download(h, cnt + 1, h->counter + 1, 1));
@@ -471,7 +410,7 @@ static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, i
     const int64_t nb = nblk(nT, kQmBlock);
     hipLaunchKernelGGL(quad_count_kernel, dim3((unsigned)nb), dim3(kQmBlock), 0, h->stream, nT, b.mate, b.block_count);
     hipLaunchKernelGGL(quad_scan_kernel, dim3(1), dim3(kQmBlock), 0, h->stream, nb, b.block_count, b.block_off, h->counter);
-    hipLaunchKernelGGL(quad_emit_kernel, dim3((unsigned)nb), dim3(kQmBlock), 0, h->stream, nT, nT / 2, b.tris, d_pts, b.live, b.mate, b.block_off,
+    hipLaunchKernelGGL(quad_emit_kernel, dim3((unsigned)nb), dim3(kQmBlock), 0, h->stream, nT, nT / 2, d_tris, d_pts, b.live, b.mate, b.block_off,
                        b.quads, b.tri_quad);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->quad_ev[4], h->stream));
@@ -480,15 +419,24 @@ static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, i
     HIPCHK(hipStreamSynchronize(h->stream));
     if (cnt[0] != cnt[1] || cnt[0] > (unsigned long long)(nT / 2))
         return fail(h, SITRK_EINVAL, "%s: %llu pairs matched, %llu compacted", fn, cnt[1], cnt[0]);
-    if (cnt[0]) HIPCHK(download(h, quads, b.quads, (size_t)4 * cnt[0]));
-    HIPCHK(download(h, tri_quad, b.tri_quad, (size_t)nT));
-    HIPCHK(hipStreamSynchronize(h->stream));
     *nQ = (int64_t)cnt[0];
     *rounds = (int)nround;
     return SITRK_OK;
 }
 
-static QuadParams quad_params(double cos_lo, double cos_hi, double ratio_min, double area_min, double area_max)
+// The host entry points: the triangles go up in front of the core, the rows come down behind it.
+static int quad_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, int64_t nT, const int32_t *tris, const QuadBuffers &b,
+                    const QuadParams &c, int32_t *quads, int32_t *tri_quad, int64_t *nQ, int *rounds)
+{
+    HIPCHK(upload(h, b.tris, tris, (size_t)3 * nT));
+    RCCHK(quad_core(h, fn, nP, d_pts, nT, b.tris, b, c, nQ, rounds));
+    if (*nQ) HIPCHK(download(h, quads, b.quads, (size_t)4 * *nQ));
+    HIPCHK(download(h, tri_quad, b.tri_quad, (size_t)nT));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SITRK_OK;
+}
+
+QuadParams sitrk::quad_params(double cos_lo, double cos_hi, double ratio_min, double area_min, double area_max)
 {
     QuadParams c;
     c.c_lo2 = cos_lo * std::fabs(cos_lo);
@@ -515,8 +463,6 @@ SITRK_API int sitrk_tri2quad(sitrk_t *h, int64_t nP, const double *yx, const int
     if (nT == 0) return SITRK_OK;
     if (nP == 0) return fail(h, SITRK_EINDEX, "%s: %lld triangle(s) have a vertex index outside [0, 0)", fn, (long long)nT);
     HIPCHK(hipSetDevice(h->device));
-    for (hipEvent_t &e : h->quad_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
     pt *d_pts; int8_t *d_mask;
     QuadBuffers b;
     RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_pts, nP); c.take(d_mask, nP); quad_carve(c, b, nT); }));
@@ -546,8 +492,6 @@ SITRK_API int sitrk_tri2quad_buoys(sitrk_t *h, int64_t nT, const int32_t *tris, 
     if (rounds) *rounds = 0;
     if (nT == 0) return SITRK_OK;
     HIPCHK(hipSetDevice(h->device));
-    for (hipEvent_t &e : h->quad_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
     const int64_t nP = h->nP;
     pt *d_pts;
     QuadBuffers b;

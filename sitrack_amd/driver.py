@@ -88,6 +88,16 @@ def parse_args(argv=None):
                          'default off = every sub-step of a record uses that record\'s fields): `centre` = records are time means '
                          'centred on their step interval (what NEMO writes), `start` = snapshots at its start.  Partners are taken '
                          'among the records the run reads; siconc and the Survive test are never interpolated')
+    ap.add_argument('--deform', type=_deform_arg, default=[],
+                    help='SPEC[,SPEC...], at most 8; SPEC = RMAX_KM or RMAX_KM@RD_KM: deformation rates of quadrangle meshes that live on '
+                         'the GPU next to the buoys (extra; default none).  Each SPEC is one mesh: the Delaunay triangles of circumradius '
+                         '<= RMAX_KM of the buoys alive at the start of a window, paired into quadrangles; @RD_KM first coarsens the '
+                         'cloud to that spacing.  Several SPECs give the scales of a scaling analysis from one run.  Written to '
+                         './npz/<...>_deformation_<...>.npz; one rank only')
+    ap.add_argument('--deform-window', type=_deform_window_arg, default=0,
+                    help='with --deform: model records per window (extra; default 0 = the whole run is one window).  Every mesh is built '
+                         'anew at the start of each window and its rates are taken after the window\'s last record; a last, shorter '
+                         'window is kept')
     return ap.parse_args(argv)
 
 
@@ -98,22 +108,67 @@ def _sample_arg(text):
     return names
 
 
+DEFORM_MAX = _lib.MESH_MAX
+
+
+def _deform_arg(text):
+    """--deform: [(rmax_km, rd_km or 0.)] of RMAX_KM[@RD_KM][,...]: 1..8 entries, RMAX_KM finite in (0, 500], RD_KM finite > 0"""
+    err = argparse.ArgumentTypeError
+    specs = []
+    parts = text.split(',')
+    if len(parts) > DEFORM_MAX:
+        raise err("--deform: at most %d meshes, got %d" % (DEFORM_MAX, len(parts)))
+    for part in parts:
+        tok = part.strip().split('@')
+        if len(tok) not in (1, 2) or not all(t.strip() for t in tok):
+            raise err("--deform: expected RMAX_KM or RMAX_KM@RD_KM, got %r" % part)
+        try:
+            val = [float(t) for t in tok]
+        except ValueError:
+            raise err("--deform: expected numbers in RMAX_KM[@RD_KM], got %r" % part)
+        if not (np.isfinite(val[0]) and 0. < val[0] <= 500.):
+            raise err("--deform: RMAX_KM must be finite and in (0, 500], got %r" % part)
+        if len(val) == 2 and not (np.isfinite(val[1]) and val[1] > 0.):
+            raise err("--deform: RD_KM must be finite and > 0, got %r" % part)
+        specs.append((val[0], val[1] if len(val) == 2 else 0.))
+    return specs
+
+
+def _deform_window_arg(text):
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--deform-window: expected an integer, got %r" % text)
+    if n < 0:
+        raise argparse.ArgumentTypeError("--deform-window: must be >= 0 records, got %d" % n)
+    return n
+
+
+def deform_windows(Nt, kstrt, nwin):
+    """--deform-window: the windows [(jrec0, jrec1)] of model records, nwin records each (0: the whole run), the last one
+    shorter where nwin does not divide Nt"""
+    nwin = Nt if nwin <= 0 else nwin
+    return [(kstrt + j, kstrt + min(j + nwin, Nt) - 1) for j in range(0, Nt, nwin)]
+
+
 def output_due(jrec, kstrt, Nt, lFull, stride=1, ends=()):
     """does the step of model record jrec produce a record that is written (the series' k-th, or some buoys' last)"""
     k = jrec - kstrt + 1                               # the record of the series this step produces
     return bool((lFull and (k % stride == 0 or k == Nt)) or ((not lFull) and jrec in ends))
 
 
-def plan_batches(Nt, kstrt, K, lFull, stride=1, ends=(), firsts=None):
+def plan_batches(Nt, kstrt, K, lFull, stride=1, ends=(), firsts=None, cuts=None):
     """The record loop's batches [(jt, m)]: consecutive records go into one sitrk_run of up to K // 2 records, cut after every
     record whose output is due (output_due) and -- only when fields are sampled (`firsts` = the distinct first records of the
-    buoys' windows) -- in front of every record some buoy starts in, where its seed is sampled before the step."""
+    buoys' windows) -- in front of every record some buoy starts in, where its seed is sampled before the step.  `cuts`: model
+    records after each of which a batch ends as well (--deform: the last record of every window)."""
     firsts = set(firsts) if firsts is not None else set()
+    cuts = set(cuts) if cuts is not None else set()
     batches, jt = [], 0
     while jt < Nt:
         m = 1
         while m < K // 2 and jt + m < Nt and not output_due(jt + m - 1 + kstrt, kstrt, Nt, lFull, stride, ends) \
-                and (jt + m + kstrt) not in firsts:
+                and (jt + m + kstrt) not in firsts and (jt + m - 1 + kstrt) not in cuts:
             m += 1
         batches.append((jt, m))
         jt += m
@@ -367,6 +422,9 @@ def main(argv=None):
     lUse2DTime = not a.fxdt
     iUVstrategy = a.uv_strategy
     comm = Comm()
+    if a.deform and comm.multi:
+        comm.close()
+        raise ValueError('--deform: the cells of a mesh would span the ranks\' buoy ranges; run it on one rank (%d ranks here)' % comm.world)
     say = print if comm.root else (lambda *args, **kw: None)
     say('\n *** SITRACK ice particule tracker, GPU build; NetCDF backend = ' + ncio.backend()
         + ('; %d ranks (%s)' % (comm.world, comm.backend) if comm.multi else ''))
@@ -544,7 +602,12 @@ def main(argv=None):
             raise ValueError('--tinterp is not available together with --full-records under an RCCL launch (the record broadcaster '
                              'hands a slot back before its partner has been stepped with): drop --full-records')
         bcast = RecordBroadcaster(ctx)                 # rank 0 reads; one RCCL broadcast per record, overlapped with the stepping
-    batches = plan_batches(Nt, kstrt, K_plan, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None)
+    # --deform: the windows, the batches' cuts behind them, and what is kept of every (mesh, window) for the file
+    dfm_win = deform_windows(Nt, kstrt, a.deform_window) if a.deform else []
+    dfm_first, dfm_last = {w[0]: k for k, w in enumerate(dfm_win)}, {w[1]: k for k, w in enumerate(dfm_win)}
+    dfm_out = {}
+    batches = plan_batches(Nt, kstrt, K_plan, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None,
+                           cuts=set(dfm_last) if a.deform else None)
     tplan = plan_tinterp(batches, Nt, K) if tphase is not None else None
     band = {"box": None, "age": None, "bytes": 0, "boxes": {}}
     esz = np.dtype(fdt).itemsize
@@ -610,6 +673,44 @@ def main(argv=None):
                 rows[:, smp_names.index('siconc')] = ctx.sample_slot((jrec - kstrt) % K, jrec, mode, 'siconc')
         clk.add("sample_s", t_s)
         return to_caller_order(comm.gather_rows(rows, nP))
+
+    def deform_build(kw):
+        """--deform, in front of the first record of window kw: every mesh from the cloud as it is now"""
+        t_d = clk.now()
+        jrec0 = dfm_win[kw][0]
+        keep_of = {}
+        for km, (rmax, rd) in enumerate(a.deform):
+            msk = None
+            if rd > 0.:
+                if rd not in keep_of:                    # the alive cloud, coarsened to spacing rd on the positions as they are now
+                    st = ctx.fetch()
+                    al = np.asarray(st["alive"]) != 0
+                    keep = np.zeros(nP, dtype=np.int8)
+                    if al.any():
+                        keep[np.where(al)[0][ctx.subsample_cloud(st["yx"][al], rd)[0]]] = 1
+                    keep_of[rd] = keep
+                msk = keep_of[rd]
+            r = trk.mesh(rmax, jrec0, slot=km, mask=msk)
+            dfm_out["m%d_w%d_cells" % (km, kw)] = np.asarray(IDs)[trk.mesh_cells(km)].astype(np.int64).reshape(-1, 4)
+            say(' *** --deform window %d mesh %d (rmax %g km%s): %d triangles -> %d quadrangles'
+                % (kw, km, rmax, ', rd %g km' % rd if rd > 0. else '', r["nT"], r["nQ"]))
+        clk.add("deform_s", t_d)
+
+    def deform_take(kw):
+        """--deform, behind the last record of window kw: the rates of every mesh since the window's start"""
+        t_d = clk.now()
+        for km in range(len(a.deform)):
+            r = trk.mesh_deform(dfm_win[kw][1], slot=km)
+            pre = "m%d_w%d_" % (km, kw)
+            for n in ("div", "shr", "vor", "area0", "area1"):
+                dfm_out[pre + n] = r[n]
+            dfm_out[pre + "status"] = r["status"]
+            stt = r["stats"]
+            dfm_out[pre + "stats"] = np.array([stt[n] for n in _lib.MESH_STATS], dtype=np.float64)
+            say(' *** --deform window %d mesh %d: nQ = %d, status 0/1/2 = %d/%d/%d, area-weighted mean total deformation = %s'
+                % (kw, km, len(r["status"]), stt["n0"], stt["n1"], stt["n2"],
+                   '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
+        clk.add("deform_s", t_d)
 
     tk = clk.add("setup_s", tk)
     t_loop = clk.now()
@@ -691,6 +792,9 @@ def main(argv=None):
                         series.abort()
                         raise
             t_q = clk.now()
+        if jrec0 in dfm_first:
+            deform_build(dfm_first[jrec0])
+            t_q = clk.now()
         if tplan is None:
             trk.run(jrec0, jt0 % K, m)
         else:
@@ -709,6 +813,8 @@ def main(argv=None):
                 upload(*batches[ib + 1])           # travels while the launch above runs
             else:
                 upload_recs(batches[ib + 1][0], tplan[ib]["behind"])
+        if jrecN in dfm_last:
+            deform_take(dfm_last[jrecN])
         jt, jrec, itime = jt0 + m - 1, jrecN, vTime[jt0 + m - 1]
         need = need_output(jrec)
         t_f = clk.now()
@@ -788,6 +894,15 @@ def main(argv=None):
     ncio.ncSaveCloudBuoys(cf_nc_out, zvt, IDs, z2XY[:, :, 0], z2XY[:, :, 1], z2GC[:, :, 0], z2GC[:, :, 1], mask=zMSK, xtime=zTim,
                           corigin=corgn, extra={n: (zS[n], smp_attrs[n]) for n in smp_names} if smp_names else None)
     outs.append(cf_nc_out)
+
+    if a.deform:
+        cf_dfm = ('./npz/' + corgn + '_deformation_' + SeedBatch + cdtbin + '_' + date_tag(vTime[0]) + '_' + date_tag(vTime[Nt]) + csfkm
+                  + '.npz')
+        _savez_deflate(cf_dfm, meshes=np.array(a.deform, dtype=np.float64).reshape(-1, 2),
+                       windows=np.array(dfm_win, dtype=np.int64).reshape(-1, 2),
+                       time0=np.array([vTime[w[0] - kstrt] for w in dfm_win], dtype=np.int64),
+                       time1=np.array([vTime[w[1] - kstrt + 1] for w in dfm_win], dtype=np.int64), **dfm_out)
+        outs.append(cf_dfm)
 
     if a.plot > 0:
         try:

@@ -274,6 +274,45 @@ class IceTracker:
         tris, _, _ = self.ctx.delaunay_buoys(_rmax('ERROR [IceTracker.tris()]: ', rmax_km))
         return tris
 
+    def mesh(self, rmax_km, jrec0, slot=0, mask=None, angles=(60., 120.), ratio_min=0.5, area=(0., float("inf"))):
+        """Builds the device-resident quadrangle mesh `slot` (0..7) from the buoys alive now, at their current positions: tris()
+        followed by quads() with nothing leaving the device, and the t0 positions of deform taken on the spot (an extra the
+        reference does not have; sitrk_mesh_build).  `jrec0` = the model record that will be stepped next; mask (nP): 0 = the
+        buoy is no point of this mesh; the other arguments as sit.Tri2Quad.  Returns {"nT", "nQ", "rounds"}."""
+        from .delaunay import _rmax
+        from .quadmesh import _params
+        cerr = 'ERROR [IceTracker.mesh()]: '
+        kw = _params(cerr, np.empty((0, 3), dtype=np.int32), angles, ratio_min, area)
+        if mask is not None and np.shape(mask) != (self.ctx.nP,):
+            raise ValueError(cerr + '`mask` must be (nP,), got %s' % (np.shape(mask),))
+        nT, nQ, rounds = self.ctx.mesh_build(slot, jrec0, _rmax(cerr, rmax_km), mask=mask, **kw)
+        return {"nT": nT, "nQ": nQ, "rounds": rounds}
+
+    def mesh_cells(self, slot=0):
+        """The quadrangles (nQ,4) int32 of buoy indices of mesh `slot`, rows as quads() gives them"""
+        return self.ctx.mesh_cells(slot)
+
+    def mesh_mark(self, jrec0, slot=0):
+        """Takes the t0 positions of mesh `slot` again, for the same cells, at the current positions; `jrec0` = the model record
+        that will be stepped next.  A cell with a vertex that is not alive now is invalid from then on."""
+        self.ctx.mesh_mark(slot, jrec0)
+
+    def mesh_deform(self, jrec1, slot=0, full=True):
+        """Right after the step of `jrec1`: deformation rates of the cells of mesh `slot` between its t0 and now.  A dict with
+        div, shr, vor, area0, area1 (nQ,) fp64 (FillValue where status is 0), status (nQ,) int8 -- 0 invalid, 1 valid and still an
+        acceptable quadrangle now, 2 valid but distorted beyond the mesh's own acceptance tests -- and stats, a dict under the
+        names _lib.MESH_STATS: the three counts and the area-weighted sums over the status-1 cells.  full=False: the stats only,
+        80 bytes from the device."""
+        r = self.ctx.mesh_deform(slot, jrec1, want=("out", "status", "stats") if full else ("stats",))
+        stats = dict(zip(_lib.MESH_STATS, (float(x) for x in r["stats"])))
+        if not full:
+            return stats
+        out = r["out"]
+        return {"div": out[0], "shr": out[1], "vor": out[2], "area0": out[3], "area1": out[4], "status": r["status"], "stats": stats}
+
+    def mesh_free(self, slot=0):
+        self.ctx.mesh_free(slot)
+
     def dist2coast(self, rmax_km=None, return_seg=False):
         """Distance [km, polar-stereographic plane] of every buoy, alive or not, to the coastline of the tracker's own mesh, from
         the device-resident positions, in the caller's order (an extra the reference does not have; sitrk_coast_dist_buoys).
