@@ -547,6 +547,35 @@ __device__ __forceinline__ pt geo_pt(const char *__restrict__ gb, unsigned off, 
     return *(const pt *)(gb + (size_t)off + (ptrdiff_t)imm);
 }
 
+// CrossedEdge (:189-200) as the byte offset of the crossing tables' row kc-1 (64-byte rows): the first of bottom, right,
+// upper hit, else left.  Same predicates on the same operands in the same order as resolve_crossing(); the choice is a
+// priority one, so the terms only a later edge needs -- its two side tests and ccw(P1,P2,.) of its far vertex, 13 fp64-class
+// instructions per edge -- sit behind a test of the lanes still undecided: a wave whose crossers all left by the bottom edge
+// skips both groups, one whose crossers left by the bottom or the right edge skips the second (a wave's crossers share the
+// local flow direction).  The lanes that do go on compute what every lane computed before.  pin_edge keeps the compiler from
+// hoisting a group's arithmetic back above its test (the callers sit in both arms of the patch / global-table choice).
+__device__ __forceinline__ void pin_edge(pt &v) { asm volatile("" : "+v"(v.y), "+v"(v.x)); }
+
+__device__ __forceinline__ unsigned crossed_edge_row(pt P1, pt P2, pt bl, pt br, pt ur, pt ul)
+{
+    const bool sbl = ccw(P1, P2, bl), sbr = ccw(P1, P2, br);
+    const bool h1 = (ccw(P1, bl, br) != ccw(P2, bl, br)) && (sbl != sbr);
+    unsigned ro = 0u;
+    if (!h1) {
+        pin_edge(ur);
+        const bool sur = ccw(P1, P2, ur);
+        const bool h2 = (ccw(P1, br, ur) != ccw(P2, br, ur)) && (sbr != sur);
+        ro = 64u;
+        if (!h2) {
+            pin_edge(ul);
+            const bool sul = ccw(P1, P2, ul);
+            const bool h3 = (ccw(P1, ur, ul) != ccw(P2, ur, ul)) && (sur != sul);
+            ro = h3 ? 128u : 192u;
+        }
+    }
+    return ro;
+}
+
 // P1 -> P2 leaves the cell whose quad is (bl, br, ur, ul); k48 = byte offset of the cell's geometry record, k9 = the
 // Survive bits of the cell's 8 neighbours for this record (pack_kill9_kernel).  Returns the crossed edge kc (1..4) and
 // fills the increments of the destination cell; `killed` = the destination's Survive byte.
@@ -556,11 +585,7 @@ __device__ __forceinline__ int resolve_crossing_tab(pt P1, pt P2, pt bl, pt br, 
                                                     const int *__restrict__ tab /* LDS */, int &dcell, int &dk, bool &killed,
                                                     int *codes = nullptr)
 {
-    const bool sbl = ccw(P1, P2, bl), sbr = ccw(P1, P2, br), sur = ccw(P1, P2, ur), sul = ccw(P1, P2, ul);
-    const bool h1 = (ccw(P1, bl, br) != ccw(P2, bl, br)) && (sbl != sbr);
-    const bool h2 = (ccw(P1, br, ur) != ccw(P2, br, ur)) && (sbr != sur);
-    const bool h3 = (ccw(P1, ur, ul) != ccw(P2, ur, ul)) && (sur != sul);
-    const unsigned ro = h1 ? 0u : (h2 ? 64u : (h3 ? 128u : 192u));            // byte offset of row kc-1 (selected as such)
+    const unsigned ro = crossed_edge_row(P1, P2, bl, br, ur, ul);             // byte offset of row kc-1 (selected as such)
     const int kc = (int)(ro >> 6) + 1;                                       // (only the probes look at it)
     const int *row = (const int *)((const char *)tab + ro);
     const int4 r0 = *(const int4 *)(row), r1 = *(const int4 *)(row + 4), r2 = *(const int4 *)(row + 8);
@@ -572,14 +597,18 @@ __device__ __forceinline__ int resolve_crossing_tab(pt P1, pt P2, pt bl, pt br, 
     bool hitA = ccw(P1, va, eA) != ccw(P2, va, eA);
     bool hitB = ccw(P1, vb, eB) != ccw(P2, vb, eB);
     // ... and only for lanes that pass it the second half of intersect2Seg (a diagonal move is rare: most waves skip this)
+    // UpdtInd4NewCell (:257-300); first match wins (if / elif).  The straight destination is the default; the selects of a
+    // diagonal one sit with the test that can make one, so a wave without such a lane does not issue them.
+    dcell = r1.x;
+    dk = r1.w;
+    int msk = r2.z;
     if (hitA || hitB) {
         hitA = hitA && (ccw(P1, P2, va) != ccw(P1, P2, eA));
         hitB = hitB && (ccw(P1, P2, vb) != ccw(P1, P2, eB));
+        dcell = hitA ? r1.y : (hitB ? r1.z : dcell);
+        dk = hitA ? r2.x : (hitB ? r2.y : dk);
+        msk = hitA ? r2.w : (hitB ? bB : msk);
     }
-    // UpdtInd4NewCell (:257-300); first match wins (if / elif)
-    dcell = hitA ? r1.y : (hitB ? r1.z : r1.x);
-    dk = hitA ? r2.x : (hitB ? r2.y : r1.w);
-    const int msk = hitA ? r2.w : (hitB ? bB : r2.z);
     killed = (k9 & (unsigned)msk) != 0;                                      // Survive (:483-484)
     if (codes) {
         const int cA = (kc == 1) ? 5 : (kc == 2) ? 6 : 8, cB = (kc == 1) ? 6 : (kc == 4) ? 5 : 7;
@@ -757,7 +786,7 @@ struct RunArgs {
 // the two record-independent orientation terms of the velocity pick (ccw(F,V01,V11), ccw(F,U10,U11)) are
 // (re)loaded only when the buoy changes cell (3-16 % of the records); per record only the four velocity
 // candidates are loaded.  Same operations on the same operands in the same order as advance_record.
-// 72 VGPRs, no scratch -> 7 waves/SIMD (78 -> 6 with per-buoy record windows; round 1: 91 VGPRs, 5 waves; requesting the
+// 70 VGPRs, no scratch -> 7 waves/SIMD (72 with per-buoy record windows; before the crossing-path trim 72 and 78; round 1: 91 VGPRs, 5 waves; requesting the
 // next record's velocities one record ahead was measured 7 % slower then: more instructions in the loop).
 // ---------------------------------------------------------------------------
 struct CellCtx {
@@ -844,11 +873,7 @@ __device__ __forceinline__ void resolve_crossing_lds(pt P1, pt P2, pt bl, pt br,
                                                      const int *__restrict__ tab, const int *__restrict__ tabL, int &dcell, int &dk,
                                                      int &dlo, bool &killed)
 {
-    const bool sbl = ccw(P1, P2, bl), sbr = ccw(P1, P2, br), sur = ccw(P1, P2, ur), sul = ccw(P1, P2, ul);
-    const bool h1 = (ccw(P1, bl, br) != ccw(P2, bl, br)) && (sbl != sbr);
-    const bool h2 = (ccw(P1, br, ur) != ccw(P2, br, ur)) && (sbr != sur);
-    const bool h3 = (ccw(P1, ur, ul) != ccw(P2, ur, ul)) && (sur != sul);
-    const unsigned ro = h1 ? 0u : (h2 ? 64u : (h3 ? 128u : 192u));            // both tables have 64-byte rows
+    const unsigned ro = crossed_edge_row(P1, P2, bl, br, ur, ul);             // both tables have 64-byte rows
     const int *row = (const int *)((const char *)tab + ro), *rowL = (const int *)((const char *)tabL + ro);
     const int4 r1 = *(const int4 *)(row + 4), r2 = *(const int4 *)(row + 8);
     const int bB = row[12];
@@ -857,14 +882,18 @@ __device__ __forceinline__ void resolve_crossing_lds(pt P1, pt P2, pt bl, pt br,
     const pt eA = lds_pt_at(lo + (unsigned)l0.z), eB = lds_pt_at(lo + (unsigned)l0.w);
     bool hitA = ccw(P1, va, eA) != ccw(P2, va, eA);
     bool hitB = ccw(P1, vb, eB) != ccw(P2, vb, eB);
+    dcell = r1.x;                                                            // (the selects: see resolve_crossing_tab)
+    dk = r1.w;
+    dlo = l1.x;
+    int msk = r2.z;
     if (hitA || hitB) {
         hitA = hitA && (ccw(P1, P2, va) != ccw(P1, P2, eA));
         hitB = hitB && (ccw(P1, P2, vb) != ccw(P1, P2, eB));
+        dcell = hitA ? r1.y : (hitB ? r1.z : dcell);
+        dk = hitA ? r2.x : (hitB ? r2.y : dk);
+        dlo = hitA ? l1.y : (hitB ? l1.z : dlo);
+        msk = hitA ? r2.w : (hitB ? bB : msk);
     }
-    dcell = hitA ? r1.y : (hitB ? r1.z : r1.x);
-    dk = hitA ? r2.x : (hitB ? r2.y : r1.w);
-    dlo = hitA ? l1.y : (hitB ? l1.z : l1.x);
-    const int msk = hitA ? r2.w : (hitB ? bB : r2.z);
     killed = (k9 & (unsigned)msk) != 0;
 }
 
@@ -878,10 +907,11 @@ static constexpr int kRunLdsFixed = 256 + 256 + 64;      // crossing table, its 
 // path high / the rest low is no better than no hint.
 static constexpr int kPrioLoads = 3, kPrioCross = 2, kPrioBase = 0;
 static constexpr int kRunBlock = 256;   // workgroup size of the fused kernel
-static constexpr int kRunWaves = 7;     // 72 VGPRs, no scratch (the cell is stored behind a lane flag, crel and the row-below offset are
+static constexpr int kRunWaves = 7;     // 70 VGPRs, no scratch (the cell is stored behind a lane flag, crel and the row-below offset are
                                         // derived where they are used): +2.6 % over 6 waves; 8 waves (64 VGPRs) spill 32 registers
 static constexpr int kRunWavesWindow = 6;   // the form with per-buoy record windows carries two more registers: 9 spilled at 7 waves
                                             // (13-25 with the window packed into one register, as a single test, or as a predicate on the body)
+                                            // (figures from before crossed_edge_row; the bound is kept, the form now allocates 72 VGPRs under it)
 
 // TWINS: the sub-step and time-blend kernels run this kernel's prologue, lane set-up, re-cell step, kill write and epilogue
 // from fused_prologue, lane_setup, recell, record_kill and store_state below (this kernel cannot call them: its ISA is
