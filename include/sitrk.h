@@ -536,6 +536,57 @@ int sitrk_mesh_free(sitrk_t *h, int mesh);
  * may be NULL, SITRK_EINVAL for a phase that has not run */
 int sitrk_mesh_kernel_ms(sitrk_t *h, float *build_ms, float *points_ms, float *cells_ms, float *stats_ms);
 
+/* ---- buoy cells rasterised onto a regular grid -----------------------------------
+ * An EXTRA the reference does not have: which cell each point of a regular grid lies in, and for a device-resident mesh the
+ * deformation of that cell -- the map of a mesh without its per-cell results moving to the host.  No parity
+ * claim is made against any other code; the contract below is this library's own.  Everything in fp64, one rounded operation
+ * per symbol in the order written, no fused multiply-add; only + - * and comparisons, so nothing is unpinned.
+ * THE GRID is (y0_km, x0_km, d_km, ny, nx) in the polar-stereographic plane the tracker works in: square pixels of side d_km,
+ * pixel (j,i) with j along y and i along x, its centre at
+ *     cy_j = y0 + ((double)j + 0.5) * d ; cx_i = x0 + ((double)i + 0.5) * d        (one rounded product and one rounded sum each)
+ * SITRK_EINVAL before any device work unless y0, x0, d are finite, d > 0, ny, nx >= 1 and ny*nx <= 2^28.
+ * A CELL is nv = 3 or 4 vertices (y_k, x_k), k' = (k+1) mod nv, in either orientation.  A2 = the shoelace sum relative to
+ * vertex 0, the expression of sitrk_deform_cells.  The cell is DRAWABLE iff all 2 nv coordinates are finite, A2 is finite and
+ * A2 != 0; s = +1 if A2 > 0, else -1.
+ * THE INSIDE TEST: for each edge
+ *     o_k = (x_k' - x_k)*(cy - y_k) - (y_k' - y_k)*(cx - x_k)
+ * and a centre lies IN the cell iff s*o_k >= 0 for every k: the boundary counts as inside.  For a quadrangle that is not convex
+ * this is the part of it seen from all four edges; the cells of a mesh are strictly convex by the acceptance tests of
+ * sitrk_tri2quad, at t0 always and at t1 where their status is 1.
+ * THE OWNER: owner (ny,nx) int32 = the LOWEST index among the drawn cells the pixel's centre lies in, -1 for none.  A centre on a
+ * shared edge or vertex, or in several overlapping cells (at t1, after convergence), goes to the lowest index whatever order
+ * the cells are processed in: two calls on the same state return the same bits.  *nowned (may be NULL) = the number of pixels
+ * with owner >= 0.  A cell's bounding box only bounds the pixels that are tested (its index range widened by one pixel each way,
+ * the centre arithmetic not being exactly invertible, and checked against the centres themselves); the result is that of testing
+ * every pixel against every cell.
+ *
+ * sitrk_raster_cells: host arrays yx (nP,2) [y,x] km, cells (nC,nv) int32, draw (nC) int8 (NULL: all): a cell is drawn iff its
+ * byte is not 0 and it is drawable.  A vertex index outside [0, nP) is SITRK_EINDEX with the number of offending cells in
+ * sitrk_last_error (owner unspecified); such an index is never dereferenced and the handle stays usable.  nC == 0 is valid:
+ * every pixel -1.  Synchronous on the handle's stream.  Uses the context's transient scratch only (never read by the stepping):
+ * the grid, buoys, records and meshes of a tracker on the same handle are left as they were.  SITRK_EINVAL for nv not in {3,4}
+ * and missing pointers.
+ * sitrk_mesh_raster is valid wherever sitrk_mesh_deform(mesh, jrec1, ...) is, and runs the same pass over the buoys and the same
+ * cell kernel; the statuses and rates stay on the device.  at_t1 == 0: the geometry is the mesh's stored t0 positions and the
+ * cells of status 1 or 2 are drawn (the most deformed cells are the ones a map is made for).  at_t1 == 1: the geometry is the
+ * current positions and only the cells of status 1 are drawn (a cell of status 2 may have turned inside out).  fields (may be
+ * NULL) is (5,ny,nx) fp64: the bits of div, shr, vor, area0, area1 of the pixel's owner as sitrk_mesh_deform returns them,
+ * SITRK_FILL where owner == -1.  owner may be NULL when fields is not; both NULL is SITRK_EINVAL, as is at_t1 outside {0,1}.
+ * The other errors are those of sitrk_mesh_deform, plus the grid's.  An empty mesh gives -1 and SITRK_FILL everywhere.  Only the
+ * raster comes down: 4 (+ 40) bytes per pixel.
+ * sitrk_raster_kernel_ms: GPU time [ms] of the last of the two calls on this handle, from HIP events -- the fill of the raster
+ * with the cell kernel, the gather kernel; either pointer may be NULL, SITRK_EINVAL before any such call.
+ * sitrk_raster_stats, measurement only: with the knob "raster_count" set to 1 (default 0; it never changes a result) the cell
+ * kernel also counts *claims = the (centre, drawn cell) pairs that passed the inside test, each of which is one integer atomic;
+ * claims over *nowned is 1 where no two drawn cells share a centre.  Of the last call that ran with the knob set, SITRK_EINVAL
+ * if there is none. */
+int sitrk_raster_cells(sitrk_t *h, int64_t nP, const double *yx, int64_t nC, int nv, const int32_t *cells, const int8_t *draw,
+                       double y0_km, double x0_km, double d_km, int ny, int nx, int32_t *owner, int64_t *nowned);
+int sitrk_mesh_raster(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny, int nx,
+                      int32_t *owner, double *fields, int64_t *nowned);
+int sitrk_raster_kernel_ms(sitrk_t *h, float *cells_ms, float *gather_ms);
+int sitrk_raster_stats(sitrk_t *h, int64_t *claims);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

@@ -16,5 +16,6 @@ from .overlap import CancelTooClose                                          # n
 from .deformation import DeformCells, lattice_cells                          # noqa: F401
 from .quadmesh import Tri2Quad                                                # noqa: F401
 from .delaunay import DelaunayTris                                           # noqa: F401
+from .raster import RasterCells, raster_grid                                  # noqa: F401
 from .coast import DistToCoast, MaskCoastal                                  # noqa: F401
 from . import synthetic                                                      # noqa: F401

@@ -92,6 +92,10 @@ _SIGNATURES = {
     "sitrk_mesh_deform": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "sitrk_mesh_free": (_int, [_vp, _int]),
     "sitrk_mesh_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 4),
+    "sitrk_raster_cells": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp, _dbl, _dbl, _dbl, _int, _int, _vp, C.POINTER(_i64)]),
+    "sitrk_mesh_raster": (_int, [_vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_raster_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 2),
+    "sitrk_raster_stats": (_int, [_vp, C.POINTER(_i64)]),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -762,6 +766,71 @@ class Context:
         ask = [build, deform, deform, deform]
         self._chk(self._L.sitrk_mesh_kernel_ms(self._h, *[C.byref(x) if a else None for x, a in zip(v, ask)]))
         return tuple(x.value if a else None for x, a in zip(v, ask))
+
+    # -- cells rasterised onto a regular grid (sitrk_raster_*)
+    @staticmethod
+    def _grid_arg(grid, name):
+        """(y0, x0, d, ny, nx) as the C types; the library checks the values"""
+        try:
+            y0, x0, d, ny, nx = grid
+            g = (float(y0), float(x0), float(d), int(ny), int(nx))
+        except (TypeError, ValueError):
+            raise ValueError("%s: grid must be (y0_km, x0_km, d_km, ny, nx), got %r" % (name, grid)) from None
+        if g[3] != ny or g[4] != nx or not (-2 ** 31 <= g[3] < 2 ** 31 and -2 ** 31 <= g[4] < 2 ** 31):
+            raise ValueError("%s: ny and nx must be integers that fit int32, got %r, %r" % (name, ny, nx))
+        return g
+
+    def raster_cells(self, yx, cells, grid, draw=None):
+        """sitrk_raster_cells: (owner (ny,nx) int32, nowned) of the cells (nC, 3|4) of indices into the points yx (nP,2) km on the
+        grid (y0_km, x0_km, d_km, ny, nx): per pixel the lowest-indexed drawn cell its centre lies in, -1 for none; draw (nC):
+        0 = the cell is not drawn."""
+        g = self._grid_arg(grid, "raster_cells")
+        yx = as_c(yx, np.float64)
+        nP = yx.shape[0]
+        yx = as_c(yx, np.float64, (nP, 2), "yx")
+        c = self._deform_cells_arg(cells, "raster_cells")
+        nC, nv = c.shape
+        dr = None if draw is None else as_c(np.asarray(draw) != 0, np.int8, (nC,), "draw")
+        owner = np.empty((max(g[3], 0), max(g[4], 0)), dtype=np.int32)
+        nowned = _i64(0)
+        self._chk(self._L.sitrk_raster_cells(self._h, nP, _ptr(yx), nC, nv, _ptr(c), _ptr(dr), *g, _ptr(owner), C.byref(nowned)))
+        return owner, nowned.value
+
+    def mesh_raster(self, mesh, jrec1, grid, at_t1=False, want=("owner", "fields")):
+        """sitrk_mesh_raster, right after the step of jrec1: a dict with those of owner (ny,nx) int32 and fields (5,ny,nx) fp64 =
+        div, shr, vor, area0, area1 of the owner (FillValue where there is none) that `want` names, and nowned; the cells of the
+        mesh in slot `mesh` drawn at their t0 positions (status 1 or 2) or, at_t1, at the current ones (status 1).  Only the
+        raster comes back from the device."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in ("owner", "fields")]
+        if bad or not want:
+            raise ValueError("mesh_raster: want must name some of 'owner', 'fields', got %r" % (want,))
+        g = self._grid_arg(grid, "mesh_raster")
+        ny, nx = max(g[3], 0), max(g[4], 0)
+        res = {}
+        if "owner" in want:
+            res["owner"] = np.empty((ny, nx), dtype=np.int32)
+        if "fields" in want:
+            res["fields"] = np.empty((5, ny, nx), dtype=np.float64)
+        nowned = _i64(0)
+        self._chk(self._L.sitrk_mesh_raster(self._h, int(mesh), int(jrec1), 1 if at_t1 else 0, *g, _ptr(res.get("owner")),
+                                            _ptr(res.get("fields")), C.byref(nowned)))
+        res["nowned"] = nowned.value
+        return res
+
+    def raster_kernel_ms(self):
+        """(cells_ms, gather_ms): GPU time of the fill with the cell kernel and of the gather kernel of the last raster call
+        (sitrk_raster_kernel_ms)"""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self._L.sitrk_raster_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def raster_stats(self):
+        """claims -- centres found inside a drawn cell, one atomic each -- of the last raster call that ran under
+        set_tuning(raster_count=1) (sitrk_raster_stats)"""
+        a = _i64(0)
+        self._chk(self._L.sitrk_raster_stats(self._h, C.byref(a)))
+        return a.value
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

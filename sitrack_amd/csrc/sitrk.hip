@@ -130,6 +130,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     quadmesh_release(h);
     delaunay_release(h);
     mesh_release(h, true);
+    raster_release(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
@@ -306,6 +307,11 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
     else if (!strcmp(knob, "delaunay_bin")) {        // cells per reach of the next sitrk_delaunay
         if (value < 1 || value > 4) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: delaunay_bin must be 1..4");
         h->delaunay_bin = value;
+        return SITRK_OK;
+    }
+    else if (!strcmp(knob, "raster_count")) {        // the next raster calls count their claims and atomics (sitrk_raster_stats)
+        if (value < 0 || value > 1) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: raster_count must be 0 or 1");
+        h->raster_count = value;
         return SITRK_OK;
     }
     else if (!strcmp(knob, "locate_bruteforce")) bit = TUNE_LOCATE_BRUTEFORCE;

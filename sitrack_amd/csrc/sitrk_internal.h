@@ -254,6 +254,14 @@ struct sitrk_ctx {
     hipEvent_t mesh_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool mesh_build_timed = false, mesh_deform_timed = false;
 
+    // rasterised cells (sitrk_raster.hip): events around the fill with the cell kernel and around the gather kernel of the last
+    // call; with the knob raster_count its centres found inside a drawn cell (= the atomics issued)
+    hipEvent_t raster_ev[3] = {nullptr, nullptr, nullptr};
+    bool raster_timed = false;
+    int raster_count = 0;               // knob: count them (a measurement build of the cell kernel; never changes results)
+    bool raster_counted = false;
+    unsigned long long raster_claims = 0;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -280,6 +288,25 @@ int deform_points_now(sitrk_ctx *h, pt *out);
 int deform_points_span(sitrk_ctx *h, int jrec0, int jrec1, pt *out);
 // sitrk_mesh.hip: frees every mesh (free_buoys of sitrk.hip); destroy = the timing events too
 void mesh_release(sitrk_ctx *h, bool destroy);
+// ... and the body of sitrk_mesh_deform behind its argument checks (mesh_deform_check), everything left in the transient scratch:
+// the pass over the buoys, the cell kernel and, when asked for, the final sum are queued on the compute stream and the pointers
+// of MeshDeformDev say where their results lie.  `extra` bytes of the same scratch layout come with them for the caller's own
+// buffers (sitrk_raster.hip).  An empty mesh queues nothing and returns null pointers next to `extra`.
+struct MeshDeformDev {
+    int64_t nQ = 0;
+    const int32_t *quads = nullptr;     // (nQ,4) the mesh's own
+    const pt *t0 = nullptr;             // (nQ,4) the mesh's own
+    const pt *p1 = nullptr;             // (nP) current positions in the caller's order, NaN in y = no valid vertex
+    const double *out = nullptr;        // (5,nQ)
+    const int8_t *status = nullptr;     // (nQ)
+    const double *stats = nullptr;      // (SITRK_MESH_NSTATS)
+    char *extra = nullptr;
+};
+int mesh_deform_check(sitrk_ctx *h, const char *fn, int mesh, int jrec1);
+int mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want_status, bool want_stats, size_t extra,
+                     MeshDeformDev *r);
+// sitrk_raster.hip: destroys the timing events (sitrk_destroy)
+void raster_release(sitrk_ctx *h);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
 void quadmesh_release(sitrk_ctx *h);
 // sitrk_delaunay.hip: destroys the timing events (sitrk_destroy)

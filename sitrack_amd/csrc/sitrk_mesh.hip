@@ -281,44 +281,66 @@ SITRK_API int sitrk_mesh_mark(sitrk_t *h, int mesh, int jrec0)
     return SITRK_OK;
 }
 
-SITRK_API int sitrk_mesh_deform(sitrk_t *h, int mesh, int jrec1, double *out, int8_t *status, double *stats)
+int sitrk::mesh_deform_check(sitrk_ctx *h, const char *fn, int mesh, int jrec1)
 {
-    const char *fn = "sitrk_mesh_deform";
-    NEED(h, "null handle");
     RCCHK(mesh_check(h, fn, mesh, true));
     const Mesh &m = h->mesh[mesh];
     if (jrec1 < m.jrec0) return fail(h, SITRK_EINVAL, "%s: jrec1 = %d lies before the mesh's t0 at record %d", fn, jrec1, m.jrec0);
-    if (!out && !status && !stats) return fail(h, SITRK_EINVAL, "%s: out, status and stats are all null", fn);
-    if (stats)
-        for (int k = 0; k < SITRK_MESH_NSTATS; k++) stats[k] = 0.0;
+    return SITRK_OK;
+}
+
+int sitrk::mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want_status, bool want_stats, size_t extra,
+                            MeshDeformDev *r)
+{
+    const Mesh &m = h->mesh[mesh];
     const int64_t nQ = m.nQ, nP = h->nP;
-    if (nQ == 0) return SITRK_OK;
     const double T = (double)((int64_t)jrec1 - m.jrec0 + 1) * h->rdt;                  // one rounded product
     HIPCHK(hipSetDevice(h->device));
     RCCHK(mesh_events(h));
-    h->mesh_deform_timed = false;
     const int64_t nb = nblk(nQ);
-    pt *d_p1; double *d_out, *d_part, *d_stats; int8_t *d_status;
+    pt *d_p1; double *d_out, *d_part, *d_stats; int8_t *d_status; char *d_extra;
     RCCHK(carve_scratch(h, [&](Carver &c) {
-        c.take(d_p1, nP); c.take(d_out, out ? (size_t)5 * nQ : 0); c.take(d_status, status ? (size_t)nQ : 0);
-        c.take(d_part, stats ? (size_t)nb * SITRK_MESH_NSTATS : 0); c.take(d_stats, SITRK_MESH_NSTATS);
+        c.take(d_p1, nQ ? nP : 0); c.take(d_out, want_out ? (size_t)5 * nQ : 0); c.take(d_status, want_status ? (size_t)nQ : 0);
+        c.take(d_part, want_stats ? (size_t)nb * SITRK_MESH_NSTATS : 0); c.take(d_stats, nQ ? SITRK_MESH_NSTATS : 0);
+        c.take(d_extra, extra);
     }));
+    *r = MeshDeformDev();
+    r->extra = d_extra;
+    if (nQ == 0) return SITRK_OK;
+    h->mesh_deform_timed = false;
     HIPCHK(hipEventRecord(h->mesh_ev[2], h->stream));
     RCCHK(deform_points_span(h, m.jrec0, jrec1, d_p1));
     HIPCHK(hipEventRecord(h->mesh_ev[3], h->stream));
     hipLaunchKernelGGL(mesh_cells_kernel, dim3((unsigned)nb), dim3(kMeshThreads), 0, h->stream, nQ, (const int4 *)m.quads, m.t0, d_p1, T, m.par,
-                       out ? d_out : nullptr, status ? d_status : nullptr, stats ? d_part : nullptr);
+                       want_out ? d_out : nullptr, want_status ? d_status : nullptr, want_stats ? d_part : nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->mesh_ev[4], h->stream));
-    if (stats) {
+    if (want_stats) {
         hipLaunchKernelGGL(mesh_sum_kernel, dim3(1), dim3(kMeshThreads), 0, h->stream, nb, d_part, d_stats);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(h->mesh_ev[5], h->stream));
     h->mesh_deform_timed = true;
-    if (out) HIPCHK(download(h, out, d_out, (size_t)5 * nQ));
-    if (status) HIPCHK(download(h, status, d_status, (size_t)nQ));
-    if (stats) HIPCHK(download(h, stats, d_stats, (size_t)SITRK_MESH_NSTATS));
+    r->nQ = nQ; r->quads = m.quads; r->t0 = m.t0; r->p1 = d_p1;
+    r->out = want_out ? d_out : nullptr; r->status = want_status ? d_status : nullptr; r->stats = want_stats ? d_stats : nullptr;
+    return SITRK_OK;
+}
+
+SITRK_API int sitrk_mesh_deform(sitrk_t *h, int mesh, int jrec1, double *out, int8_t *status, double *stats)
+{
+    const char *fn = "sitrk_mesh_deform";
+    NEED(h, "null handle");
+    RCCHK(mesh_deform_check(h, fn, mesh, jrec1));
+    if (!out && !status && !stats) return fail(h, SITRK_EINVAL, "%s: out, status and stats are all null", fn);
+    if (stats)
+        for (int k = 0; k < SITRK_MESH_NSTATS; k++) stats[k] = 0.0;
+    const int64_t nQ = h->mesh[mesh].nQ;
+    if (nQ == 0) return SITRK_OK;
+    MeshDeformDev d;
+    RCCHK(mesh_deform_core(h, mesh, jrec1, out != nullptr, status != nullptr, stats != nullptr, 0, &d));
+    if (out) HIPCHK(download(h, out, d.out, (size_t)5 * nQ));
+    if (status) HIPCHK(download(h, status, d.status, (size_t)nQ));
+    if (stats) HIPCHK(download(h, stats, d.stats, (size_t)SITRK_MESH_NSTATS));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
 }

@@ -22,7 +22,7 @@ from os import path
 
 import numpy as np
 
-from . import _lib, ncio
+from . import _lib, ncio, raster
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
@@ -98,7 +98,16 @@ def parse_args(argv=None):
                     help='with --deform: model records per window (extra; default 0 = the whole run is one window).  Every mesh is built '
                          'anew at the start of each window and its rates are taken after the window\'s last record; a last, shorter '
                          'window is kept')
-    return ap.parse_args(argv)
+    ap.add_argument('--deform-grid', type=_deform_grid_arg, default=None,
+                    help='with --deform: D_KM or D_KM@t0 or D_KM@t1: every mesh is also rasterised, after each window, onto one regular '
+                         'grid of square D_KM pixels that covers the model\'s F-points in the polar-stereographic plane (extra; default '
+                         'none).  Per pixel the index of the cell it lies in (-1: none), stored as m<k>_w<k>_owner next to `grid` = (y0, '
+                         'x0, d, ny, nx) and `grid_at`; a map is m<k>_w<k>_div[owner] where owner >= 0.  @t0 (default): the cells where '
+                         'they were at the window\'s start, @t1: where they are at its end (status 1 only).  At most 2^28 pixels')
+    a = ap.parse_args(argv)
+    if a.deform_grid is not None and not a.deform:
+        ap.error("--deform-grid: there is no mesh to rasterise without --deform")
+    return a
 
 
 def _sample_arg(text):
@@ -132,6 +141,32 @@ def _deform_arg(text):
             raise err("--deform: RD_KM must be finite and > 0, got %r" % part)
         specs.append((val[0], val[1] if len(val) == 2 else 0.))
     return specs
+
+
+def _deform_grid_arg(text):
+    """--deform-grid: (d_km, "t0" | "t1") of D_KM[@t0|@t1], D_KM finite > 0"""
+    err = argparse.ArgumentTypeError
+    tok = text.strip().split('@')
+    if len(tok) not in (1, 2) or (len(tok) == 2 and tok[1] not in ("t0", "t1")):
+        raise err("--deform-grid: expected D_KM, D_KM@t0 or D_KM@t1, got %r" % text)
+    try:
+        d = float(tok[0])
+    except ValueError:
+        raise err("--deform-grid: expected a number of km in D_KM[@t0|@t1], got %r" % text)
+    if not (np.isfinite(d) and d > 0.):
+        raise err("--deform-grid: D_KM must be finite and > 0, got %r" % text)
+    return (d, tok[1] if len(tok) == 2 else "t0")
+
+
+def deform_grid(xYf, xXf, d_km):
+    """--deform-grid: the one grid of a run, raster_grid over the model's finite F-point coordinates; refuses more than 2^28 pixels"""
+    ok = np.isfinite(xYf) & np.isfinite(xXf)
+    if not ok.any():
+        raise ValueError('--deform-grid: the model grid has no finite F-point')
+    g = raster.raster_grid(xYf[ok].min(), xYf[ok].max(), xXf[ok].min(), xXf[ok].max(), d_km)
+    if g[3] * g[4] > raster.MAX_PIXELS:
+        raise ValueError('--deform-grid: %g km over the model grid is %d x %d pixels, more than 2^28: take a coarser grid' % (d_km, g[3], g[4]))
+    return g
 
 
 def _deform_window_arg(text):
@@ -461,6 +496,8 @@ def main(argv=None):
     else:
         xYv, xXv, xYu, xXu = xYf, xXf, xYf, xXf     # never read by the cell-mean rule
     (Nj, Ni) = np.shape(imaskt)
+    # --deform-grid: one grid for the whole run, refused now -- before anything is computed -- if it is too large
+    dfm_grid = deform_grid(xYf, xXf, a.deform_grid[0]) if a.deform_grid else None
     records = ncio.ModelRecords(cf_uv)
     # --sample: every name must be a (time, y, x) variable of the SI3 file -- checked now, before anything is computed
     smp_names, smp_attrs, smp_dtype = list(a.sample), {}, {}
@@ -710,6 +747,8 @@ def main(argv=None):
             say(' *** --deform window %d mesh %d: nQ = %d, status 0/1/2 = %d/%d/%d, area-weighted mean total deformation = %s'
                 % (kw, km, len(r["status"]), stt["n0"], stt["n1"], stt["n2"],
                    '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
+            if dfm_grid is not None:                     # the map is out[:, owner] on the host: no second copy of the rates
+                dfm_out[pre + "owner"] = trk.mesh_raster(dfm_win[kw][1], dfm_grid, slot=km, at=a.deform_grid[1], fields=False)["owner"]
         clk.add("deform_s", t_d)
 
     tk = clk.add("setup_s", tk)
@@ -901,7 +940,8 @@ def main(argv=None):
         _savez_deflate(cf_dfm, meshes=np.array(a.deform, dtype=np.float64).reshape(-1, 2),
                        windows=np.array(dfm_win, dtype=np.int64).reshape(-1, 2),
                        time0=np.array([vTime[w[0] - kstrt] for w in dfm_win], dtype=np.int64),
-                       time1=np.array([vTime[w[1] - kstrt + 1] for w in dfm_win], dtype=np.int64), **dfm_out)
+                       time1=np.array([vTime[w[1] - kstrt + 1] for w in dfm_win], dtype=np.int64), **dfm_out,
+                       **({"grid": np.array(dfm_grid, dtype=np.float64), "grid_at": np.array(a.deform_grid[1])} if dfm_grid else {}))
         outs.append(cf_dfm)
 
     if a.plot > 0:

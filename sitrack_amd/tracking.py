@@ -310,6 +310,24 @@ class IceTracker:
         out = r["out"]
         return {"div": out[0], "shr": out[1], "vor": out[2], "area0": out[3], "area1": out[4], "status": r["status"], "stats": stats}
 
+    def mesh_raster(self, jrec1, grid, slot=0, at="t0", fields=True):
+        """Right after the step of `jrec1`: mesh `slot` rasterised onto the grid (y0_km, x0_km, d_km, ny, nx) of sit.raster_grid
+        (an extra the reference does not have; sitrk_mesh_raster).  A dict with owner (ny,nx) int32 -- per pixel the lowest-indexed
+        cell its centre lies in, -1 for none -- and, with fields=True, the maps div, shr, vor, area0, area1 (ny,nx) fp64: the
+        values mesh_deform() gives for that cell, FillValue where there is none.  at="t0": the cells where they were when the mesh
+        was built or marked, those of status 1 and 2; at="t1": where they are now, those of status 1.  The per-cell results stay
+        on the device: only the raster comes down."""
+        from .raster import check_grid
+        cerr = 'ERROR [IceTracker.mesh_raster()]: '
+        if at not in ("t0", "t1"):
+            raise ValueError(cerr + '`at` must be "t0" or "t1", got %r' % (at,))
+        g = check_grid(grid, cerr)
+        r = self.ctx.mesh_raster(slot, jrec1, g, at_t1=(at == "t1"), want=("owner", "fields") if fields else ("owner",))
+        res = {"owner": r["owner"]}
+        if fields:
+            res.update(zip(("div", "shr", "vor", "area0", "area1"), r["fields"]))
+        return res
+
     def mesh_free(self, slot=0):
         self.ctx.mesh_free(slot)
 

@@ -2,13 +2,16 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [-o OUT.npz]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM] [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
 positions of record K0 (Delaunay; needs scipy).  Records default to the first and the last; the elapsed time comes from
 `time`; validity from `mask` when the file has it, otherwise from the `_FillValue` of `y_pos`.  OUT (default: TRACKFILE
 with `_deform.npz` for its extension) holds div, shr, vor, tot [1/s], area0, area1 [km^2], valid, cells (the ids) and
-time0, time1.
+time0, time1.  `--grid D_KM` also rasterises the cells at their K0 positions onto square pixels of D_KM km over the bounding
+box of the valid points (sitrk_raster_cells): OUT then holds `owner` (ny, nx) int32, per pixel the row of the
+valid cell its centre lies in (the lowest on a shared edge, -1 for none), and `grid` = (y0, x0, d, ny, nx); a map is
+`div[owner]` where owner >= 0.
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -63,8 +66,12 @@ def main(argv=None):
     ap.add_argument('-k', '--k0', type=int, default=0, help='first record (default 0)')
     ap.add_argument('-K', '--k1', type=int, default=-1, help='second record (default: the last)')
     ap.add_argument('-o', '--fout', default=None, help='output file (default: <input>_deform.npz)')
+    ap.add_argument('--grid', type=float, default=None, metavar='D_KM',
+                    help='also rasterise the valid cells at their first-record positions onto pixels of D_KM km (`owner`, `grid` in the output)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
+    if a.grid is not None and not (np.isfinite(a.grid) and a.grid > 0.):
+        sys.exit('ERROR: --grid: D_KM must be finite and > 0, got %r' % a.grid)
     ncio.chck4f(a.fin)
     with ncio._Reader(a.fin) as f:
         for cv in ('time', 'id_buoy', 'y_pos', 'x_pos'):
@@ -104,11 +111,22 @@ def main(argv=None):
     ctx = sit.Context(a.device)
     try:
         r = sit.DeformCells(yx0, yx1, cols, T, mask0=ok0, mask1=ok1, ctx=ctx)
+        if a.grid is not None:
+            if not ok0.any():
+                sys.exit('ERROR: --grid: no valid buoy at record %d' % k0)
+            grid = sit.raster_grid(yx0[ok0, 0].min(), yx0[ok0, 0].max(), yx0[ok0, 1].min(), yx0[ok0, 1].max(), a.grid)
+            if grid[3] * grid[4] > 2 ** 28:
+                sys.exit('ERROR: --grid: %g km over the points is %d x %d pixels, more than 2^28' % (a.grid, grid[3], grid[4]))
+            r['owner'] = sit.RasterCells(yx0, cols, grid, draw=r['valid'], ctx=ctx)
+            r['grid'] = np.array(grid, dtype=np.float64)
     finally:
         ctx.close()
     fout = a.fout or os.path.splitext(a.fin)[0] + '_deform.npz'
     np.savez(fout, cells=cell_ids, time0=vtime[k0], time1=vtime[k1], **r)
     print(' *** records %d -> %d (T = %g s): %d of %d cells valid -> %s' % (k0, k1, T, int(r['valid'].sum()), len(cell_ids), fout))
+    if a.grid is not None:
+        print(' *** --grid %g km: %d x %d pixels, %d of them in a valid cell' % (a.grid, r['owner'].shape[0], r['owner'].shape[1],
+                                                                               int((r['owner'] >= 0).sum())))
     return 0
 
 
