@@ -7,18 +7,24 @@ Same flags and defaults (reference si3_part_tracker.py:42-73), same module const
 per-record inverse projection (:493) run on the GPU.  Differences, all opt-in or forced:
 extra flags `--device`, `--uv-strategy`, `--rdt` (model output period: the reference's constant 3600, or `auto` = the spacing
 of the model file's time axis) and `--nsub` (Euler sub-steps per record, default 1); under `torchrun` (WORLD_SIZE > 1) the buoys are range-partitioned over the
-ranks by latitude band and every rank reads only the rows of each record its own buoys can touch (row-band ingest, no
-collective; `--full-records`: rank 0 reads, RCCL broadcast), rank 0 writes the files; errors raise instead of
+ranks by latitude band and every rank reads only the box (rows x columns) of each record its own buoys can touch (box
+ingest, no collective; `--full-records`: rank 0 reads, RCCL broadcast), rank 0 writes the files; errors raise instead of
 `print; exit(0)`; maps need the
 optional `mojito` package and are skipped without it; the full (Nt+1,nP,2) series is NEVER held in host memory (the
 reference keeps it twice, si3_part_tracker.py:324-330: 320 GB at 1e7 buoys x 1000 records): with `-F` every record is
 appended to the series file as it is fetched (ncio.CloudBuoysStream: O(nP) memory), `--out-stride K` writes every K-th
 record only, and the always-written 2-record file keeps records 0 and Nt.
+
+`main()` is the run itself: open_run, read_mesh / sample_vars, init_seeds / seed_windows, open_tracker, then the record loop
+over plan_batches.  What the loop keeps between batches lives in one object per concern -- Partition (who owns which buoys,
+re-balancing), BoxIngest (which hyperslab of a record is read), Outputs (the series and the two-record file) and, where the
+run asks for them, Sampler (--sample) and DeformSeries (--deform), None otherwise.
 """
 import argparse
 import os
 from datetime import datetime, timezone
 from os import path
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -449,73 +455,76 @@ def _tame_malloc():
         pass
 
 
-def main(argv=None):
-    a = parse_args(argv)
-    _tame_malloc()
-    clk = _Clock()
-    cf_uv, cf_mm, fNCseed, jrecSeed, cdate_stop, CONF = a.fsi3, a.fmmm, a.fsdg, a.krec, a.dend, a.ncnf
-    lUse2DTime = not a.fxdt
-    iUVstrategy = a.uv_strategy
-    comm = Comm()
-    if a.deform and comm.multi:
-        comm.close()
-        raise ValueError('--deform: the cells of a mesh would span the ranks\' buoy ranges; run it on one rank (%d ranks here)' % comm.world)
-    say = print if comm.root else (lambda *args, **kw: None)
-    say('\n *** SITRACK ice particule tracker, GPU build; NetCDF backend = ' + ncio.backend()
-        + ('; %d ranks (%s)' % (comm.world, comm.backend) if comm.multi else ''))
-    say(' *** SI3 file =>', cf_uv, '\n *** mesh_mask =>', cf_mm, '\n *** seeding  =>', fNCseed, jrecSeed)
+def out_file(run, kind, t0, t1, ext='nc', tail=''):
+    """./<ext>/<origin>_<kind>_<seed batch><time-bin tag>_<first date>_<last date><resolution tag><tail>.<ext> (reference :510-517,565-568)"""
+    return ('./' + ext + '/' + run.corgn + '_' + kind + '_' + run.SeedBatch + run.cdtbin + '_' + date_tag(t0) + '_' + date_tag(t1)
+            + run.csfkm + tail + '.' + ext)
 
-    cdtbin, csfkm = seed_name_tokens(path.basename(fNCseed))
-    idateSeedA, idateSeedB, SeedName, SeedBatch, zTpos = ncio.SeedFileTimeInfo(fNCseed, ltime2d=lUse2DTime)
-    Nt0, ztime_model, idateModA, idateModB, ModConf, ModExp = ncio.ModelFileTimeInfo(cf_uv)
+
+def open_run(a, comm, say):
+    """Run opening: the span of model records the seeding file asks for, the period and sub-steps of a record, the tags of the
+    output names; makes the output directories (rank 0).  None when no model record matches."""
+    lUse2DTime = not a.fxdt
+    cdtbin, csfkm = seed_name_tokens(path.basename(a.fsdg))
+    idateSeedA, idateSeedB, SeedName, SeedBatch, zTpos = ncio.SeedFileTimeInfo(a.fsdg, ltime2d=lUse2DTime)
+    Nt0, ztime_model, idateModA, idateModB, ModConf, ModExp = ncio.ModelFileTimeInfo(a.fsi3)
     rdt = run_rdt(a.rdt, ztime_model, say)              # the module constant's value unless --rdt says otherwise
-    nsub = a.nsub
-    if rdt != 3600. or nsub != 1:
-        say(' *** rdt = %g s per model record, %d Euler sub-step(s) of %g s each' % (rdt, nsub, rdt / nsub))
+    if rdt != 3600. or a.nsub != 1:
+        say(' *** rdt = %g s per model record, %d Euler sub-step(s) of %g s each' % (rdt, a.nsub, rdt / a.nsub))
 
     date_stop = None
-    if cdate_stop:
-        date_stop = clock2epoch(cdate_stop)
+    if a.dend:
+        date_stop = clock2epoch(a.dend)
     elif idateSeedB - idateSeedA >= 3600.:
         date_stop = idateSeedB                      # several records in the seeding file: replicate its time span (:168-172)
     Nt, kstrt, kstop, iTmA, iTmB = GetTimeSpan(rdt, ztime_model, idateSeedA, idateModA, idateModB, iStop=date_stop)
     if Nt < 1:
         say(' QUITTING since no matching model records!')
-        comm.close()
-        return 0
+        return None
     say(' *** model records %d..%d (%d records): %s -> %s' % (kstrt, kstop, Nt, epoch2clock(iTmA), epoch2clock(iTmB)))
     if comm.root:
         for cd in ('seed', 'nc', 'npz'):
             os.makedirs(cd, exist_ok=True)
+    return SimpleNamespace(lUse2DTime=lUse2DTime, cdtbin=cdtbin, csfkm=csfkm, SeedName=SeedName, SeedBatch=SeedBatch, zTpos=zTpos,
+                           Nt0=Nt0, ztime_model=ztime_model, corgn='NEMO-SI3_' + ModConf + '_' + ModExp, rdt=rdt, nsub=a.nsub,
+                           Nt=Nt, kstrt=kstrt, kstop=kstop, iTmA=iTmA, iTmB=iTmB)
 
-    ctx = _lib.Context(comm.device if comm.multi else a.device)
-    tk = clk.now()
-    imaskt, xlatT, xlonT, xYt, xXt, xYf, xXf, xResKM = ncio.GetModelGrid(cf_mm, ctx=ctx)
-    if iUVstrategy >= 1:
-        xYv, xXv, xYu, xXu = ncio.GetModelUVGrid(cf_mm, ctx=ctx)
+
+def read_mesh(a, ctx):
+    """The model mesh (projected on the GPU of `ctx`) and, with --deform-grid, the one grid of the run: refused here -- before
+    the model records are opened or anything is computed -- if it is too large."""
+    imaskt, xlatT, xlonT, xYt, xXt, xYf, xXf, xResKM = ncio.GetModelGrid(a.fmmm, ctx=ctx)
+    if a.uv_strategy >= 1:
+        xYv, xXv, xYu, xXu = ncio.GetModelUVGrid(a.fmmm, ctx=ctx)
     else:
         xYv, xXv, xYu, xXu = xYf, xXf, xYf, xXf     # never read by the cell-mean rule
     (Nj, Ni) = np.shape(imaskt)
-    # --deform-grid: one grid for the whole run, refused now -- before anything is computed -- if it is too large
     dfm_grid = deform_grid(xYf, xXf, a.deform_grid[0]) if a.deform_grid else None
-    records = ncio.ModelRecords(cf_uv)
-    # --sample: every name must be a (time, y, x) variable of the SI3 file -- checked now, before anything is computed
-    smp_names, smp_attrs, smp_dtype = list(a.sample), {}, {}
-    for n in smp_names:
+    return SimpleNamespace(imaskt=imaskt, xlatT=xlatT, xlonT=xlonT, xYf=xYf, xXf=xXf, xYu=xYu, xXu=xXu, xYv=xYv, xXv=xXv,
+                           xResKM=xResKM, Nj=Nj, Ni=Ni, dfm_grid=dfm_grid)
+
+
+def sample_vars(names, records, cf_uv, kstrt, Nj, Ni):
+    """--sample: every name must be a (time, y, x) variable of the SI3 file -- checked before anything is computed.  Returns
+    the attributes the files give each variable and the type (f4 / f8) it is sampled in."""
+    attrs, dtype = {}, {}
+    for n in names:
         if not records.f.has_var(n):
             raise ValueError("--sample: the SI3 file %s has no variable '%s'" % (cf_uv, n))
         x0 = np.asarray(records.fields(kstrt, (n,))[0])
         if x0.shape != (Nj, Ni):
             raise ValueError("--sample: variable '%s' of %s is not a (time, y, x) field of the %d x %d mesh" % (n, cf_uv, Nj, Ni))
-        smp_attrs[n] = ncio.model_var_attrs(records.f, n)
-        smp_dtype[n] = np.dtype(np.float32) if x0.dtype.newbyteorder('=') == np.float32 else np.dtype(np.float64)
+        attrs[n] = ncio.model_var_attrs(records.f, n)
+        dtype[n] = np.dtype(np.float32) if x0.dtype.newbyteorder('=') == np.float32 else np.dtype(np.float64)
         if n in ncio.SCHEMA_VARS:
             raise ValueError("--sample: '%s' collides with a variable of the trajectory files" % n)
-    tk = clk.add("read_mesh_s", tk)
+    return attrs, dtype
 
-    # ---- seeding, with the reference's intermediate cache (:205-255).  Seeds are independent: with several ranks
-    #      each one locates its own contiguous range and the results are concatenated in rank (= seed) order.
-    cf_npz_itm = './seed/Initialized_buoys_' + SeedName + '_' + CONF + '.npz'
+
+def init_seeds(a, run, mesh, records, comm, ctx, say):
+    """Seeding, with the reference's intermediate cache (:205-255).  Seeds are independent: with several ranks each one
+    locates its own contiguous range and the results are concatenated in rank (= seed) order."""
+    cf_npz_itm = './seed/Initialized_buoys_' + run.SeedName + '_' + a.ncnf + '.npz'
     if comm.bcast_obj(path.exists(cf_npz_itm)):
         say(' *** using cached seed initialisation ' + cf_npz_itm)
         pack = None
@@ -525,314 +534,507 @@ def main(argv=None):
         xPosG0, xPosC0, IDs, vJIt, VRTCS, idxK = comm.bcast_arrays(pack)          # tensors, not pickles
         nP = len(IDs)
     else:
-        (xIC,) = records.fields(kstrt, ('siconc',))
-        zt, zIDs, XseedG, XseedC = ncio.LoadNCdata(fNCseed, krec=jrecSeed)
+        (xIC,) = records.fields(run.kstrt, ('siconc',))
+        zt, zIDs, XseedG, XseedC = ncio.LoadNCdata(a.fsdg, krec=a.krec)
         (nP0, _) = np.shape(XseedG)
         IDs = np.array(zIDs, dtype=int)
         lo, hi = comm.range(nP0)
-        part = SeedInit(IDs[lo:hi], XseedG[lo:hi], XseedC[lo:hi], xlatT, xlonT, xYf, xXf, xResKM, imaskt,
+        kept = SeedInit(IDs[lo:hi], XseedG[lo:hi], XseedC[lo:hi], mesh.xlatT, mesh.xlonT, mesh.xYf, mesh.xXf, mesh.xResKM, mesh.imaskt,
                         xIceConc=np.asarray(xIC, dtype=np.float64), ctx=ctx)
         # every rank's kept seeds, concatenated in rank (= seed) order: tensor all-gathers
-        xPosG0, xPosC0, IDs, vJIt, VRTCS, idxK = comm.allgather_rows(part[1:6] + (lo + part[6],))
+        xPosG0, xPosC0, IDs, vJIt, VRTCS, idxK = comm.allgather_rows(kept[1:6] + (lo + kept[6],))
         nP = len(IDs)
         if nP < nP0:
             say(' *** `SeedInit()` had to cancel ' + str(nP0 - nP) + ' buoys! => nP = ' + str(nP))
         if comm.root:
             _savez_deflate(cf_npz_itm, nP=nP, xPosG0=xPosG0, xPosC0=xPosC0, IDs=IDs, vJIt=vJIt, VRTCS=VRTCS, idxKeep=idxK)
+    return SimpleNamespace(nP=nP, xPosG0=xPosG0, xPosC0=xPosC0, IDs=IDs, vJIt=vJIt, idxK=idxK)
 
-    tk = clk.add("seed_init_and_cache_s", tk)
-    # ---- per-buoy record windows (:264-318)
-    z1stModelRec = np.zeros(nP, dtype=int) + kstrt
-    zLstModelRec = np.zeros(nP, dtype=int) + kstop
-    if lUse2DTime:
-        zTpos = zTpos if np.ma.isMaskedArray(zTpos) else np.asarray(zTpos)
-        if zTpos.shape != (2, nP) and zTpos.ndim == 2 and zTpos.shape[1] > nP and len(idxK) == nP:
-            # SeedInit cancelled buoys: keep the time positions of the survivors.  (The reference has this line
-            # commented out, si3_part_tracker.py:250, and then stops on the shape check of :269-272.)
-            say(' *** adjusting `zTpos` to the %d buoys kept by SeedInit' % nP)
-            zTpos = zTpos[:, idxK]
-        if zTpos.shape != (2, nP):
-            raise ValueError('wrong shape for the 2D time array `zTpos`: %s vs nP=%d' % (zTpos.shape, nP))
-        z1stModelRec, zLstModelRec = record_windows(zTpos, ztime_model, kstrt, kstop, iTmA, iTmB, nP, rdt=rdt)
-    k0 = z1stModelRec - kstrt
 
-    # ---- device state.  Under torchrun every rank owns a contiguous range of the buoys ordered by host row, i.e. a
-    #      latitude band: with row-band ingest each rank then reads only its own rows of every record, no collective.
-    order = np.argsort(vJIt[:, 0], kind='stable') if comm.multi else np.arange(nP)
-    lo, hi = comm.range(nP)
-    part = {"order": order, "mine": order[lo:hi]}          # who owns what; re-made by rebalance()
-    mine = part["mine"]
+def seed_windows(run, seeds, say):
+    """Per-buoy first / last model record (:264-318): the whole run with -F, record_windows() of the seeding file's 2-D time
+    otherwise."""
+    nP = seeds.nP
+    if not run.lUse2DTime:
+        return np.zeros(nP, dtype=int) + run.kstrt, np.zeros(nP, dtype=int) + run.kstop
+    zTpos = run.zTpos if np.ma.isMaskedArray(run.zTpos) else np.asarray(run.zTpos)
+    if zTpos.shape != (2, nP) and zTpos.ndim == 2 and zTpos.shape[1] > nP and len(seeds.idxK) == nP:
+        # SeedInit cancelled buoys: keep the time positions of the survivors.  (The reference has this line
+        # commented out, si3_part_tracker.py:250, and then stops on the shape check of :269-272.)
+        say(' *** adjusting `zTpos` to the %d buoys kept by SeedInit' % nP)
+        zTpos = zTpos[:, seeds.idxK]
+    if zTpos.shape != (2, nP):
+        raise ValueError('wrong shape for the 2D time array `zTpos`: %s vs nP=%d' % (zTpos.shape, nP))
+    return record_windows(zTpos, run.ztime_model, run.kstrt, run.kstop, run.iTmA, run.iTmB, nP, rdt=run.rdt)
 
-    def to_caller_order(rows):            # rows gathered in rank order -> the caller's buoy order
-        if rows is None or not comm.multi:
-            return rows
-        out = np.empty_like(rows)
-        out[part["order"]] = rows
-        return out
 
-    (u0,) = records.fields(kstrt, ('u_ice',))
+def open_tracker(a, run, mesh, records, ctx):
+    """The tracker on the device: `K` resident record slots of the model file's type; with --tinterp the ring and the `K_plan`
+    plan_batches is given are those of tinterp_slots().  Returns (trk, K, K_plan, tphase), tphase None without --tinterp."""
+    (u0,) = records.fields(run.kstrt, ('u_ice',))
     fdt = np.float64 if np.asarray(u0).dtype == np.float64 else np.float32
     K = int(max(2, min(a.slots, 64)))
     tphase = None if a.tinterp == 'off' else tinterp_phase(a.tinterp)
     K_plan = K
     if tphase is not None:
         K, K_plan = tinterp_slots(K)
-    trk = IceTracker(xYf, xXf, xYu, xXu, xYv, xXv, imaskt, rdt=rdt, iUVstrategy=iUVstrategy, nslots=K, field_dtype=fdt, ctx=ctx,
-                     nsub=nsub)
-    trk.set_buoys(xPosC0[mine], vJIt[mine], z1stModelRec[mine] if lUse2DTime else None, zLstModelRec[mine] if lUse2DTime else None)
+    trk = IceTracker(mesh.xYf, mesh.xXf, mesh.xYu, mesh.xXu, mesh.xYv, mesh.xXv, mesh.imaskt, rdt=run.rdt, iUVstrategy=a.uv_strategy,
+                     nslots=K, field_dtype=fdt, ctx=ctx, nsub=run.nsub)
+    return trk, K, K_plan, tphase
 
-    # ---- outputs (rank 0).  The reference allocates the whole series -- xPosC, xPosG (Nt+1,nP,2) f8, xmask -- and writes it at the
-    #      end (:324-330,515-519).  Here the series file is opened now and every record is appended when it is fetched: host
-    #      memory stays O(nP).  Its time axis is known in advance (record times of the model file).
-    lFull = not lUse2DTime
-    stride = max(1, int(a.out_stride)) if lFull else 1
-    vTime = np.zeros(Nt + 1, dtype=int)
-    for jt_ in range(Nt):
-        vTime[jt_] = records.time(jt_ + kstrt) - int(rdt / 2.)
-    vTime[Nt] = vTime[Nt - 1] + int(rdt)
-    corgn = 'NEMO-SI3_' + ModConf + '_' + ModExp
-    series, cf_series = None, None
-    if lFull and comm.root:
-        cf_series = ('./nc/' + corgn + '_tracking_' + SeedBatch + cdtbin + '_' + date_tag(vTime[0]) + '_' + date_tag(vTime[Nt]) + csfkm
-                     + ('_stride%d' % stride if stride > 1 else '') + '.nc')
-        series = ncio.CloudBuoysStream(cf_series, vTime[::stride], IDs, with_mask=True, corigin=corgn,
-                                       extra_names={n: smp_attrs[n] for n in smp_names} if smp_names else None)
-        # record 0: the seeds as the seeding file gave them (:331-333; in 1-D-time mode every window opens at record 0); with
-        # --sample it waits for the fields sampled in the seeds' cells, in front of the first step
-        if not smp_names:
-            series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'))
-        z2XY, z2GC = np.zeros((2, nP, 2)) + FILL, np.zeros((2, nP, 2)) + FILL
-        zMSK = np.zeros((2, nP), dtype='i1')
-        z2XY[0], z2GC[0], zMSK[0] = xPosC0, xPosG0, 1
-    if lUse2DTime:
-        ends = set(np.unique(zLstModelRec).tolist())
+
+def record_broadcaster(a, comm, ctx, tphase):
+    """--full-records under an RCCL launch: rank 0 reads; one RCCL broadcast per record, overlapped with the stepping.  None
+    for every other run."""
+    if not (a.full_records and comm.multi and comm.backend == "nccl"):
+        return None
+    from .distributed import RecordBroadcaster
+    if tphase is not None:
+        raise ValueError('--tinterp is not available together with --full-records under an RCCL launch (the record broadcaster '
+                         'hands a slot back before its partner has been stepped with): drop --full-records')
+    return RecordBroadcaster(ctx)
+
+
+def rebalance_places(rows, allh, rank, ranges):
+    """Re-balancing: where the buoys of rank `rank` go.  rows: their host rows, in local order; allh (world, Nj): every rank's
+    histogram of host rows; ranges: all_ranges(nP, world).  Returns newpos, each buoy's place in the new global order -- by
+    (row, owning rank, local order) -- and dest, the rank whose range that place falls in."""
+    hist = allh[rank]
+    before_row = np.concatenate([[0], np.cumsum(allh.sum(axis=0))[:-1]])    # buoys in lower rows
+    before_rank = allh[:rank].sum(axis=0)                                   # same row, lower ranks
+    o = np.argsort(rows, kind='stable')
+    within = np.empty(len(rows), dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(hist)[:-1]])
+    within[o] = np.arange(len(rows)) - starts[rows[o]]                      # same row, this rank, local order
+    newpos = before_row[rows] + before_rank[rows] + within
+    ends = np.array([hi for _, hi in ranges])
+    return newpos, np.searchsorted(ends, newpos, side='right')
+
+
+def rebalance_due(batches, every, multi):
+    """after which batches the ranks re-balance: a function of the record count alone (never after the last one)"""
+    due, since = [], 0
+    for (_, m) in batches:
+        since += m
+        due.append(multi and every > 0 and since >= every)
+        if due[-1]:
+            since = 0
+    if due:
+        due[-1] = False
+    return due
+
+
+class Partition:
+    """Who owns which buoys.  Under torchrun every rank owns a contiguous range of the buoys ordered by host row, i.e. a
+    latitude band: with box ingest each rank then reads only its own rows of every record, no collective.
+      order    the caller's indices of all buoys in rank order (rank 0 keeps it up to date)
+      mine     those of this rank;  range: its [lo, hi) of `order` at the start
+      windows  (first, last) model record of every buoy in the caller's order, None with -F"""
+
+    def __init__(self, comm, vJIt, nP, Nj, windows=None):
+        self.comm, self.nP, self.Nj, self.windows = comm, nP, Nj, windows
+        self.order = np.argsort(vJIt[:, 0], kind='stable') if comm.multi else np.arange(nP)
+        self.range = comm.range(nP)
+        self.mine = self.order[self.range[0]:self.range[1]]
+        self.rebalances = self.migrated = 0
+
+    def to_caller_order(self, rows):
+        """rows gathered in rank order -> the caller's buoy order"""
+        if rows is None or not self.comm.multi:
+            return rows
+        out = np.empty_like(rows)
+        out[self.order] = rows
+        return out
+
+    def gather(self, rows):
+        """this rank's rows -> all buoys' rows in the caller's order on rank 0, None elsewhere"""
+        return self.to_caller_order(self.comm.gather_rows(rows, self.nP))
+
+    def rebalance(self, ctx, ingest):
+        """Re-partition the buoys over the ranks by their CURRENT host row (SURVEY 8f-4: migration / re-balancing).
+        Each rank fetches its buoys' state, a global histogram of host rows fixes every buoy's place in the new order
+        (rebalance_places), hence its new owner; the states travel in one all-to-all of 50-byte rows and every rank
+        re-creates its buoy set with their history (dead flags, kill records).  Trajectories do not depend on who steps a
+        buoy; only the rows a rank has to read do: `ingest` starts over."""
+        comm = self.comm
+        st = ctx.fetch()
+        rows = st["jiT"][:, 0].astype(np.int64)
+        hist = np.bincount(rows, minlength=self.Nj).astype(np.int64)
+        allh = comm.allgather_rows((hist[None, :],))[0]                        # (world, Nj)
+        newpos, dest = rebalance_places(rows, allh, comm.rank, all_ranges(self.nP, comm.world))
+        f8 = np.concatenate([st["yx"], newpos[:, None].astype(np.float64)], axis=1)          # positions travel exactly
+        win = (self.windows[0][self.mine], self.windows[1][self.mine]) if self.windows else (np.zeros(len(rows), dtype=int),) * 2
+        i8 = np.stack([self.mine.astype(np.int64), st["jiT"][:, 0].astype(np.int64), st["jiT"][:, 1].astype(np.int64),
+                       st["alive"].astype(np.int64), st["kill_rec"].astype(np.int64), np.asarray(win[0], dtype=np.int64),
+                       np.asarray(win[1], dtype=np.int64)], axis=1)
+        self.rebalances += 1
+        self.migrated += comm.sum_int(int((dest != comm.rank).sum()))
+        chunks = [(f8[dest == d], i8[dest == d]) for d in range(comm.world)]
+        rf8, ri8 = comm.alltoall_rows(chunks)
+        k = np.argsort(rf8[:, 2], kind='stable')                               # the new order inside this rank's range
+        rf8, ri8 = rf8[k], ri8[k]
+        self.mine = ri8[:, 0].copy()
+        ctx.set_buoys(np.ascontiguousarray(rf8[:, :2]), ri8[:, 1:3].astype(np.int32),
+                      ri8[:, 5].astype(np.int32) if self.windows else None, ri8[:, 6].astype(np.int32) if self.windows else None, sort=False)
+        ctx.restore_state(ri8[:, 3].astype(np.int8), ri8[:, 4].astype(np.int32))
+        ctx.sort_buoys()
+        allmine = comm.gather_rows(self.mine, self.nP)
         if comm.root:
-            z2XY, z2GC = np.zeros((2, nP, 2)) + FILL, np.zeros((2, nP, 2)) + FILL
-            zMSK, zTim = np.zeros((2, nP), dtype='i1'), np.zeros((2, nP), dtype=int) + int(FILL)
-            z2XY[0], z2GC[0], zMSK[0] = xPosC0, xPosG0, 1
-            zTim[0] = ztime_model[z1stModelRec] - int(rdt / 2)
+            self.order = allmine
+        ingest.reset()
+
+
+class BoxIngest:
+    """Record ingest: records jt -> slots jt % K, asynchronously.  By default only the box (rows x columns, round 4) this
+    rank's buoys can touch is read from the file and uploaded: their host cells at the last evaluation, widened by one cell
+    per record stepped or queued since (sitrk_buoy_box waits for the GPU: only every REEVALUATE_AFTER records).
+      boxes    batch start jt0 -> (j0, j1, i0, i1), what the batch's slots hold: the box its records are sampled in.  Empty
+               with --full-records (whole records; under torchrun rank 0 reads and the record is broadcast)
+      bytes    read and uploaded so far"""
+    REEVALUATE_AFTER = 96
+
+    def __init__(self, ctx, records, comm, clk, kstrt, K, Nj, esz, full_records=False, tinterp=False, bcast=None):
+        self.ctx, self.records, self.comm, self.clk, self.bcast = ctx, records, comm, clk, bcast
+        self.kstrt, self.K, self.Nj, self.esz, self.full_records, self.tinterp = kstrt, K, Nj, esz, full_records, tinterp
+        self.box, self.age, self.bytes, self.boxes = None, None, 0, {}
+
+    def reset(self):
+        """the buoys are others now (re-balancing): their box is evaluated at the next batch"""
+        self.age = None
+
+    def plan(self, jt0, m, not_queued=0):
+        """the box of the batch jt0..jt0+m-1; not_queued: records planned in front of it that the GPU has not been given yet"""
+        if self.full_records:
+            return
+        if self.age is None or self.age + m > self.REEVALUATE_AFTER:
+            self.box = self.ctx.buoy_box()
+            self.age = not_queued
+        self.boxes[jt0] = self.ctx.box_of(*self.box, batch_box_age(self.age, m, self.tinterp))
+        self.age += m
+
+    def upload(self, jt0, m):
+        """records jt0..jt0+m-1 -> slots (jt0+r) % K"""
+        self.plan(jt0, m)
+        self.upload_recs(jt0, range(jt0, jt0 + m))
+
+    def upload_recs(self, jt0, jts):
+        """records jts of (or, as a partner, next to) the batch that starts at jt0 -> slots jt % K, over that batch's box"""
+        t_up = self.clk.now()
+        ctx, records, comm, Nj = self.ctx, self.records, self.comm, self.Nj
+        if not self.full_records:
+            j0, j1, i0, i1 = self.boxes[jt0]
+        for jt_r in jts:
+            jrec, slot = jt_r + self.kstrt, jt_r % self.K
+            if not self.full_records:
+                if j1 > j0:
+                    ctx.stage_fill(slot, j0, j1 - j0, lambda *outs: records.fields_box_into(jrec, j0, j1, i0, i1, outs), i0=i0, ncols=i1 - i0)
+                    self.bytes += 3 * (j1 - j0) * (i1 - i0) * self.esz
+                else:
+                    ctx.commit_record_rows(slot, 0, 0)                  # no live buoy: nothing to read
+            elif not comm.multi:
+                ctx.stage_fill(slot, 0, Nj, lambda *outs: records.fields_rows_into(jrec, 0, Nj, outs))   # the whole record (:372-374)
+            elif self.bcast is not None:
+                self.bcast.deliver(slot, records.fields(jrec) if comm.root else None)
+            else:
+                comm.deliver_record(ctx, slot, records.fields(jrec) if comm.root else None)   # gloo rehearsal: host broadcast
+        self.clk.add("read_and_stage_records_s", t_up)
+
+
+class Sampler:
+    """--sample: the model fields at the buoys, written next to the positions.
+      firsts   the model records in front of which seeds are sampled before the step: record kstrt with -F, every distinct
+               first record of the windows otherwise
+      keep()   fills the two rows of the tracking12 file (rank 0)"""
+
+    def __init__(self, names, attrs, dtype, ctx, records, part, clk, kstrt, K, Nj, Ni, z1st=None):
+        self.names, self.attrs, self.dtype = list(names), attrs, dtype
+        self.ctx, self.records, self.part, self.clk, self.kstrt, self.K, self.Nj, self.Ni = ctx, records, part, clk, kstrt, K, Nj, Ni
+        self.firsts = set(np.unique(z1st).tolist()) if z1st is not None else {kstrt}
+        self.zS = {n: np.full((2, part.nP), FILL, dtype=np.float32) for n in self.names} if part.comm.root else None
+
+    def sample(self, jrec, box, mode):
+        """The fields at this rank's buoys for model record jrec -- 'enter' before its step, 'after' behind it -- gathered into
+        (nP, names) f4 in the caller's order on rank 0 (None elsewhere).  siconc comes from the resident slot; the other
+        variables are read from the file for this record only, as the `box` the batch's slots hold (a buoy's cell stays
+        inside it during the batch; None: whole records), and travel to the GPU through sitrk_sample_fields."""
+        t_s = self.clk.now()
+        names, ctx = self.names, self.ctx
+        nloc = len(self.part.mine)
+        rows = np.full((nloc, len(names)), FILL, dtype=np.float32)
+        if nloc and (box is None or (box[1] > box[0] and box[3] > box[2])):
+            for dt in (np.dtype(np.float32), np.dtype(np.float64)):
+                cols = [k for k, n in enumerate(names) if n != 'siconc' and self.dtype[n] == dt]
+                for b in range(0, len(cols), _lib.SAMPLE_MAX_FIELDS):
+                    grp = cols[b:b + _lib.SAMPLE_MAX_FIELDS]
+                    j0, j1, i0, i1 = box if box is not None else (0, self.Nj, 0, self.Ni)
+                    bufs = [np.empty((j1 - j0, i1 - i0), dtype=dt) for _ in grp]
+                    self.records.fields_box_into(jrec, j0, j1, i0, i1, bufs, names=[names[k] for k in grp])
+                    rows[:, grp] = ctx.sample_fields(jrec, mode, bufs, box=(j0, j1, i0, i1)).T
+            if 'siconc' in names:
+                rows[:, names.index('siconc')] = ctx.sample_slot((jrec - self.kstrt) % self.K, jrec, mode, 'siconc')
+        self.clk.add("sample_s", t_s)
+        return self.part.gather(rows)
+
+    def keep(self, row, sel, srow):
+        """the sampled values srow of the buoys `sel` -> row 0 (seeds) or 1 (last positions) of the tracking12 file"""
+        for kn, n in enumerate(self.names):
+            self.zS[n][row, sel] = srow[sel, kn]
+
+    def columns(self, srow):
+        """a record of the series: {name: values of all buoys}"""
+        return {n: srow[:, kn] for kn, n in enumerate(self.names)}
+
+    def rows(self):
+        """the tracking12 file's {name: ((2, nP) values, attributes)}"""
+        return {n: (self.zS[n], self.attrs[n]) for n in self.names}
+
+
+class DeformSeries:
+    """--deform: quadrangle meshes that live on the GPU next to the buoys, built anew in front of every window of model
+    records and their rates taken behind it.
+      win      the windows [(jrec0, jrec1)];  first / last: model record -> the window it opens / closes
+      out      what is kept of every (mesh, window) for the file"""
+
+    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk):
+        self.specs, self.grid, self.grid_at = specs, grid, grid_at
+        self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
+        self.win = deform_windows(Nt, kstrt, window)
+        self.first, self.last = {w[0]: k for k, w in enumerate(self.win)}, {w[1]: k for k, w in enumerate(self.win)}
+        self.out = {}
+
+    def build(self, kw):
+        """in front of the first record of window kw: every mesh from the cloud as it is now"""
+        t_d = self.clk.now()
+        ctx, trk = self.ctx, self.trk
+        jrec0 = self.win[kw][0]
+        keep_of = {}
+        for km, (rmax, rd) in enumerate(self.specs):
+            msk = None
+            if rd > 0.:
+                if rd not in keep_of:                    # the alive cloud, coarsened to spacing rd on the positions as they are now
+                    st = ctx.fetch()
+                    al = np.asarray(st["alive"]) != 0
+                    keep = np.zeros(self.nP, dtype=np.int8)
+                    if al.any():
+                        keep[np.where(al)[0][ctx.subsample_cloud(st["yx"][al], rd)[0]]] = 1
+                    keep_of[rd] = keep
+                msk = keep_of[rd]
+            r = trk.mesh(rmax, jrec0, slot=km, mask=msk)
+            self.out["m%d_w%d_cells" % (km, kw)] = np.asarray(self.IDs)[trk.mesh_cells(km)].astype(np.int64).reshape(-1, 4)
+            self.say(' *** --deform window %d mesh %d (rmax %g km%s): %d triangles -> %d quadrangles'
+                     % (kw, km, rmax, ', rd %g km' % rd if rd > 0. else '', r["nT"], r["nQ"]))
+        self.clk.add("deform_s", t_d)
+
+    def take(self, kw):
+        """behind the last record of window kw: the rates of every mesh since the window's start"""
+        t_d = self.clk.now()
+        jrec1 = self.win[kw][1]
+        for km in range(len(self.specs)):
+            r = self.trk.mesh_deform(jrec1, slot=km)
+            pre = "m%d_w%d_" % (km, kw)
+            for n in ("div", "shr", "vor", "area0", "area1"):
+                self.out[pre + n] = r[n]
+            self.out[pre + "status"] = r["status"]
+            stt = r["stats"]
+            self.out[pre + "stats"] = np.array([stt[n] for n in _lib.MESH_STATS], dtype=np.float64)
+            self.say(' *** --deform window %d mesh %d: nQ = %d, status 0/1/2 = %d/%d/%d, area-weighted mean total deformation = %s'
+                     % (kw, km, len(r["status"]), stt["n0"], stt["n1"], stt["n2"],
+                        '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
+            if self.grid is not None:                    # the map is out[:, owner] on the host: no second copy of the rates
+                self.out[pre + "owner"] = self.trk.mesh_raster(jrec1, self.grid, slot=km, at=self.grid_at, fields=False)["owner"]
+        self.clk.add("deform_s", t_d)
+
+    def write(self, fname, vTime, kstrt):
+        """the run's .npz; vTime: the times of records 0..Nt of the series"""
+        _savez_deflate(fname, meshes=np.array(self.specs, dtype=np.float64).reshape(-1, 2),
+                       windows=np.array(self.win, dtype=np.int64).reshape(-1, 2),
+                       time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64),
+                       time1=np.array([vTime[w[1] - kstrt + 1] for w in self.win], dtype=np.int64), **self.out,
+                       **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}))
+
+
+class Outputs:
+    """The files of positions.  The reference allocates the whole series -- xPosC, xPosG (Nt+1,nP,2) f8, xmask -- and writes it
+    at the end (:324-330,515-519).  Here, with -F, the series file is opened at once and every record is appended when it is
+    fetched: host memory stays O(nP).  Its time axis is known in advance (record times of the model file).  The always-written
+    two-record `tracking12` file keeps every buoy's first and last position: rows 0 and 1 of z2XY, z2GC, zMSK (and zTim in
+    2-D-time mode), held on rank 0 only.
+      vTime    the times of records 0..Nt of the series (every rank)
+      ends     2-D-time mode: the model records some buoy's window closes with; () with -F"""
+
+    def __init__(self, run, seeds, z1st, zLst, records, ctx, stride=1, smp=None, root=True):
+        Nt, kstrt, nP = run.Nt, run.kstrt, seeds.nP
+        self.run, self.seeds, self.z1st, self.zLst, self.ctx, self.smp = run, seeds, z1st, zLst, ctx, smp
+        self.lFull = not run.lUse2DTime
+        self.stride = max(1, int(stride)) if self.lFull else 1
+        self.vTime = vTime = np.zeros(Nt + 1, dtype=int)
+        for jt in range(Nt):
+            vTime[jt] = records.time(jt + kstrt) - int(run.rdt / 2.)
+        vTime[Nt] = vTime[Nt - 1] + int(run.rdt)
+        self.ends = () if self.lFull else set(np.unique(zLst).tolist())
+        self.series, self.cf_series, self.zTim = None, None, []
+        if not root:
+            return
+        xPosC0, xPosG0 = seeds.xPosC0, seeds.xPosG0
+        if self.lFull:
+            self.cf_series = out_file(run, 'tracking', vTime[0], vTime[Nt], tail='_stride%d' % self.stride if self.stride > 1 else '')
+            self.series = ncio.CloudBuoysStream(self.cf_series, vTime[::self.stride], seeds.IDs, with_mask=True, corigin=run.corgn,
+                                                extra_names=smp.attrs if smp else None)
+            # record 0: the seeds as the seeding file gave them (:331-333; in 1-D-time mode every window opens at record 0); with
+            # --sample it waits for the fields sampled in the seeds' cells, in front of the first step
+            if not smp:
+                self.series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'))
+        self.z2XY, self.z2GC = np.zeros((2, nP, 2)) + FILL, np.zeros((2, nP, 2)) + FILL
+        self.zMSK = np.zeros((2, nP), dtype='i1')
+        self.z2XY[0], self.z2GC[0], self.zMSK[0] = xPosC0, xPosG0, 1
+        if not self.lFull:
+            self.zTim = np.zeros((2, nP), dtype=int) + int(FILL)
+            self.zTim[0] = run.ztime_model[z1st] - int(run.rdt / 2)
             # a buoy whose window opens later has its seed position pre-written at record k0, and the reference converts
             # that row to lat/lon when it passes over record k0-1 (:493)
-            late = k0 > 0
+            late = z1st - kstrt > 0
             if np.any(late):
-                z2GC[0, late] = ctx.cart2geo(xPosC0[late])
+                self.z2GC[0, late] = ctx.cart2geo(xPosC0[late])
+
+    def need(self, jrec):
+        """does the step of model record jrec produce a record that is written"""
+        return output_due(jrec, self.run.kstrt, self.run.Nt, self.lFull, self.stride, self.ends)
+
+    def fetch(self, trk, part, jrec):
+        """every rank: the record the step of jrec produced -> (pos, msk, ll) of all buoys in the caller's order on rank 0.
+        One record at a time, never the series: xPosC[jt+1], xmask[jt+1] (:459-460) and, for the series, xPosG[jt+1] =
+        CartNPSkm2Geo1D of that row, FillValue rows included (:493), converted on the device by the rank that owns the rows"""
+        ll = None
+        if self.lFull:
+            pos_l, msk_l, ll_l = trk.record(jrec, latlon=True)
+            ll = part.gather(ll_l)
+        else:
+            pos_l, msk_l = trk.record(jrec)
+        return part.gather(pos_l), part.gather(msk_l), ll
+
+    def _put(self, k, pos, ll, msk, srow):
+        try:
+            self.series.put(k, pos[:, 0], pos[:, 1], ll[:, 0], ll[:, 1], msk, extra=self.smp.columns(srow) if self.smp else None)
+        except BaseException:
+            self.series.abort()
+            raise
+
+    def seeds_sampled(self, jrec0, srow):
+        """rank 0, --sample: the seeds that start at jrec0 were sampled in that record before it moves them: row 0 of the files"""
+        self.smp.keep(0, np.where(self.z1st == jrec0)[0], srow)
+        if self.lFull:
+            self._put(0, self.seeds.xPosC0, self.seeds.xPosG0, np.ones(self.seeds.nP, dtype='i1'), srow)
+
+    def store(self, jrec, pos, msk, ll=None, srow=None):
+        """rank 0: what fetch() gave for model record jrec (and, with --sample, the fields sampled behind its step)"""
+        run = self.run
+        k = jrec - run.kstrt + 1                           # the record of the series
+        if self.lFull:
+            if k % self.stride == 0:
+                self._put(k // self.stride, pos, ll, msk, srow)
+            if k == run.Nt:
+                self.z2XY[1], self.z2GC[1], self.zMSK[1] = pos, ll, msk
+                if self.smp:
+                    self.smp.keep(1, slice(None), srow)
+        elif jrec in self.ends:
+            sel = np.where(self.zLst == jrec)[0]
+            self.z2XY[1, sel] = pos[sel]
+            self.z2GC[1, sel] = self.ctx.cart2geo(pos[sel])
+            self.zMSK[1, sel] = msk[sel]
+            self.zTim[1, sel[msk[sel] == 1]] = int(self.vTime[k - 1] + run.rdt)
+            if self.smp:
+                self.smp.keep(1, sel, srow)
+
+    def write(self):
+        """closes the series and writes the tracking12 file (:509-571); returns the files and their first and last date"""
+        outs, vTime = [], self.vTime
+        if self.lFull:
+            self.series.close()                                  # every record is in the file already
+            outs.append(self.cf_series)
+            zvt = np.array([vTime[0], vTime[self.run.Nt]])
+        else:
+            zvt = np.array([np.mean(self.zTim[0, :]), np.mean(self.zTim[1, :])])
+        cf_nc_out = out_file(self.run, 'tracking12', zvt[0], zvt[1])
+        ncio.ncSaveCloudBuoys(cf_nc_out, zvt, self.seeds.IDs, self.z2XY[:, :, 0], self.z2XY[:, :, 1], self.z2GC[:, :, 0], self.z2GC[:, :, 1],
+                              mask=self.zMSK, xtime=self.zTim, corigin=self.run.corgn, extra=self.smp.rows() if self.smp else None)
+        outs.append(cf_nc_out)
+        return outs, zvt
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    _tame_malloc()
+    clk = _Clock()
+    comm = Comm()
+    if a.deform and comm.multi:
+        comm.close()
+        raise ValueError('--deform: the cells of a mesh would span the ranks\' buoy ranges; run it on one rank (%d ranks here)' % comm.world)
+    say = print if comm.root else (lambda *args, **kw: None)
+    say('\n *** SITRACK ice particule tracker, GPU build; NetCDF backend = ' + ncio.backend()
+        + ('; %d ranks (%s)' % (comm.world, comm.backend) if comm.multi else ''))
+    say(' *** SI3 file =>', a.fsi3, '\n *** mesh_mask =>', a.fmmm, '\n *** seeding  =>', a.fsdg, a.krec)
+    run = open_run(a, comm, say)
+    if run is None:
+        comm.close()
+        return 0
+    Nt, kstrt = run.Nt, run.kstrt
+
+    # ---- mesh, records, seeds
+    ctx = _lib.Context(comm.device if comm.multi else a.device)
+    tk = clk.now()
+    mesh = read_mesh(a, ctx)
+    records = ncio.ModelRecords(a.fsi3)
+    smp_attrs, smp_dtype = sample_vars(a.sample, records, a.fsi3, kstrt, mesh.Nj, mesh.Ni)
+    tk = clk.add("read_mesh_s", tk)
+    seeds = init_seeds(a, run, mesh, records, comm, ctx, say)
+    tk = clk.add("seed_init_and_cache_s", tk)
+    z1st, zLst = seed_windows(run, seeds, say)
+    windows = (z1st, zLst) if run.lUse2DTime else None
+    nP = seeds.nP
+
+    # ---- device state, and the stages that apply to this run (None: not asked for)
+    part = Partition(comm, seeds.vJIt, nP, mesh.Nj, windows)
+    trk, K, K_plan, tphase = open_tracker(a, run, mesh, records, ctx)
+    trk.set_buoys(seeds.xPosC0[part.mine], seeds.vJIt[part.mine], z1st[part.mine] if windows else None, zLst[part.mine] if windows else None)
+    smp = Sampler(a.sample, smp_attrs, smp_dtype, ctx, records, part, clk, kstrt, K, mesh.Nj, mesh.Ni, z1st if windows else None) if a.sample else None
+    out = Outputs(run, seeds, z1st, zLst, records, ctx, a.out_stride, smp, comm.root)
+    bcast = record_broadcaster(a, comm, ctx, tphase)
+    ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
+    dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
+                       say, clk) if a.deform else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no
     #      per-record output is due between them -- always in the default 2-D-time mode, which writes first/last positions
     #      only (:565-571).  Records are read straight into the library's pinned staging and uploaded on its copy stream
     #      while the previous batch is stepped with; `-F` / `-p` need every record's positions: batches of one.
-    def need_output(jrec):
-        return output_due(jrec, kstrt, Nt, lFull, stride, ends if lUse2DTime else ())
-
-    # --sample: the two rows of the tracking12 file (root), and where seeds are sampled before the step: record kstrt with -F,
-    # every distinct first record of the windows otherwise
-    firsts = None
-    if smp_names:
-        firsts = set(np.unique(z1stModelRec).tolist()) if lUse2DTime else {kstrt}
-        zS = {n: np.full((2, nP), FILL, dtype=np.float32) for n in smp_names} if comm.root else None
-
-    bcast = None
-    if a.full_records and comm.multi and comm.backend == "nccl":
-        from .distributed import RecordBroadcaster
-        if tphase is not None:
-            raise ValueError('--tinterp is not available together with --full-records under an RCCL launch (the record broadcaster '
-                             'hands a slot back before its partner has been stepped with): drop --full-records')
-        bcast = RecordBroadcaster(ctx)                 # rank 0 reads; one RCCL broadcast per record, overlapped with the stepping
-    # --deform: the windows, the batches' cuts behind them, and what is kept of every (mesh, window) for the file
-    dfm_win = deform_windows(Nt, kstrt, a.deform_window) if a.deform else []
-    dfm_first, dfm_last = {w[0]: k for k, w in enumerate(dfm_win)}, {w[1]: k for k, w in enumerate(dfm_win)}
-    dfm_out = {}
-    batches = plan_batches(Nt, kstrt, K_plan, lFull, stride, ends if lUse2DTime else (), firsts if lUse2DTime else None,
-                           cuts=set(dfm_last) if a.deform else None)
+    batches = plan_batches(Nt, kstrt, K_plan, out.lFull, out.stride, out.ends, smp.firsts if smp and run.lUse2DTime else None,
+                           cuts=set(dfm.last) if dfm else None)
     tplan = plan_tinterp(batches, Nt, K) if tphase is not None else None
-    band = {"box": None, "age": None, "bytes": 0, "boxes": {}}
-    esz = np.dtype(fdt).itemsize
-
-    def batch_box(jt0, m, not_queued=0):
-        """the box of the batch jt0..jt0+m-1; not_queued: records planned in front of it that the GPU has not been given yet"""
-        if not a.full_records:
-            # the box (rows x columns, round 4; rows only before) this rank's buoys can touch during those records: their host
-            # cells at the last evaluation, widened by one cell per record stepped or queued since (sitrk_buoy_box waits for
-            # the GPU: only every so often).  Only that hyperslab of the record is read from the file and uploaded.
-            if band["age"] is None or band["age"] + m > 96:
-                band["box"] = ctx.buoy_box()
-                band["age"] = not_queued
-            j0, j1, i0, i1 = ctx.box_of(*band["box"], batch_box_age(band["age"], m, tphase is not None))
-            band["age"] += m
-            band["boxes"][jt0] = (j0, j1, i0, i1)            # what the batch's slots hold: the box its records are sampled in
-
-    def upload(jt0, m):
-        """records jt0..jt0+m-1 -> slots (jt0+r) % K, asynchronously"""
-        batch_box(jt0, m)
-        upload_recs(jt0, range(jt0, jt0 + m))
-
-    def upload_recs(jt0, jts):
-        """records jts of (or, as a partner, next to) the batch that starts at jt0 -> slots jt % K, over that batch's box"""
-        t_up = clk.now()
-        if not a.full_records:
-            j0, j1, i0, i1 = band["boxes"][jt0]
-        for jt_r in jts:
-            jrec, slot = jt_r + kstrt, jt_r % K
-            if not a.full_records:
-                if j1 > j0:
-                    ctx.stage_fill(slot, j0, j1 - j0, lambda *outs: records.fields_box_into(jrec, j0, j1, i0, i1, outs), i0=i0, ncols=i1 - i0)
-                    band["bytes"] += 3 * (j1 - j0) * (i1 - i0) * esz
-                else:
-                    ctx.commit_record_rows(slot, 0, 0)                  # no live buoy: nothing to read
-            elif not comm.multi:
-                ctx.stage_fill(slot, 0, Nj, lambda *outs: records.fields_rows_into(jrec, 0, Nj, outs))   # the whole record (:372-374)
-            elif bcast is not None:
-                bcast.deliver(slot, records.fields(jrec) if comm.root else None)
-            else:
-                comm.deliver_record(ctx, slot, records.fields(jrec) if comm.root else None)   # gloo rehearsal: host broadcast
-        clk.add("read_and_stage_records_s", t_up)
-
-    def sample(jrec, jt0, mode):
-        """--sample: the fields at this rank's buoys for model record jrec of the batch that starts at jt0 -- 'enter' before its
-        step, 'after' behind it -- gathered into (nP, names) f4 in the caller's order on rank 0 (None elsewhere).  siconc comes
-        from the resident slot; the other variables are read from the file for this record only, as the box the batch's slots
-        hold (a buoy's cell stays inside it during the batch), and travel to the GPU through sitrk_sample_fields."""
-        t_s = clk.now()
-        nloc = len(part["mine"])
-        rows = np.full((nloc, len(smp_names)), FILL, dtype=np.float32)
-        box = band["boxes"].get(jt0)                         # None: whole records (--full-records)
-        if nloc and (box is None or (box[1] > box[0] and box[3] > box[2])):
-            for dt in (np.dtype(np.float32), np.dtype(np.float64)):
-                cols = [k for k, n in enumerate(smp_names) if n != 'siconc' and smp_dtype[n] == dt]
-                for b in range(0, len(cols), _lib.SAMPLE_MAX_FIELDS):
-                    grp = cols[b:b + _lib.SAMPLE_MAX_FIELDS]
-                    j0, j1, i0, i1 = box if box is not None else (0, Nj, 0, Ni)
-                    bufs = [np.empty((j1 - j0, i1 - i0), dtype=dt) for _ in grp]
-                    records.fields_box_into(jrec, j0, j1, i0, i1, bufs, names=[smp_names[k] for k in grp])
-                    rows[:, grp] = ctx.sample_fields(jrec, mode, bufs, box=(j0, j1, i0, i1)).T
-            if 'siconc' in smp_names:
-                rows[:, smp_names.index('siconc')] = ctx.sample_slot((jrec - kstrt) % K, jrec, mode, 'siconc')
-        clk.add("sample_s", t_s)
-        return to_caller_order(comm.gather_rows(rows, nP))
-
-    def deform_build(kw):
-        """--deform, in front of the first record of window kw: every mesh from the cloud as it is now"""
-        t_d = clk.now()
-        jrec0 = dfm_win[kw][0]
-        keep_of = {}
-        for km, (rmax, rd) in enumerate(a.deform):
-            msk = None
-            if rd > 0.:
-                if rd not in keep_of:                    # the alive cloud, coarsened to spacing rd on the positions as they are now
-                    st = ctx.fetch()
-                    al = np.asarray(st["alive"]) != 0
-                    keep = np.zeros(nP, dtype=np.int8)
-                    if al.any():
-                        keep[np.where(al)[0][ctx.subsample_cloud(st["yx"][al], rd)[0]]] = 1
-                    keep_of[rd] = keep
-                msk = keep_of[rd]
-            r = trk.mesh(rmax, jrec0, slot=km, mask=msk)
-            dfm_out["m%d_w%d_cells" % (km, kw)] = np.asarray(IDs)[trk.mesh_cells(km)].astype(np.int64).reshape(-1, 4)
-            say(' *** --deform window %d mesh %d (rmax %g km%s): %d triangles -> %d quadrangles'
-                % (kw, km, rmax, ', rd %g km' % rd if rd > 0. else '', r["nT"], r["nQ"]))
-        clk.add("deform_s", t_d)
-
-    def deform_take(kw):
-        """--deform, behind the last record of window kw: the rates of every mesh since the window's start"""
-        t_d = clk.now()
-        for km in range(len(a.deform)):
-            r = trk.mesh_deform(dfm_win[kw][1], slot=km)
-            pre = "m%d_w%d_" % (km, kw)
-            for n in ("div", "shr", "vor", "area0", "area1"):
-                dfm_out[pre + n] = r[n]
-            dfm_out[pre + "status"] = r["status"]
-            stt = r["stats"]
-            dfm_out[pre + "stats"] = np.array([stt[n] for n in _lib.MESH_STATS], dtype=np.float64)
-            say(' *** --deform window %d mesh %d: nQ = %d, status 0/1/2 = %d/%d/%d, area-weighted mean total deformation = %s'
-                % (kw, km, len(r["status"]), stt["n0"], stt["n1"], stt["n2"],
-                   '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
-            if dfm_grid is not None:                     # the map is out[:, owner] on the host: no second copy of the rates
-                dfm_out[pre + "owner"] = trk.mesh_raster(dfm_win[kw][1], dfm_grid, slot=km, at=a.deform_grid[1], fields=False)["owner"]
-        clk.add("deform_s", t_d)
-
+    due = rebalance_due(batches, a.rebalance, comm.multi)
     tk = clk.add("setup_s", tk)
     t_loop = clk.now()
-    def rebalance():
-        """Re-partition the buoys over the ranks by their CURRENT host row (SURVEY 8f-4: migration / re-balancing).
-        Each rank fetches its buoys' state, a global histogram of host rows fixes every buoy's place in the new order --
-        by (row, owning rank, local order) -- hence its new owner; the states travel in one all-to-all of 50-byte rows and
-        every rank re-creates its buoy set with their history (dead flags, kill records).  Trajectories do not depend on
-        who steps a buoy; only the rows a rank has to read do."""
-        st = ctx.fetch()
-        mine_g = part["mine"]
-        rows = st["jiT"][:, 0].astype(np.int64)
-        hist = np.bincount(rows, minlength=Nj).astype(np.int64)
-        allh = comm.allgather_rows((hist[None, :],))[0]                        # (world, Nj)
-        before_row = np.concatenate([[0], np.cumsum(allh.sum(axis=0))[:-1]])    # buoys in lower rows
-        before_rank = allh[:comm.rank].sum(axis=0)                              # same row, lower ranks
-        o = np.argsort(rows, kind='stable')
-        within = np.empty(len(rows), dtype=np.int64)
-        starts = np.concatenate([[0], np.cumsum(hist)[:-1]])
-        within[o] = np.arange(len(rows)) - starts[rows[o]]                      # same row, this rank, local order
-        newpos = before_row[rows] + before_rank[rows] + within                  # place in the new global order
-        ends = np.array([hi_ for _, hi_ in all_ranges(nP, comm.world)])         # the new owner: whose range the place falls in
-        dest = np.searchsorted(ends, newpos, side='right')
-        f8 = np.concatenate([st["yx"], newpos[:, None].astype(np.float64)], axis=1)          # positions travel exactly
-        win = (z1stModelRec[mine_g], zLstModelRec[mine_g]) if lUse2DTime else (np.zeros(len(rows), dtype=int),) * 2
-        i8 = np.stack([mine_g.astype(np.int64), st["jiT"][:, 0].astype(np.int64), st["jiT"][:, 1].astype(np.int64),
-                       st["alive"].astype(np.int64), st["kill_rec"].astype(np.int64), np.asarray(win[0], dtype=np.int64),
-                       np.asarray(win[1], dtype=np.int64)], axis=1)
-        part["rebalances"] = part.get("rebalances", 0) + 1
-        part["migrated"] = part.get("migrated", 0) + comm.sum_int(int((dest != comm.rank).sum()))
-        chunks = [(f8[dest == d], i8[dest == d]) for d in range(comm.world)]
-        rf8, ri8 = comm.alltoall_rows(chunks)
-        k = np.argsort(rf8[:, 2], kind='stable')                               # the new order inside this rank's range
-        rf8, ri8 = rf8[k], ri8[k]
-        part["mine"] = ri8[:, 0].copy()
-        ctx.set_buoys(np.ascontiguousarray(rf8[:, :2]), ri8[:, 1:3].astype(np.int32),
-                      ri8[:, 5].astype(np.int32) if lUse2DTime else None, ri8[:, 6].astype(np.int32) if lUse2DTime else None, sort=False)
-        ctx.restore_state(ri8[:, 3].astype(np.int8), ri8[:, 4].astype(np.int32))
-        ctx.sort_buoys()
-        allmine = comm.gather_rows(part["mine"], nP)
-        if comm.root:
-            part["order"] = allmine
-        band["age"] = None                                                      # the rows this rank reads start over
-
-    due, since = [], 0
-    for (jt0, m) in batches:              # after which batches the ranks re-balance: a function of the record count alone
-        since += m
-        due.append(comm.multi and a.rebalance > 0 and since >= a.rebalance)
-        if due[-1]:
-            since = 0
-    if due:
-        due[-1] = False
     if batches:
-        upload(*batches[0])
+        ingest.upload(*batches[0])
     for ib, (jt0, m) in enumerate(batches):
         jrec0, jrecN = jt0 + kstrt, jt0 + m - 1 + kstrt
         if m == 1:
             nalive = comm.sum_int(trk.alive_count())
-            say(' *** record #%d/%d  date = %s   buoys alive = %d' % (jrec0 + 1, Nt0, epoch2clock(vTime[jt0]), nalive))
+            say(' *** record #%d/%d  date = %s   buoys alive = %d' % (jrec0 + 1, run.Nt0, epoch2clock(out.vTime[jt0]), nalive))
         else:
-            say(' *** records #%d..#%d/%d  dates = %s .. %s   (one fused launch)' % (jrec0 + 1, jrecN + 1, Nt0, epoch2clock(vTime[jt0]),
-                                                                                   epoch2clock(vTime[jt0 + m - 1])))
+            say(' *** records #%d..#%d/%d  dates = %s .. %s   (one fused launch)'
+                % (jrec0 + 1, jrecN + 1, run.Nt0, epoch2clock(out.vTime[jt0]), epoch2clock(out.vTime[jt0 + m - 1])))
         t_q = clk.now()
         used = [(jt0 + r) % K for r in range(m)]
         if bcast is not None:
             bcast.before_run(used)
-        if smp_names and jrec0 in firsts:
-            # the seeds that start at jrec0, sampled in that record before it moves them: row 0 of the files
-            srow = sample(jrec0, jt0, 'enter')
+        if smp and jrec0 in smp.firsts:
+            srow = smp.sample(jrec0, ingest.boxes.get(jt0), 'enter')
             if comm.root:
-                sel = np.where(z1stModelRec == jrec0)[0]
-                for kn, n in enumerate(smp_names):
-                    zS[n][0, sel] = srow[sel, kn]
-                if lFull:
-                    try:
-                        series.put(0, xPosC0[:, 0], xPosC0[:, 1], xPosG0[:, 0], xPosG0[:, 1], np.ones(nP, dtype='i1'),
-                                   extra={n: srow[:, kn] for kn, n in enumerate(smp_names)})
-                    except BaseException:
-                        series.abort()
-                        raise
+                out.seeds_sampled(jrec0, srow)
             t_q = clk.now()
-        if jrec0 in dfm_first:
-            deform_build(dfm_first[jrec0])
+        if dfm and jrec0 in dfm.first:
+            dfm.build(dfm.first[jrec0])
             t_q = clk.now()
         if tplan is None:
             trk.run(jrec0, jt0 % K, m)
@@ -840,8 +1042,8 @@ def main(argv=None):
             # --tinterp: the first record of the next batch is this batch's last partner: it travels in front of the launch
             # (the GPU has not been given this batch's m records yet when its box is worked out)
             if tplan[ib]["ahead"] is not None:
-                batch_box(*batches[ib + 1], not_queued=m)
-                upload_recs(batches[ib + 1][0], [tplan[ib]["ahead"]])
+                ingest.plan(*batches[ib + 1], not_queued=m)
+                ingest.upload_recs(batches[ib + 1][0], [tplan[ib]["ahead"]])
                 t_q = clk.now()
             trk.run(jrec0, jt0 % K, m, tinterp=tphase, have_prev=tplan[ib]["have_prev"], have_next=tplan[ib]["have_next"])
         if bcast is not None:
@@ -849,101 +1051,54 @@ def main(argv=None):
         clk.add("enqueue_stepping_s", t_q)
         if ib + 1 < len(batches) and not due[ib]:
             if tplan is None:
-                upload(*batches[ib + 1])           # travels while the launch above runs
+                ingest.upload(*batches[ib + 1])           # travels while the launch above runs
             else:
-                upload_recs(batches[ib + 1][0], tplan[ib]["behind"])
-        if jrecN in dfm_last:
-            deform_take(dfm_last[jrecN])
-        jt, jrec, itime = jt0 + m - 1, jrecN, vTime[jt0 + m - 1]
-        need = need_output(jrec)
+                ingest.upload_recs(batches[ib + 1][0], tplan[ib]["behind"])
+        if dfm and jrecN in dfm.last:
+            dfm.take(dfm.last[jrecN])
         t_f = clk.now()
-        if need:
-            # one record at a time, never the series: xPosC[jt+1], xmask[jt+1] (:459-460) and, for the series, xPosG[jt+1] =
-            # CartNPSkm2Geo1D of that row, FillValue rows included (:493), converted on the device by the rank that owns the rows
-            if lFull:
-                pos_l, msk_l, ll_l = trk.record(jrec, latlon=True)
-                ll = to_caller_order(comm.gather_rows(ll_l, nP))
-            else:
-                pos_l, msk_l = trk.record(jrec)
-            pos, msk = to_caller_order(comm.gather_rows(pos_l, nP)), to_caller_order(comm.gather_rows(msk_l, nP))
-            if smp_names:
+        if out.need(jrecN):
+            rec = out.fetch(trk, part, jrecN)
+            srow = None
+            if smp:
                 t_f = clk.add("fetch_and_store_outputs_s", t_f)
-                srow = sample(jrec, jt0, 'after')
+                srow = smp.sample(jrecN, ingest.boxes.get(jt0), 'after')
                 t_f = clk.now()
-        if need and comm.root:
-            stepped = msk == 1
-            if lFull:
-                k = jt + 1
-                try:
-                    if k % stride == 0:
-                        series.put(k // stride, pos[:, 0], pos[:, 1], ll[:, 0], ll[:, 1], msk,
-                                   extra={n: srow[:, kn] for kn, n in enumerate(smp_names)} if smp_names else None)
-                except BaseException:
-                    series.abort()
-                    raise
-                if k == Nt:
-                    z2XY[1], z2GC[1], zMSK[1] = pos, ll, msk
-                    for kn, n in enumerate(smp_names):
-                        zS[n][1] = srow[:, kn]
-            if lUse2DTime and jrec in ends:
-                sel = np.where(zLstModelRec == jrec)[0]
-                z2XY[1, sel] = pos[sel]
-                z2GC[1, sel] = ctx.cart2geo(pos[sel])
-                zMSK[1, sel] = msk[sel]
-                zTim[1, sel[stepped[sel]]] = int(itime + rdt)
-                for kn, n in enumerate(smp_names):
-                    zS[n][1, sel] = srow[sel, kn]
+            if comm.root:
+                out.store(jrecN, *rec, srow)
         clk.add("fetch_and_store_outputs_s", t_f)
         if due[ib]:
             t_r = clk.now()
-            rebalance()
+            part.rebalance(ctx, ingest)
             clk.add("rebalance_s", t_r)
-            upload(*batches[ib + 1])
+            ingest.upload(*batches[ib + 1])
             if tplan is not None:
                 # the next batch's first partner was uploaded over the box of this rank's former buoys: once more, over the new one
-                upload_recs(batches[ib + 1][0], [jt0 + m - 1])
+                ingest.upload_recs(batches[ib + 1][0], [jt0 + m - 1])
     ctx.sync()
     if bcast is not None:
         bcast.close()
     clk.add("record_loop_s", t_loop)
+    record_bytes = 3 * mesh.Nj * mesh.Ni * ctx.field_dtype.itemsize
     if not a.full_records:
         # what box ingest bought, per rank (every rank prints its own line)
         print(' *** rank %d read and uploaded %.1f MB of the %.1f MB of its %d records (box ingest: the rows x columns its own buoys can touch)'
-              % (comm.rank, band["bytes"] / 1e6, 3.0 * Nj * Ni * esz * Nt / 1e6, Nt), flush=True)
+              % (comm.rank, ingest.bytes / 1e6, record_bytes * Nt / 1e6, Nt), flush=True)
     tk = clk.now()
     records.close()
     launches = ctx.launch_stats()
     state = trk.state()
-    vJIt_end, alive_end = to_caller_order(comm.gather_rows(state["vJIt"], nP)), to_caller_order(comm.gather_rows(state["iAlive"], nP))
+    vJIt_end, alive_end = part.gather(state["vJIt"]), part.gather(state["iAlive"])
     trk.close()
     if not comm.root:
         comm.close()
-        return {"rank": comm.rank, "nP": nP, "range": (lo, hi), "upload_bytes": band["bytes"]}
+        return {"rank": comm.rank, "nP": nP, "range": part.range, "upload_bytes": ingest.bytes}
 
     # ---- outputs (:509-571)
-    outs = []
-    if not lUse2DTime:
-        series.close()                                       # every record is in the file already
-        outs.append(cf_series)
-        zTim = []
-        zvt = np.array([vTime[0], vTime[Nt]])
-    else:
-        zvt = np.array([np.mean(zTim[0, :]), np.mean(zTim[1, :])])
-    cf_nc_out = './nc/' + corgn + '_tracking12_' + SeedBatch + cdtbin + '_' + date_tag(zvt[0]) + '_' + date_tag(zvt[1]) + csfkm + '.nc'
-    ncio.ncSaveCloudBuoys(cf_nc_out, zvt, IDs, z2XY[:, :, 0], z2XY[:, :, 1], z2GC[:, :, 0], z2GC[:, :, 1], mask=zMSK, xtime=zTim,
-                          corigin=corgn, extra={n: (zS[n], smp_attrs[n]) for n in smp_names} if smp_names else None)
-    outs.append(cf_nc_out)
-
-    if a.deform:
-        cf_dfm = ('./npz/' + corgn + '_deformation_' + SeedBatch + cdtbin + '_' + date_tag(vTime[0]) + '_' + date_tag(vTime[Nt]) + csfkm
-                  + '.npz')
-        _savez_deflate(cf_dfm, meshes=np.array(a.deform, dtype=np.float64).reshape(-1, 2),
-                       windows=np.array(dfm_win, dtype=np.int64).reshape(-1, 2),
-                       time0=np.array([vTime[w[0] - kstrt] for w in dfm_win], dtype=np.int64),
-                       time1=np.array([vTime[w[1] - kstrt + 1] for w in dfm_win], dtype=np.int64), **dfm_out,
-                       **({"grid": np.array(dfm_grid, dtype=np.float64), "grid_at": np.array(a.deform_grid[1])} if dfm_grid else {}))
-        outs.append(cf_dfm)
-
+    outs, zvt = out.write()
+    if dfm:
+        outs.append(out_file(run, 'deformation', out.vTime[0], out.vTime[Nt], ext='npz'))
+        dfm.write(outs[-1], out.vTime, kstrt)
     if a.plot > 0:
         try:
             import mojito as mjt          # noqa: F401  optional, as in the reference (:20,587-600)
@@ -956,6 +1111,6 @@ def main(argv=None):
     clk.add("write_outputs_s", tk)
     clk.t["total_s"] = clk.now() - clk.t0
     comm.close()
-    return {"files": outs, "nP": nP, "IDs": IDs, "vJIt": vJIt_end, "iAlive": alive_end, "Nt": Nt, "kstrt": kstrt,
-            "timing": dict(clk.t), "launches": launches, "upload_bytes": band["bytes"], "record_bytes": 3 * Nj * Ni * esz,
-            "rebalances": part.get("rebalances", 0), "migrated": part.get("migrated", 0)}
+    return {"files": outs, "nP": nP, "IDs": seeds.IDs, "vJIt": vJIt_end, "iAlive": alive_end, "Nt": Nt, "kstrt": kstrt,
+            "timing": dict(clk.t), "launches": launches, "upload_bytes": ingest.bytes, "record_bytes": record_bytes,
+            "rebalances": part.rebalances, "migrated": part.migrated}
