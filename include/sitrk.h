@@ -587,6 +587,63 @@ int sitrk_mesh_raster(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km, 
 int sitrk_raster_kernel_ms(sitrk_t *h, float *cells_ms, float *gather_ms);
 int sitrk_raster_stats(sitrk_t *h, int64_t *claims);
 
+/* ---- coarse-grained deformation of buoy cells: the spatial scaling curve -------------
+ * An EXTRA the reference does not have: the cells' velocity gradients box-averaged on a pyramid over a regular grid, and per
+ * level the area-weighted moments of the total deformation of the boxes -- one point of the curve <tot^q>(L) per level, L =
+ * d*2^l, from one mesh and one call (the spatial scaling analysis of Marsan et al. 2004).  No parity claim is
+ * made against any other code; the contract below is this library's own.  Everything in fp64, one rounded operation per symbol
+ * in the order written, no fused multiply-add.  The level sums use only + - * /, so every bit of `boxes` is pinned; the one
+ * unpinned operation is the device's sqrt, in the moments table.
+ * THE GRID is (y0_km, x0_km, d_km, ny, nx) as for sitrk_raster_cells, and 1 <= nlev <= SITRK_COARSE_MAXLEV.  Level l has
+ *     ny_l = (ny + 2^l - 1) >> l  by  nx_l = (nx + 2^l - 1) >> l  boxes of side L_l = d*2^l (an exact scaling);
+ * box (J,I) of level l+1 has the children (2J,2I), (2J,2I+1), (2J+1,2I), (2J+1,2I+1) of level l; the levels above the one that
+ * reaches 1 x 1 stay 1 x 1.  SITRK_EINVAL before any device work unless y0, x0, d are finite, d > 0, ny, nx >= 1, ny*nx <= 2^24
+ * (the pyramid holds 48 bytes per box), nlev is in range and fmin is finite and >= 0.
+ * A CELL'S TERMS: with a = area0 and u_x, u_y, v_x, v_y of the sitrk_deform_cells contract, the five terms a, a*u_x, a*u_y,
+ * a*v_x, a*v_y.
+ * WHERE A CELL GOES: by its t0 centroid,
+ *     nv = 4:  cy = 0.25*((y_0 + y_1) + (y_2 + y_3))        nv = 3:  cy = ((y_0 + y_1) + y_2)/3.0         cx likewise
+ *     fy = (cy - y0)/d ; fx = (cx - x0)/d
+ * The cell is IN THE GRID iff fy >= 0 && fy < ny && fx >= 0 && fx < nx, compared in fp64, and its pixel is (floor(fy),
+ * floor(fx)): a centroid exactly on a pixel line belongs to the upper pixel.  A cell goes whole to that pixel.
+ * LEVEL 0: each pixel has six values n, A, AUx, AUy, AVx, AVy.  n = the number of contributing cells of the pixel, as fp64.
+ * Each of the five sums starts at +0.0 and the terms of the pixel's contributing cells are added IN ASCENDING CELL INDEX,
+ * S = S + t.
+ * LEVEL l+1: each of the six values is (c00 + c01) + (c10 + c11) of the children, a child beyond the edge counting as +0.0.
+ * No floating-point atomics anywhere: two calls return the same bits, and a permutation of the cell rows returns the bits of
+ * this contract evaluated on the permuted rows.
+ * THE TABLE is (nlev, SITRK_COARSE_NCOLS) fp64, per level: [0] the number of boxes with n >= 1; [1] the number of FILLED boxes,
+ * those with n >= 1, A > 0 and A >= fmin*(L_l*L_l); then sums over the filled boxes only: [2] A, [3] A*div, [4] A*shr,
+ * [5] A*tot, [6] (A*tot)*tot, [7] ((A*tot)*tot)*tot, where per filled box
+ *     UX = AUx/A ; UY = AUy/A ; VX = AVx/A ; VY = AVy/A
+ *     div = UX + VY ; e1 = UX - VY ; e2 = UY + VX ; shr = sqrt(e1*e1 + e2*e2) ; tot = sqrt(div*div + shr*shr)
+ * The order of these eight sums is the implementation's, fixed by the level's size alone (columns 0 and 1 are exact).
+ * OUTPUTS: boxes (may be NULL) is the whole pyramid, level-major, each level (6, ny_l, nx_l) fp64; table as above; *nin and
+ * *nout (may be NULL) = the contributing cells inside and outside the grid.
+ *
+ * sitrk_coarse_cells: host arrays with the argument rules of sitrk_deform_cells -- yx0, yx1 (nP,2), mask0 / mask1 (nP) or NULL,
+ * cells (nC,nv), T finite and > 0 -- and use (nC) int8 (NULL: all).  A cell CONTRIBUTES iff its use byte is not 0 and it is valid
+ * in the sense of sitrk_deform_cells.  A vertex index outside [0, nP) is SITRK_EINDEX with the number of offending cells in
+ * sitrk_last_error (outputs unspecified); such an index is never dereferenced and the handle stays usable.  nC == 0 is valid:
+ * zeros.  Synchronous on the handle's stream.  Uses the context's transient scratch only: the grid, buoys, records and meshes of
+ * a tracker on the same handle are left as they were.
+ * sitrk_mesh_coarse is valid wherever sitrk_mesh_deform(mesh, jrec1, ...) is, and runs the same pass over the buoys and the same
+ * cell kernel; the statuses stay on the device.  The cells of status 1 contribute; their t0 geometry is the mesh's stored t0
+ * positions, T that of sitrk_mesh_deform.  The result is that of sitrk_coarse_cells on those positions, the mesh's cells and
+ * use = (status == 1).  An empty mesh gives zeros.  The errors are those of sitrk_mesh_deform plus the grid's.  Only the table
+ * (64 bytes per level) and, when asked for, the pyramid come down.
+ * sitrk_coarse_kernel_ms: GPU time [ms] of the phases of the last of the two calls on this handle, from HIP events -- the cells'
+ * terms and keys, the sort, level 0, the levels above it, the table; any pointer may be NULL, SITRK_EINVAL before any such
+ * call. */
+#define SITRK_COARSE_MAXLEV 16
+#define SITRK_COARSE_NCOLS 8
+int sitrk_coarse_cells(sitrk_t *h, int64_t nP, const double *yx0, const double *yx1, const int8_t *mask0, const int8_t *mask1,
+                       int64_t nC, int nv, const int32_t *cells, const int8_t *use, double T, double y0_km, double x0_km,
+                       double d_km, int ny, int nx, int nlev, double fmin, double *boxes, double *table, int64_t *nin, int64_t *nout);
+int sitrk_mesh_coarse(sitrk_t *h, int mesh, int jrec1, double y0_km, double x0_km, double d_km, int ny, int nx, int nlev,
+                      double fmin, double *boxes, double *table, int64_t *nin, int64_t *nout);
+int sitrk_coarse_kernel_ms(sitrk_t *h, float *terms_ms, float *sort_ms, float *level0_ms, float *pyramid_ms, float *table_ms);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

@@ -17,5 +17,6 @@ from .deformation import DeformCells, lattice_cells                          # n
 from .quadmesh import Tri2Quad                                                # noqa: F401
 from .delaunay import DelaunayTris                                           # noqa: F401
 from .raster import RasterCells, raster_grid                                  # noqa: F401
+from .coarse import CoarseCells, scaling_exponents                            # noqa: F401
 from .coast import DistToCoast, MaskCoastal                                  # noqa: F401
 from . import synthetic                                                      # noqa: F401

@@ -23,6 +23,10 @@ _SLOT_FIELDS = {"u": 0, "u_ice": 0, "v": 1, "v_ice": 1, "siconc": 2, "sic": 2, 0
 FillValue = -9999.0
 MESH_MAX = 8                                 # SITRK_MESH_MAX
 MESH_NSTATS = 10                             # SITRK_MESH_NSTATS, in this order:
+COARSE_MAXLEV = 16                           # SITRK_COARSE_MAXLEV
+COARSE_NCOLS = 8                             # SITRK_COARSE_NCOLS, in this order:
+COARSE_COLS = ("nboxes", "nfilled", "area", "area_div", "area_shr", "area_tot", "area_tot2", "area_tot3")
+COARSE_VALUES = ("n", "A", "AUx", "AUy", "AVx", "AVy")     # the six values of a box
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -96,6 +100,10 @@ _SIGNATURES = {
     "sitrk_mesh_raster": (_int, [_vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_raster_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 2),
     "sitrk_raster_stats": (_int, [_vp, C.POINTER(_i64)]),
+    "sitrk_coarse_cells": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _int, _int, _int, _dbl,
+                                  _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_mesh_coarse": (_int, [_vp, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _dbl, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_coarse_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 5),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -831,6 +839,67 @@ class Context:
         a = _i64(0)
         self._chk(self._L.sitrk_raster_stats(self._h, C.byref(a)))
         return a.value
+
+    # -- coarse-grained deformation (sitrk_coarse_*)
+    @staticmethod
+    def coarse_level_shapes(ny, nx, nlev):
+        """[(ny_l, nx_l)] of the levels 0 .. nlev-1 of the pyramid over an ny x nx grid"""
+        return [((ny + (1 << l) - 1) >> l, (nx + (1 << l) - 1) >> l) for l in range(nlev)]
+
+    def _coarse_out(self, g, nlev, boxes):
+        nlev = int(nlev)
+        shapes = self.coarse_level_shapes(max(g[3], 0), max(g[4], 0), min(max(nlev, 0), COARSE_MAXLEV))
+        pyr = np.empty(6 * sum(a * b for a, b in shapes), dtype=np.float64) if boxes else None
+        return nlev, shapes, pyr, np.zeros((len(shapes), COARSE_NCOLS), dtype=np.float64)
+
+    @staticmethod
+    def _coarse_result(shapes, pyr, table, nin, nout):
+        levels = None
+        if pyr is not None:
+            levels, o = [], 0
+            for a, b in shapes:
+                levels.append(pyr[o:o + 6 * a * b].reshape(6, a, b))
+                o += 6 * a * b
+        return {"table": table, "nin": nin.value, "nout": nout.value, "levels": levels}
+
+    def coarse_cells(self, yx0, yx1, cells, T, grid, nlev, fmin=0.5, mask0=None, mask1=None, use=None, boxes=False):
+        """sitrk_coarse_cells: the cells (nC, 3|4) of indices into the points yx0, yx1 (nP,2) km, T seconds apart, coarse-grained
+        on the pyramid of nlev levels over the grid (y0_km, x0_km, d_km, ny, nx).  A dict with table (nlev, 8) under the names
+        COARSE_COLS, nin, nout and levels: None, or with boxes=True per level the (6, ny_l, nx_l) values COARSE_VALUES.  mask0 /
+        mask1 (nP): 0 = invalid vertex; use (nC): 0 = the cell does not contribute."""
+        g = self._grid_arg(grid, "coarse_cells")
+        yx0 = as_c(yx0, np.float64)
+        nP = yx0.shape[0]
+        yx0 = as_c(yx0, np.float64, (nP, 2), "yx0")
+        yx1 = as_c(yx1, np.float64, (nP, 2), "yx1")
+        m0 = None if mask0 is None else as_c(np.asarray(mask0) != 0, np.int8, (nP,), "mask0")
+        m1 = None if mask1 is None else as_c(np.asarray(mask1) != 0, np.int8, (nP,), "mask1")
+        c = self._deform_cells_arg(cells, "coarse_cells")
+        nC, nv = c.shape
+        u = None if use is None else as_c(np.asarray(use) != 0, np.int8, (nC,), "use")
+        nlev, shapes, pyr, table = self._coarse_out(g, nlev, boxes)
+        nin, nout = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_coarse_cells(self._h, nP, _ptr(yx0), _ptr(yx1), _ptr(m0), _ptr(m1), nC, nv, _ptr(c), _ptr(u), float(T),
+                                             *g, nlev, float(fmin), _ptr(pyr), _ptr(table), C.byref(nin), C.byref(nout)))
+        return self._coarse_result(shapes, pyr, table, nin, nout)
+
+    def mesh_coarse(self, mesh, jrec1, grid, nlev, fmin=0.5, boxes=False):
+        """sitrk_mesh_coarse, right after the step of jrec1: the status-1 cells of the mesh in slot `mesh` coarse-grained like
+        coarse_cells(), at their t0 positions; the same dict.  Only the table -- and with boxes=True the pyramid -- comes back
+        from the device."""
+        g = self._grid_arg(grid, "mesh_coarse")
+        nlev, shapes, pyr, table = self._coarse_out(g, nlev, boxes)
+        nin, nout = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_mesh_coarse(self._h, int(mesh), int(jrec1), *g, nlev, float(fmin), _ptr(pyr), _ptr(table),
+                                            C.byref(nin), C.byref(nout)))
+        return self._coarse_result(shapes, pyr, table, nin, nout)
+
+    def coarse_kernel_ms(self):
+        """(terms_ms, sort_ms, level0_ms, pyramid_ms, table_ms): GPU time of the phases of the last coarse-graining call
+        (sitrk_coarse_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(5)]
+        self._chk(self._L.sitrk_coarse_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

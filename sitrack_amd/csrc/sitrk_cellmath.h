@@ -1,7 +1,7 @@
 // sitrk_cellmath.h -- the per-cell arithmetic of two contracts of include/sitrk.h as __device__ functions, so that every kernel
 // that evaluates them runs the same statements: the deformation rates of sitrk_deform_cells and the shoelace
-// sum, acceptance tests and score of sitrk_tri2quad.  Included by sitrk_deform.hip, sitrk_quadmesh.hip and
-// sitrk_mesh.hip only; one rounded fp64 operation per symbol, no fused multiply-add.
+// sum, acceptance tests and score of sitrk_tri2quad.  Included by sitrk_deform.hip, sitrk_quadmesh.hip,
+// sitrk_mesh.hip, sitrk_raster.hip and sitrk_coarse.hip only; one rounded fp64 operation per symbol, no fused multiply-add.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +50,39 @@ __device__ __forceinline__ bool deform_rates(const pt (&a)[NV], const pt (&b)[NV
     r[2] = vx - uy;
     r[3] = 0.5 * fabs(A2);
     r[4] = 0.5 * fabs(B2);
+    return ok;
+}
+
+// The velocity gradients of the same contract, for the box averages of sitrk_coarse_* (DESIGN.md 3.16): the statements of
+// deform_rates up to u_x, u_y, v_x, v_y, in the same order, so that both give the same bits for them.  g = a, a*u_x, a*u_y, a*v_x,
+// a*v_y with a = area0; false: the cell is invalid in the sense of deform_rates and g is not to be used.
+template <int NV>
+__device__ __forceinline__ bool deform_gradient_terms(const pt (&a)[NV], const pt (&b)[NV], double T, double (&g)[5])
+{
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < NV; k++) ok = ok && finite64(a[k].y) && finite64(a[k].x) && finite64(b[k].y) && finite64(b[k].x);
+
+    double dx[NV], dy[NV], u[NV], v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        dx[k] = a[k].x - a[0].x; dy[k] = a[k].y - a[0].y;
+        u[k] = (b[k].x - a[k].x) / T; v[k] = (b[k].y - a[k].y) / T;
+    }
+    double A2 = 0.0, Suy = 0.0, Sux = 0.0, Svy = 0.0, Svx = 0.0;
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        const int q = (k + 1) % NV;
+        A2 = A2 + (dx[k] * dy[q] - dx[q] * dy[k]);
+        const double us = u[q] + u[k], vs = v[q] + v[k], ddy = dy[q] - dy[k], ddx = dx[q] - dx[k];
+        Suy = Suy + us * ddy; Sux = Sux + us * ddx;
+        Svy = Svy + vs * ddy; Svx = Svx + vs * ddx;
+    }
+    ok = ok && A2 != 0.0 && finite64(A2);
+    const double ux = Suy / A2, uy = -(Sux / A2), vx = Svy / A2, vy = -(Svx / A2);
+    const double ar = 0.5 * fabs(A2);
+    g[0] = ar;
+    g[1] = ar * ux; g[2] = ar * uy; g[3] = ar * vx; g[4] = ar * vy;
     return ok;
 }
 

@@ -262,6 +262,11 @@ struct sitrk_ctx {
     bool raster_counted = false;
     unsigned long long raster_claims = 0;
 
+    // coarse-grained deformation (sitrk_coarse.hip): events around the five phases of the last call -- terms, sort, level 0,
+    // pyramid, table
+    hipEvent_t coarse_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool coarse_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -291,7 +296,7 @@ void mesh_release(sitrk_ctx *h, bool destroy);
 // ... and the body of sitrk_mesh_deform behind its argument checks (mesh_deform_check), everything left in the transient scratch:
 // the pass over the buoys, the cell kernel and, when asked for, the final sum are queued on the compute stream and the pointers
 // of MeshDeformDev say where their results lie.  `extra` bytes of the same scratch layout come with them for the caller's own
-// buffers (sitrk_raster.hip).  An empty mesh queues nothing and returns null pointers next to `extra`.
+// buffers (sitrk_raster.hip, sitrk_coarse.hip).  An empty mesh queues nothing and returns null pointers next to `extra`.
 struct MeshDeformDev {
     int64_t nQ = 0;
     const int32_t *quads = nullptr;     // (nQ,4) the mesh's own
@@ -307,6 +312,8 @@ int mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want
                      MeshDeformDev *r);
 // sitrk_raster.hip: destroys the timing events (sitrk_destroy)
 void raster_release(sitrk_ctx *h);
+// sitrk_coarse.hip: destroys the timing events (sitrk_destroy)
+void coarse_release(sitrk_ctx *h);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
 void quadmesh_release(sitrk_ctx *h);
 // sitrk_delaunay.hip: destroys the timing events (sitrk_destroy)

@@ -28,7 +28,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib, ncio, raster
+from . import _lib, coarse, ncio, raster
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
@@ -110,9 +110,17 @@ def parse_args(argv=None):
                          'none).  Per pixel the index of the cell it lies in (-1: none), stored as m<k>_w<k>_owner next to `grid` = (y0, '
                          'x0, d, ny, nx) and `grid_at`; a map is m<k>_w<k>_div[owner] where owner >= 0.  @t0 (default): the cells where '
                          'they were at the window\'s start, @t1: where they are at its end (status 1 only).  At most 2^28 pixels')
+    ap.add_argument('--deform-coarse', type=_deform_coarse_arg, default=None,
+                    help='with --deform and --deform-grid: NLEV or NLEV@FMIN: every mesh is also coarse-grained, after each window, on '
+                         'NLEV levels of boxes of side D_KM*2^l over that grid (extra; default none): the area-weighted velocity '
+                         'gradients of its status-1 cells box-averaged on the GPU, and per level the sums of A, A*div, A*shr, A*tot^q '
+                         '(q = 1, 2, 3) over the boxes filled to at least FMIN (default 0.5) of their area, stored as m<k>_w<k>_coarse '
+                         '(NLEV, 8) next to `coarse` = (nlev, fmin); the scaling exponents are logged.  At most 2^24 pixels')
     a = ap.parse_args(argv)
     if a.deform_grid is not None and not a.deform:
         ap.error("--deform-grid: there is no mesh to rasterise without --deform")
+    if a.deform_coarse is not None and a.deform_grid is None:
+        ap.error("--deform-coarse: it works on the grid of --deform-grid; give that flag too")
     return a
 
 
@@ -162,6 +170,14 @@ def _deform_grid_arg(text):
     if not (np.isfinite(d) and d > 0.):
         raise err("--deform-grid: D_KM must be finite and > 0, got %r" % text)
     return (d, tok[1] if len(tok) == 2 else "t0")
+
+
+def _deform_coarse_arg(text):
+    """--deform-coarse: (nlev, fmin) of NLEV[@FMIN], NLEV in 1..16, FMIN finite >= 0 (default 0.5)"""
+    try:
+        return coarse.coarse_arg(text, '--deform-coarse')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def deform_grid(xYf, xXf, d_km):
@@ -500,6 +516,9 @@ def read_mesh(a, ctx):
         xYv, xXv, xYu, xXu = xYf, xXf, xYf, xXf     # never read by the cell-mean rule
     (Nj, Ni) = np.shape(imaskt)
     dfm_grid = deform_grid(xYf, xXf, a.deform_grid[0]) if a.deform_grid else None
+    if a.deform_coarse and dfm_grid[3] * dfm_grid[4] > coarse.MAX_PIXELS:
+        raise ValueError('--deform-coarse: %g km over the model grid is %d x %d pixels, more than 2^24: take a coarser --deform-grid'
+                         % (dfm_grid[2], dfm_grid[3], dfm_grid[4]))
     return SimpleNamespace(imaskt=imaskt, xlatT=xlatT, xlonT=xlonT, xYf=xYf, xXf=xXf, xYu=xYu, xXu=xXu, xYv=xYv, xXv=xXv,
                            xResKM=xResKM, Nj=Nj, Ni=Ni, dfm_grid=dfm_grid)
 
@@ -795,8 +814,8 @@ class DeformSeries:
       win      the windows [(jrec0, jrec1)];  first / last: model record -> the window it opens / closes
       out      what is kept of every (mesh, window) for the file"""
 
-    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk):
-        self.specs, self.grid, self.grid_at = specs, grid, grid_at
+    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None):
+        self.specs, self.grid, self.grid_at, self.coarse = specs, grid, grid_at, coarse
         self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
         self.win = deform_windows(Nt, kstrt, window)
         self.first, self.last = {w[0]: k for k, w in enumerate(self.win)}, {w[1]: k for k, w in enumerate(self.win)}
@@ -842,6 +861,12 @@ class DeformSeries:
                         '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
             if self.grid is not None:                    # the map is out[:, owner] on the host: no second copy of the rates
                 self.out[pre + "owner"] = self.trk.mesh_raster(jrec1, self.grid, slot=km, at=self.grid_at, fields=False)["owner"]
+            if self.coarse is not None:                  # the scaling curve of this mesh and window: 64 bytes per level come down
+                tab = self.trk.mesh_coarse(jrec1, self.grid, self.coarse[0], fmin=self.coarse[1], slot=km)["table"]
+                self.out[pre + "coarse"] = tab
+                beta = coarse.scaling_exponents(tab, self.grid[2])["beta"]
+                self.say(' *** --deform-coarse window %d mesh %d: %d levels from %g km, filled boxes %s, beta(1..3) = %s'
+                         % (kw, km, len(tab), self.grid[2], '/'.join('%d' % n for n in tab[:, 1]), ', '.join('%.4f' % b for b in beta)))
         self.clk.add("deform_s", t_d)
 
     def write(self, fname, vTime, kstrt):
@@ -850,7 +875,8 @@ class DeformSeries:
                        windows=np.array(self.win, dtype=np.int64).reshape(-1, 2),
                        time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64),
                        time1=np.array([vTime[w[1] - kstrt + 1] for w in self.win], dtype=np.int64), **self.out,
-                       **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}))
+                       **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}),
+                       **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}))
 
 
 class Outputs:
@@ -1001,7 +1027,7 @@ def main(argv=None):
     bcast = record_broadcaster(a, comm, ctx, tphase)
     ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
-                       say, clk) if a.deform else None
+                       say, clk, coarse=a.deform_coarse) if a.deform else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no

@@ -328,6 +328,20 @@ class IceTracker:
             res.update(zip(("div", "shr", "vor", "area0", "area1"), r["fields"]))
         return res
 
+    def mesh_coarse(self, jrec1, grid, nlev, fmin=0.5, slot=0, boxes=False):
+        """Right after the step of `jrec1`: the status-1 cells of mesh `slot` coarse-grained on a pyramid of `nlev` levels over the
+        grid (y0_km, x0_km, d_km, ny, nx) of sit.raster_grid (an extra the reference does not have; sitrk_mesh_coarse): their
+        area-weighted velocity gradients summed into the pixel of their t0 centroid and up the levels of side d*2^l.  A dict with
+        table (nlev, 8) under the names _lib.COARSE_COLS -- per level the boxes with a cell, the filled boxes (area >= fmin of
+        the box) and over those the sums of A, A*div, A*shr, A*tot^q for q = 1, 2, 3 --, nin and nout (the cells inside and outside
+        the grid) and levels: None, or with boxes=True per level a dict of (ny_l, nx_l) arrays n, A, AUx, AUy, AVx, AVy.
+        sit.scaling_exponents(table, d_km) reads the exponents off it.  The per-cell results stay on the device."""
+        from .coarse import check_levels, name_levels
+        from .raster import check_grid
+        cerr = 'ERROR [IceTracker.mesh_coarse()]: '
+        g = check_levels(check_grid(grid, cerr), nlev, fmin, cerr)
+        return name_levels(self.ctx.mesh_coarse(slot, jrec1, g, int(nlev), fmin=float(fmin), boxes=boxes))
+
     def mesh_free(self, slot=0):
         self.ctx.mesh_free(slot)
 

@@ -2,7 +2,7 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM] [-o OUT.npz]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]]] [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
 positions of record K0 (Delaunay; needs scipy).  Records default to the first and the last; the elapsed time comes from
@@ -11,7 +11,10 @@ with `_deform.npz` for its extension) holds div, shr, vor, tot [1/s], area0, are
 time0, time1.  `--grid D_KM` also rasterises the cells at their K0 positions onto square pixels of D_KM km over the bounding
 box of the valid points (sitrk_raster_cells): OUT then holds `owner` (ny, nx) int32, per pixel the row of the
 valid cell its centre lies in (the lowest on a shared edge, -1 for none), and `grid` = (y0, x0, d, ny, nx); a map is
-`div[owner]` where owner >= 0.
+`div[owner]` where owner >= 0.  `--coarse NLEV[@FMIN]` with it coarse-grains the valid cells on NLEV levels of boxes of side
+D_KM*2^l over that grid (sitrk_coarse_cells): OUT then holds `coarse_table` (NLEV, 8) -- per level the boxes
+with a cell, the boxes filled to FMIN (default 0.5) of their area and over those the sums of A, A*div, A*shr, A*tot^q, q = 1,
+2, 3 --, `coarse` = (nlev, fmin) and `beta` (3,), the scaling exponents sit.scaling_exponents reads off the table.
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -68,8 +71,19 @@ def main(argv=None):
     ap.add_argument('-o', '--fout', default=None, help='output file (default: <input>_deform.npz)')
     ap.add_argument('--grid', type=float, default=None, metavar='D_KM',
                     help='also rasterise the valid cells at their first-record positions onto pixels of D_KM km (`owner`, `grid` in the output)')
+    ap.add_argument('--coarse', default=None, metavar='NLEV[@FMIN]',
+                    help='with --grid: also coarse-grain the valid cells on NLEV levels over that grid (`coarse_table`, `coarse`, `beta` in the output)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
+    coarse = None
+    if a.coarse is not None:
+        from sitrack_amd.coarse import coarse_arg
+        if a.grid is None:
+            sys.exit('ERROR: --coarse: it works on the grid of --grid; give that flag too')
+        try:
+            coarse = coarse_arg(a.coarse)
+        except ValueError as e:
+            sys.exit('ERROR: %s' % e)
     if a.grid is not None and not (np.isfinite(a.grid) and a.grid > 0.):
         sys.exit('ERROR: --grid: D_KM must be finite and > 0, got %r' % a.grid)
     ncio.chck4f(a.fin)
@@ -119,6 +133,12 @@ def main(argv=None):
                 sys.exit('ERROR: --grid: %g km over the points is %d x %d pixels, more than 2^28' % (a.grid, grid[3], grid[4]))
             r['owner'] = sit.RasterCells(yx0, cols, grid, draw=r['valid'], ctx=ctx)
             r['grid'] = np.array(grid, dtype=np.float64)
+            if coarse is not None:
+                if grid[3] * grid[4] > 2 ** 24:
+                    sys.exit('ERROR: --coarse: %g km over the points is %d x %d pixels, more than 2^24' % (a.grid, grid[3], grid[4]))
+                rc = sit.CoarseCells(yx0, yx1, cols, T, grid, coarse[0], fmin=coarse[1], mask0=ok0, mask1=ok1, ctx=ctx)
+                r['coarse_table'], r['coarse'] = rc['table'], np.array(coarse, dtype=np.float64)
+                r['beta'] = sit.scaling_exponents(rc['table'], a.grid)['beta']
     finally:
         ctx.close()
     fout = a.fout or os.path.splitext(a.fin)[0] + '_deform.npz'
@@ -127,6 +147,9 @@ def main(argv=None):
     if a.grid is not None:
         print(' *** --grid %g km: %d x %d pixels, %d of them in a valid cell' % (a.grid, r['owner'].shape[0], r['owner'].shape[1],
                                                                                int((r['owner'] >= 0).sum())))
+    if coarse is not None:
+        print(' *** --coarse %d levels, fmin %g: filled boxes %s, beta(1..3) = %s'
+              % (coarse[0], coarse[1], '/'.join('%d' % n for n in r['coarse_table'][:, 1]), ', '.join('%.4f' % b for b in r['beta'])))
     return 0
 
 
