@@ -644,6 +644,54 @@ int sitrk_mesh_coarse(sitrk_t *h, int mesh, int jrec1, double y0_km, double x0_k
                       double fmin, double *boxes, double *table, int64_t *nin, int64_t *nout);
 int sitrk_coarse_kernel_ms(sitrk_t *h, float *terms_ms, float *sort_ms, float *level0_ms, float *pyramid_ms, float *table_ms);
 
+/* ---- features of a map: connected components of a mask on a regular grid ---------------
+ * An EXTRA the reference does not have: the connected bands of pixels of a raster that pass a test -- the leads, ridges and
+ * linear kinematic features of a deformation map -- labelled on the device, and one row of integers per feature brought down
+ * instead of the map.  No parity claim is made against any other code; the contract below is this library's
+ * own.  Everything is integer, so nothing is unpinned.
+ * THE RASTER is (ny, nx) with 1 <= ny, nx <= 32768 and ny*nx <= 2^28 (the side keeps the sum of j*j below 2^63); the linear
+ * index of pixel (j,i) is p = j*nx + i.  THE MASK active (ny,nx) int8: a pixel is active iff its byte is not 0.
+ * CONNECTIVITY conn is 4 (the neighbours across a pixel's four sides) or 8 (those and the four across its corners); anything
+ * else is SITRK_EINVAL.  A component is a maximal set of active pixels joined by chains of neighbours.
+ * THE LABELS: labels (ny,nx) int32, may be NULL: -1 for a pixel that is not active, else THE LOWEST LINEAR INDEX OF THE PIXEL'S
+ * COMPONENT.  That is canonical: it does not depend on the tiling, the launch geometry or which lane gets where first, and two
+ * calls return the same bits.
+ * THE TABLE: table (maxfeat, SITRK_FEAT_NCOLS) int64, one row per component with npix >= min_pix (min_pix >= 1), the rows in
+ * ascending label; only the first maxfeat of them are written (maxfeat >= 0; table may be NULL iff maxfeat == 0) and the rest of
+ * `table` is left as it was.  Columns: [0] the label; [1] npix; [2] jmin, [3] jmax, [4] imin, [5] imax; the sums over the
+ * component's pixels [6] j, [7] i, [8] j*j, [9] i*i, [10] j*i; [11] the perimeter = the number of sides of the component's
+ * pixels whose other pixel is not active, the raster's rim counting as not active (an active pixel across a side belongs to the
+ * same component for conn 4 and 8 alike).
+ * THE COUNTS, each may be NULL: *nfeat = the components with npix >= min_pix, which may exceed maxfeat -- that is how the caller
+ * learns that the table is truncated; *ncomp = all components; *nactive = the active pixels.
+ *
+ * sitrk_label_raster: a host mask.  Synchronous on the handle's stream.  Uses the context's transient scratch only: the grid,
+ * buoys, records and meshes of a tracker on the same handle are left as they were.  A mask of zeros is valid: every label -1,
+ * the counts 0.  SITRK_EINVAL before any device work for a raster, conn, min_pix or maxfeat out of range and missing pointers.
+ * sitrk_mesh_features is valid wherever sitrk_mesh_raster(mesh, jrec1, at_t1, grid, ...) is, and runs the same pass over the
+ * buoys, the same cell kernel and the same rasteriser; owner and rates stay on the device, where the mask is made, and only what
+ * was asked for comes down: with labels == NULL the rows of the table and the three counts.  Its result is DEFINED BY THE
+ * EXISTING CONTRACTS: that of sitrk_label_raster on the mask  owner >= 0 && test(out[:, owner]),  owner being what
+ * sitrk_mesh_raster returns and out what sitrk_mesh_deform returns for the same arguments.  THE TEST: `what` selects f -- 0: div,
+ * 1: shr, 2: vor -- and the pixel is active iff  sgn*f >= thr  with sgn +1 or -1, compared in fp64, a NaN never active.
+ * what == 3, the total deformation: active iff  div*div + shr*shr >= thr*thr  (one rounded operation per symbol, no fused
+ * multiply-add), which needs sgn == +1 and thr >= 0: no second square root, so the test adds nothing unpinned.  thr is finite,
+ * in the unit of out.  (shr itself ends in the device's sqrt: DESIGN.md 3.14.)  The errors are those of sitrk_mesh_raster plus
+ * the ones above, all raised before any device work.
+ * Should a union-find loop of the kernels ever reach its bound -- the number of pixels, which a chain of strictly falling
+ * indices cannot -- the call returns SITRK_EHIP with a text in sitrk_last_error instead of spinning; the outputs are unspecified.
+ * sitrk_features_kernel_ms: GPU time [ms] of the phases of the last of the two calls on this handle, from HIP events -- the mask
+ * (its kernel, or for sitrk_label_raster its upload), the labels (tiles, merge levels, flattening), the table (counts, scan,
+ * rows); any pointer may be NULL, SITRK_EINVAL before any such call. */
+#define SITRK_FEAT_NCOLS 12
+#define SITRK_LABEL_TILE 64        /* side of the tiles the labelling starts from; never changes a result */
+int sitrk_label_raster(sitrk_t *h, int ny, int nx, const int8_t *active, int conn, int64_t min_pix, int64_t maxfeat,
+                       int32_t *labels, int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive);
+int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny, int nx,
+                        int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat,
+                        int32_t *labels, int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive);
+int sitrk_features_kernel_ms(sitrk_t *h, float *mask_ms, float *label_ms, float *table_ms);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

@@ -27,6 +27,10 @@ COARSE_MAXLEV = 16                           # SITRK_COARSE_MAXLEV
 COARSE_NCOLS = 8                             # SITRK_COARSE_NCOLS, in this order:
 COARSE_COLS = ("nboxes", "nfilled", "area", "area_div", "area_shr", "area_tot", "area_tot2", "area_tot3")
 COARSE_VALUES = ("n", "A", "AUx", "AUy", "AVx", "AVy")     # the six values of a box
+FEAT_NCOLS = 12                              # SITRK_FEAT_NCOLS, in this order:
+FEAT_COLS = ("label", "npix", "jmin", "jmax", "imin", "imax", "sum_j", "sum_i", "sum_jj", "sum_ii", "sum_ji", "perimeter")
+FEAT_WHAT = {"div": 0, "shr": 1, "vor": 2, "tot": 3}       # `what` of sitrk_mesh_features
+LABEL_TILE = 64                              # SITRK_LABEL_TILE
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -104,6 +108,10 @@ _SIGNATURES = {
                                   _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_mesh_coarse": (_int, [_vp, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _dbl, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coarse_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 5),
+    "sitrk_label_raster": (_int, [_vp, _int, _int, _vp, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_mesh_features": (_int, [_vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _int, _dbl, _int, _i64, _i64, _vp, _vp,
+                                   C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_features_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -899,6 +907,55 @@ class Context:
         (sitrk_coarse_kernel_ms)"""
         v = [C.c_float(0) for _ in range(5)]
         self._chk(self._L.sitrk_coarse_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    # -- features of a map: connected components (sitrk_label_raster, sitrk_mesh_features)
+    @staticmethod
+    def _features_result(table, nfeat, ncomp, nactive, labels):
+        rows = min(nfeat.value, table.shape[0])
+        return {"table": table[:rows], "nfeat": nfeat.value, "ncomp": ncomp.value, "nactive": nactive.value, "labels": labels}
+
+    def label_raster(self, active, conn=8, min_pix=1, maxfeat=65536, labels=True):
+        """sitrk_label_raster: the connected components of the mask active (ny,nx) (a pixel is active iff its value is not 0) for
+        conn = 4 or 8 neighbours.  A dict with table (rows, 12) int64 under the names FEAT_COLS -- one row per component of at
+        least min_pix pixels, in ascending label, the first maxfeat of them --, nfeat (all such components: above maxfeat the
+        table is truncated), ncomp, nactive and labels: (ny,nx) int32, -1 or the lowest linear index of the pixel's component;
+        None with labels=False."""
+        a = np.asarray(active)
+        if a.ndim != 2:
+            raise ValueError("label_raster: active must be (ny, nx), got shape %s" % (a.shape,))
+        a = as_c(a != 0, np.int8)
+        ny, nx = a.shape
+        if not (ny < 2 ** 31 and nx < 2 ** 31):
+            raise ValueError("label_raster: ny and nx must fit int32, got %d, %d" % (ny, nx))
+        maxfeat = int(maxfeat)
+        table = np.zeros((max(maxfeat, 0), FEAT_NCOLS), dtype=np.int64)
+        lab = np.empty((ny, nx), dtype=np.int32) if labels else None
+        nfeat, ncomp, nactive = _i64(0), _i64(0), _i64(0)
+        self._chk(self._L.sitrk_label_raster(self._h, ny, nx, _ptr(a), int(conn), int(min_pix), maxfeat, _ptr(lab),
+                                             _ptr(table) if maxfeat > 0 else None, C.byref(nfeat), C.byref(ncomp), C.byref(nactive)))
+        return self._features_result(table, nfeat, ncomp, nactive, lab)
+
+    def mesh_features(self, mesh, jrec1, grid, what, thr, sgn=1, conn=8, min_pix=1, maxfeat=65536, at_t1=False, labels=False):
+        """sitrk_mesh_features, right after the step of jrec1: the mesh in slot `mesh` rasterised like mesh_raster(), the pixels
+        with an owner whose rate `what` (0 div, 1 shr, 2 vor, 3 tot, or those names) passes sgn*f >= thr (tot: div^2 + shr^2 >=
+        thr^2) labelled like label_raster(); the same dict.  Owner and rates stay on the device: only the table, the counts and,
+        with labels=True, the labels come back."""
+        g = self._grid_arg(grid, "mesh_features")
+        what = FEAT_WHAT.get(what, what)
+        maxfeat = int(maxfeat)
+        table = np.zeros((max(maxfeat, 0), FEAT_NCOLS), dtype=np.int64)
+        lab = np.empty((max(g[3], 0), max(g[4], 0)), dtype=np.int32) if labels else None
+        nfeat, ncomp, nactive = _i64(0), _i64(0), _i64(0)
+        self._chk(self._L.sitrk_mesh_features(self._h, int(mesh), int(jrec1), 1 if at_t1 else 0, *g, int(what), int(sgn), float(thr),
+                                              int(conn), int(min_pix), maxfeat, _ptr(lab), _ptr(table) if maxfeat > 0 else None,
+                                              C.byref(nfeat), C.byref(ncomp), C.byref(nactive)))
+        return self._features_result(table, nfeat, ncomp, nactive, lab)
+
+    def features_kernel_ms(self):
+        """(mask_ms, label_ms, table_ms): GPU time of the phases of the last labelling call (sitrk_features_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_features_kernel_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     # -- distance to the model coastline (sitrk_coast_*)

@@ -267,6 +267,10 @@ struct sitrk_ctx {
     hipEvent_t coarse_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool coarse_timed = false;
 
+    // labelled features (sitrk_label.hip): events around the three phases of the last call -- mask, labels, table
+    hipEvent_t label_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool label_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -312,6 +316,30 @@ int mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want
                      MeshDeformDev *r);
 // sitrk_raster.hip: destroys the timing events (sitrk_destroy)
 void raster_release(sitrk_ctx *h);
+// ... and the device side of its entry points, for a caller that goes on with the raster on the device (sitrk_label.hip): the grid's
+// checks, and the fill, cell and gather kernels queued on the compute stream.  cnt: three counters -- cells with a bad index, owned
+// pixels, and with the knob raster_count the centres inside a drawn cell.  out (5,nC) may be null when fields is
+struct RasterGrid {
+    double y0, x0, d;
+    int ny, nx;
+};
+struct RasterJob {
+    int64_t nC = 0, nP = 0;
+    int nv = 4;
+    bool block = false;                 // pts is (nC,nv) in cell order, no indices
+    const int32_t *cells = nullptr;
+    const pt *pts = nullptr;
+    const int8_t *flag = nullptr;
+    bool only_status1 = false;
+    const double *out = nullptr;
+    int32_t *owner = nullptr;
+    double *fields = nullptr;
+    unsigned long long *cnt = nullptr;
+};
+int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double d, int ny, int nx);
+int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g);
+// sitrk_label.hip: destroys the timing events (sitrk_destroy)
+void label_release(sitrk_ctx *h);
 // sitrk_coarse.hip: destroys the timing events (sitrk_destroy)
 void coarse_release(sitrk_ctx *h);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)

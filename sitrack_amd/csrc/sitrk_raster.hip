@@ -38,11 +38,6 @@ constexpr int64_t kRasMaxPixels = (int64_t)1 << 28;
 constexpr int32_t kRasNone = INT32_MAX;
 constexpr unsigned kRasGatherBlocks = 2048;        // 256 CUs x 8 resident workgroups
 
-struct RasterGrid {
-    double y0, x0, d;
-    int ny, nx;
-};
-
 __global__ __launch_bounds__(kRasThreads) void raster_fill_kernel(int64_t npix, int32_t *__restrict__ owner)
 {
     const int64_t p = (int64_t)blockIdx.x * kRasThreads + threadIdx.x;
@@ -198,22 +193,6 @@ __global__ __launch_bounds__(kRasThreads) void raster_gather_kernel(int64_t npix
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + kRasThreads - 1) / kRasThreads); }
 
-// the device side of both entry points.  cnt: three counters -- cells with a bad index, owned pixels, and with the knob raster_count
-// the centres inside a drawn cell.  out (5,nC) may be null when fields is
-struct RasterJob {
-    int64_t nC = 0, nP = 0;
-    int nv = 4;
-    bool block = false;                 // pts is (nC,nv) in cell order, no indices
-    const int32_t *cells = nullptr;
-    const pt *pts = nullptr;
-    const int8_t *flag = nullptr;
-    bool only_status1 = false;
-    const double *out = nullptr;
-    int32_t *owner = nullptr;
-    double *fields = nullptr;
-    unsigned long long *cnt = nullptr;
-};
-
 template <int NV, int SRC>
 void launch_cells(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
 {
@@ -224,6 +203,21 @@ void launch_cells(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
         hipLaunchKernelGGL((raster_cells_kernel<NV, SRC, false>), dim3(nblk(j.nC)), dim3(kRasThreads), 0, h->stream, j.nC, j.nP, j.cells, j.pts,
                            j.flag, j.only_status1, g, j.owner, j.cnt);
 }
+
+// the counters, behind the downloads of the results on the same stream; synchronises
+int raster_finish(sitrk_ctx *h, const unsigned long long *d_cnt, unsigned long long (&cnt)[3], int64_t *nowned)
+{
+    HIPCHK(download(h, cnt, d_cnt, 3));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->raster_count) {
+        h->raster_counted = true;
+        h->raster_claims = cnt[2];
+    }
+    if (nowned) *nowned = (int64_t)cnt[1];
+    return SITRK_OK;
+}
+
+}  // namespace
 
 int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
 {
@@ -254,19 +248,6 @@ int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
     return SITRK_OK;
 }
 
-// the counters, behind the downloads of the results on the same stream; synchronises
-int raster_finish(sitrk_ctx *h, const unsigned long long *d_cnt, unsigned long long (&cnt)[3], int64_t *nowned)
-{
-    HIPCHK(download(h, cnt, d_cnt, 3));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->raster_count) {
-        h->raster_counted = true;
-        h->raster_claims = cnt[2];
-    }
-    if (nowned) *nowned = (int64_t)cnt[1];
-    return SITRK_OK;
-}
-
 int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double d, int ny, int nx)
 {
     if (!std::isfinite(y0) || !std::isfinite(x0)) return fail(h, SITRK_EINVAL, "%s: y0_km and x0_km must be finite (got %g, %g)", fn, y0, x0);
@@ -275,8 +256,6 @@ int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double
     if ((int64_t)ny * nx > kRasMaxPixels) return fail(h, SITRK_EINVAL, "%s: ny*nx = %lld exceeds 2^28 pixels", fn, (long long)ny * nx);
     return SITRK_OK;
 }
-
-}  // namespace
 
 void raster_release(sitrk_ctx *h)
 {

@@ -28,7 +28,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib, coarse, ncio, raster
+from . import _lib, coarse, features, ncio, raster
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
@@ -116,7 +116,17 @@ def parse_args(argv=None):
                          'gradients of its status-1 cells box-averaged on the GPU, and per level the sums of A, A*div, A*shr, A*tot^q '
                          '(q = 1, 2, 3) over the boxes filled to at least FMIN (default 0.5) of their area, stored as m<k>_w<k>_coarse '
                          '(NLEV, 8) next to `coarse` = (nlev, fmin); the scaling exponents are logged.  At most 2^24 pixels')
+    ap.add_argument('--deform-features', type=_deform_features_arg, default=None, metavar='WHAT@THR[@MINPIX[@CONN]]',
+                    help='with --deform and --deform-grid: after each window the map of every mesh is taken apart into its features '
+                         '(extra; default none): the connected sets of pixels whose rate passes a threshold, labelled on the GPU.  WHAT '
+                         'is div (div >= THR), conv (-div >= THR), shr, vor or tot (div^2 + shr^2 >= THR^2), THR in 1/s; features of '
+                         'fewer than MINPIX pixels (default 1) are dropped; CONN = 4 or 8 neighbours (default 8).  Stored as '
+                         'm<k>_w<k>_features (rows, 12) int64 -- label, npix, jmin, jmax, imin, imax, the sums of j, i, j^2, i^2, j*i and '
+                         'the perimeter -- with m<k>_w<k>_features_counts = (nfeat, ncomp, nactive), next to `features` = (what, sgn, '
+                         'thr, min_pix, conn); the feature count and the longest feature are logged.  At most 32768 pixels a side')
     a = ap.parse_args(argv)
+    if a.deform_features is not None and a.deform_grid is None:
+        ap.error("--deform-features: it works on the grid of --deform-grid; give that flag too")
     if a.deform_grid is not None and not a.deform:
         ap.error("--deform-grid: there is no mesh to rasterise without --deform")
     if a.deform_coarse is not None and a.deform_grid is None:
@@ -176,6 +186,14 @@ def _deform_coarse_arg(text):
     """--deform-coarse: (nlev, fmin) of NLEV[@FMIN], NLEV in 1..16, FMIN finite >= 0 (default 0.5)"""
     try:
         return coarse.coarse_arg(text, '--deform-coarse')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _deform_features_arg(text):
+    """--deform-features: (what, sgn, thr, min_pix, conn) of WHAT@THR[@MINPIX[@CONN]]"""
+    try:
+        return features.features_arg(text, '--deform-features')
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -519,6 +537,8 @@ def read_mesh(a, ctx):
     if a.deform_coarse and dfm_grid[3] * dfm_grid[4] > coarse.MAX_PIXELS:
         raise ValueError('--deform-coarse: %g km over the model grid is %d x %d pixels, more than 2^24: take a coarser --deform-grid'
                          % (dfm_grid[2], dfm_grid[3], dfm_grid[4]))
+    if a.deform_features:
+        features.check_features_grid(dfm_grid, '--deform-features')
     return SimpleNamespace(imaskt=imaskt, xlatT=xlatT, xlonT=xlonT, xYf=xYf, xXf=xXf, xYu=xYu, xXu=xXu, xYv=xYv, xXv=xXv,
                            xResKM=xResKM, Nj=Nj, Ni=Ni, dfm_grid=dfm_grid)
 
@@ -814,8 +834,8 @@ class DeformSeries:
       win      the windows [(jrec0, jrec1)];  first / last: model record -> the window it opens / closes
       out      what is kept of every (mesh, window) for the file"""
 
-    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None):
-        self.specs, self.grid, self.grid_at, self.coarse = specs, grid, grid_at, coarse
+    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None):
+        self.specs, self.grid, self.grid_at, self.coarse, self.feat = specs, grid, grid_at, coarse, feat
         self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
         self.win = deform_windows(Nt, kstrt, window)
         self.first, self.last = {w[0]: k for k, w in enumerate(self.win)}, {w[1]: k for k, w in enumerate(self.win)}
@@ -867,6 +887,17 @@ class DeformSeries:
                 beta = coarse.scaling_exponents(tab, self.grid[2])["beta"]
                 self.say(' *** --deform-coarse window %d mesh %d: %d levels from %g km, filled boxes %s, beta(1..3) = %s'
                          % (kw, km, len(tab), self.grid[2], '/'.join('%d' % n for n in tab[:, 1]), ', '.join('%.4f' % b for b in beta)))
+            if self.feat is not None:                    # the features of this mesh's map: 96 bytes per feature come down
+                what, sgn, thr, min_pix, conn = self.feat
+                f = self.trk.mesh_features(jrec1, self.grid, what=what, thr=thr, sgn=sgn, conn=conn, min_pix=min_pix, slot=km,
+                                           at=self.grid_at)
+                self.out[pre + "features"] = f["table"]
+                self.out[pre + "features_counts"] = np.array([f["nfeat"], f["ncomp"], f["nactive"]], dtype=np.int64)
+                ft = features.feature_table(f["table"], self.grid)
+                self.say(' *** --deform-features window %d mesh %d: %d features of >= %d pixels (%d components, %d active pixels)%s, '
+                         'longest %s' % (kw, km, f["nfeat"], min_pix, f["ncomp"], f["nactive"],
+                                         '' if f["nfeat"] == len(f["table"]) else ', first %d kept' % len(f["table"]),
+                                         '%.3f km' % ft["length_km"].max() if len(f["table"]) else 'n/a'))
         self.clk.add("deform_s", t_d)
 
     def write(self, fname, vTime, kstrt):
@@ -876,7 +907,9 @@ class DeformSeries:
                        time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64),
                        time1=np.array([vTime[w[1] - kstrt + 1] for w in self.win], dtype=np.int64), **self.out,
                        **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}),
-                       **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}))
+                       **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}),
+                       **({"features": np.array((_lib.FEAT_WHAT[self.feat[0]],) + tuple(self.feat[1:]), dtype=np.float64)}
+                          if self.feat else {}))
 
 
 class Outputs:
@@ -1027,7 +1060,7 @@ def main(argv=None):
     bcast = record_broadcaster(a, comm, ctx, tphase)
     ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
-                       say, clk, coarse=a.deform_coarse) if a.deform else None
+                       say, clk, coarse=a.deform_coarse, feat=a.deform_features) if a.deform else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no

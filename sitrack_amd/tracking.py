@@ -342,6 +342,26 @@ class IceTracker:
         g = check_levels(check_grid(grid, cerr), nlev, fmin, cerr)
         return name_levels(self.ctx.mesh_coarse(slot, jrec1, g, int(nlev), fmin=float(fmin), boxes=boxes))
 
+    def mesh_features(self, jrec1, grid, what="tot", thr=0., sgn=1, conn=8, min_pix=1, maxfeat=65536, slot=0, at="t0", labels=False):
+        """Right after the step of `jrec1`: the features of the map of mesh `slot` on the grid (y0_km, x0_km, d_km, ny, nx) of
+        sit.raster_grid (an extra the reference does not have; sitrk_mesh_features): the connected sets, for conn = 4 or 8
+        neighbours, of the pixels mesh_raster() gives an owner whose rate passes the test -- what = "div", "shr" or "vor":
+        sgn*rate >= thr with sgn +1 or -1; what = "tot": div^2 + shr^2 >= thr^2 (sgn +1, thr >= 0); thr in the unit of mesh_deform().
+        A dict with table (rows, 12) int64 under the names _lib.FEAT_COLS, one row per feature of at least min_pix pixels in
+        ascending label, at most maxfeat rows; nfeat (all such features: above maxfeat the table is truncated), ncomp, nactive; and
+        labels: None, or with labels=True (ny,nx) int32, -1 or the lowest linear index of the pixel's feature.
+        sit.feature_table(table, grid) turns the rows into areas, lengths and orientations.  The map stays on the device."""
+        from .features import check_label_args, check_test
+        from .raster import check_grid
+        cerr = 'ERROR [IceTracker.mesh_features()]: '
+        if at not in ("t0", "t1"):
+            raise ValueError(cerr + '`at` must be "t0" or "t1", got %r' % (at,))
+        g = check_grid(grid, cerr)
+        conn, min_pix, maxfeat = check_label_args(g[3], g[4], conn, min_pix, maxfeat, cerr)
+        what, sgn, thr = check_test(what, sgn, thr, cerr)
+        return self.ctx.mesh_features(slot, jrec1, g, what, thr, sgn=sgn, conn=conn, min_pix=min_pix, maxfeat=maxfeat,
+                                      at_t1=(at == "t1"), labels=labels)
+
     def mesh_free(self, slot=0):
         self.ctx.mesh_free(slot)
 

@@ -2,7 +2,8 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]]] [-o OUT.npz]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]]]]
+                                [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
 positions of record K0 (Delaunay; needs scipy).  Records default to the first and the last; the elapsed time comes from
@@ -15,6 +16,12 @@ valid cell its centre lies in (the lowest on a shared edge, -1 for none), and `g
 D_KM*2^l over that grid (sitrk_coarse_cells): OUT then holds `coarse_table` (NLEV, 8) -- per level the boxes
 with a cell, the boxes filled to FMIN (default 0.5) of their area and over those the sums of A, A*div, A*shr, A*tot^q, q = 1,
 2, 3 --, `coarse` = (nlev, fmin) and `beta` (3,), the scaling exponents sit.scaling_exponents reads off the table.
+`--features WHAT@THR[@MINPIX[@CONN]]` with --grid takes that map apart into its features (sitrk_label_raster): the
+mask -- the pixels with an owner whose rate passes the threshold: WHAT = div (div >= THR), conv (-div >= THR), shr, vor or tot
+(div^2 + shr^2 >= THR^2), THR in 1/s -- is made here from `owner` and the rates, and its connected components (CONN = 4 or 8
+neighbours, default 8) of at least MINPIX pixels (default 1) are labelled on the GPU: OUT then holds `features` (rows, 12)
+int64 -- label, npix, jmin, jmax, imin, imax, the sums of j, i, j^2, i^2, j*i, the perimeter --, `features_counts` = (nfeat,
+ncomp, nactive) and `features_arg` = (what, sgn, thr, min_pix, conn).
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -73,8 +80,20 @@ def main(argv=None):
                     help='also rasterise the valid cells at their first-record positions onto pixels of D_KM km (`owner`, `grid` in the output)')
     ap.add_argument('--coarse', default=None, metavar='NLEV[@FMIN]',
                     help='with --grid: also coarse-grain the valid cells on NLEV levels over that grid (`coarse_table`, `coarse`, `beta` in the output)')
+    ap.add_argument('--features', default=None, metavar='WHAT@THR[@MINPIX[@CONN]]',
+                    help='with --grid: also label the connected features of the map where the rate WHAT (div, conv, shr, vor, tot) passes '
+                         'THR [1/s] (`features`, `features_counts`, `features_arg` in the output)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
+    feat = None
+    if a.features is not None:
+        from sitrack_amd.features import features_arg
+        if a.grid is None:
+            sys.exit('ERROR: --features: it works on the grid of --grid; give that flag too')
+        try:
+            feat = features_arg(a.features, '--features')
+        except ValueError as e:
+            sys.exit('ERROR: %s' % e)
     coarse = None
     if a.coarse is not None:
         from sitrack_amd.coarse import coarse_arg
@@ -139,6 +158,21 @@ def main(argv=None):
                 rc = sit.CoarseCells(yx0, yx1, cols, T, grid, coarse[0], fmin=coarse[1], mask0=ok0, mask1=ok1, ctx=ctx)
                 r['coarse_table'], r['coarse'] = rc['table'], np.array(coarse, dtype=np.float64)
                 r['beta'] = sit.scaling_exponents(rc['table'], a.grid)['beta']
+            if feat is not None:
+                if grid[3] > 32768 or grid[4] > 32768:
+                    sys.exit('ERROR: --features: %g km over the points is %d x %d pixels, more than 32768 a side' % (a.grid, grid[3], grid[4]))
+                what, sgn, thr, min_pix, conn = feat
+                own = r['owner']
+                at = np.maximum(own, 0)
+                with np.errstate(invalid='ignore'):
+                    if what == 'tot':
+                        hit = r['div'][at] * r['div'][at] + r['shr'][at] * r['shr'][at] >= thr * thr
+                    else:
+                        hit = sgn * r[what][at] >= thr
+                rf = sit.LabelRaster((own >= 0) & hit, conn=conn, min_pix=min_pix, ctx=ctx)
+                r['features'] = rf['table']
+                r['features_counts'] = np.array([rf['nfeat'], rf['ncomp'], rf['nactive']], dtype=np.int64)
+                r['features_arg'] = np.array([sit.FEAT_WHAT[what], sgn, thr, min_pix, conn], dtype=np.float64)
     finally:
         ctx.close()
     fout = a.fout or os.path.splitext(a.fin)[0] + '_deform.npz'
@@ -150,6 +184,11 @@ def main(argv=None):
     if coarse is not None:
         print(' *** --coarse %d levels, fmin %g: filled boxes %s, beta(1..3) = %s'
               % (coarse[0], coarse[1], '/'.join('%d' % n for n in r['coarse_table'][:, 1]), ', '.join('%.4f' % b for b in r['beta'])))
+    if feat is not None:
+        n = r['features_counts']
+        lengths = sit.feature_table(r['features'], tuple(r['grid'][:3]) + (r['owner'].shape[0], r['owner'].shape[1]))['length_km']
+        print(' *** --features %s: %d features of >= %d pixels (%d components, %d active pixels), longest %s'
+              % (a.features, n[0], feat[3], n[1], n[2], '%.3f km' % lengths.max() if len(lengths) else 'n/a'))
     return 0
 
 
