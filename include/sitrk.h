@@ -692,6 +692,64 @@ int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km
                         int32_t *labels, int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive);
 int sitrk_features_kernel_ms(sitrk_t *h, float *mask_ms, float *label_ms, float *table_ms);
 
+/* ---- features from window to window: kept label maps, carried by the ice, matched by overlap ---------------
+ * An EXTRA the reference does not have: which feature of one window is which feature of the next.  A tracker
+ * builds a new mesh per window, so cell identities do not survive a window; the buoys do.  A label map made on the t0 draw of
+ * window k is carried by the cells of that window's mesh to the window's end, which is the instant the t0 draw of window k+1 is
+ * made at: two maps at the same physical time on the same grid compare by plain pixel overlap.  No parity claim is made against
+ * any other code; the contract below is this library's own.  Everything is integer and no result depends on an order, so
+ * nothing is unpinned and two calls return the same bits.
+ * KEPT MAPS.  A context holds up to SITRK_KEEP_MAX kept maps, addressed by keep in 0..SITRK_KEEP_MAX-1.  Each is a shape
+ * (ny, nx) within the limits of sitrk_label_raster, an int32 map of that shape whose every value is -1 or in [0, ny*nx), and the
+ * conn and min_pix it was made with.  A kept map is a device allocation of the context's own, 4 bytes per pixel: neither the
+ * transient scratch nor a mesh.  Kept maps are freed by sitrk_keep_free and sitrk_destroy; stepping, re-sorts, sitrk_set_buoys,
+ * mesh calls and every call that uses the transient scratch leave them alone; a call that fails leaves every slot as it was.
+ * SITRK_EINVAL for a slot out of range and for reading an empty slot.
+ * sitrk_mesh_features_keep: every argument behind `keep` is one of sitrk_mesh_features, with the same validity, the same errors
+ * and the same bits in labels, table, *nfeat, *ncomp, *nactive.  It also fills slot keep with  K[p] = labels[p]  where the
+ * pixel's component has npix >= min_pix, else -1; a truncation of the table by maxfeat does not affect K.
+ * sitrk_keep_put: uploads the host map (ny,nx) into a slot, with conn in {4, 8} and min_pix >= 1 as its record of origin.  The
+ * map need not be a canonical labelling.  A value outside [-1, ny*nx) is SITRK_EINDEX with the number of offending values in
+ * sitrk_last_error; it is checked before the slot is replaced.
+ * sitrk_keep_get: any pointer may be NULL; with map == NULL nothing comes down but the four numbers.
+ * CARRYING A MAP WITH THE ICE.  sitrk_mesh_features_advect is valid wherever sitrk_mesh_raster(mesh, jrec1, ., grid) is; slot
+ * keep_from must hold a map of shape (ny, nx); keep_to may equal keep_from.  Its result is DEFINED BY THE EXISTING CONTRACTS: let
+ * o0 and o1 be the owner that sitrk_mesh_raster returns for the same arguments with at_t1 = 0 and at_t1 = 1, L the map of
+ * keep_from and nQ the cells of the mesh; then
+ *     cellfeat[q] = min { L[p] : o0[p] == q and L[p] >= 0 },  -1 when the set is empty          (q = 0 .. nQ-1)
+ *     M[p]        = o1[p] >= 0 ? cellfeat[o1[p]] : -1
+ * and slot keep_to becomes M, with keep_from's conn and min_pix.  *ncells = the cells with cellfeat >= 0, *ncarried = the pixels
+ * with M >= 0; either may be NULL.  The call does not ask whether L was made from this mesh.  A cell of status 2 is drawn at t0
+ * and not at t1 (the rasteriser's rule: it may have turned inside out), so what it carried is dropped.  Nothing but the two
+ * counts comes down.  The errors are those of sitrk_mesh_raster plus the slots'.
+ * MATCHING TWO KEPT MAPS.  sitrk_features_match needs both slots filled and of equal shape (keepA == keepB is allowed),
+ * 0 <= reach <= SITRK_MATCH_MAXREACH, |dj|, |di| <= 32768, maxpair >= 0 and pairs NULL iff maxpair == 0; else SITRK_EINVAL before
+ * any device work.  For a pixel p = (j,i) with a = A[j,i] >= 0, S(p) is the set of distinct values b >= 0 among
+ * B[j+dj+s, i+di+t] for |s|, |t| <= reach, positions outside the raster contributing nothing, and
+ *     count(a,b) = #{ p : A[p] == a and b in S(p) }.
+ * pairs (maxpair, 3) int64 holds the rows (a, b, count) with count >= 1 in ascending (a, b); only the first maxpair rows are
+ * written and the rest of `pairs` is left as it was.  *npair counts all such rows and may exceed maxpair; *nhit = the pixels of A
+ * with a non-empty S; either may be NULL.  With reach == 0 the table is the pixel overlap, symmetric under swapping the slots and
+ * negating the shift; with reach > 0 it is the A-side count, and the caller swaps the slots for the other side.  E = the sum of
+ * |S(p)| over the pixels is counted first: E > 2^31 - 1 is SITRK_EINVAL with a text, before anything is sized from it.
+ * sitrk_match_kernel_ms / sitrk_advect_kernel_ms: GPU time [ms] of the last such call on this handle, from HIP events -- the keys
+ * (counts, scan, emission), their sort, the rows (bounds, scan, rows); the kernels of the advection behind its two rasters; any
+ * pointer may be NULL, SITRK_EINVAL before any such call. */
+#define SITRK_KEEP_MAX 16
+#define SITRK_MATCH_MAXREACH 2
+int sitrk_mesh_features_keep(sitrk_t *h, int keep, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny,
+                             int nx, int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat,
+                             int32_t *labels, int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive);
+int sitrk_keep_put(sitrk_t *h, int keep, int ny, int nx, const int32_t *map, int conn, int64_t min_pix);
+int sitrk_keep_get(sitrk_t *h, int keep, int *ny, int *nx, int *conn, int64_t *min_pix, int32_t *map);
+int sitrk_keep_free(sitrk_t *h, int keep);
+int sitrk_mesh_features_advect(sitrk_t *h, int keep_from, int keep_to, int mesh, int jrec1, double y0_km, double x0_km, double d_km,
+                               int ny, int nx, int64_t *ncells, int64_t *ncarried);
+int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int di, int reach, int64_t maxpair, int64_t *pairs, int64_t *npair,
+                         int64_t *nhit);
+int sitrk_match_kernel_ms(sitrk_t *h, float *emit_ms, float *sort_ms, float *rows_ms);
+int sitrk_advect_kernel_ms(sitrk_t *h, float *advect_ms);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

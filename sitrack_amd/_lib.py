@@ -31,6 +31,9 @@ FEAT_NCOLS = 12                              # SITRK_FEAT_NCOLS, in this order:
 FEAT_COLS = ("label", "npix", "jmin", "jmax", "imin", "imax", "sum_j", "sum_i", "sum_jj", "sum_ii", "sum_ji", "perimeter")
 FEAT_WHAT = {"div": 0, "shr": 1, "vor": 2, "tot": 3}       # `what` of sitrk_mesh_features
 LABEL_TILE = 64                              # SITRK_LABEL_TILE
+KEEP_MAX = 16                                # SITRK_KEEP_MAX
+MATCH_MAXREACH = 2                           # SITRK_MATCH_MAXREACH
+MATCH_MAXSHIFT = 32768                       # |dj|, |di| of sitrk_features_match
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -112,6 +115,15 @@ _SIGNATURES = {
     "sitrk_mesh_features": (_int, [_vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _int, _dbl, _int, _i64, _i64, _vp, _vp,
                                    C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_features_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_mesh_features_keep": (_int, [_vp, _int, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _int, _dbl, _int, _i64, _i64, _vp, _vp,
+                                        C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_keep_put": (_int, [_vp, _int, _int, _int, _vp, _int, _i64]),
+    "sitrk_keep_get": (_int, [_vp, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_i64), _vp]),
+    "sitrk_keep_free": (_int, [_vp, _int]),
+    "sitrk_mesh_features_advect": (_int, [_vp, _int, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_features_match": (_int, [_vp, _int, _int, _int, _int, _int, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_match_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_advect_kernel_ms": (_int, [_vp, C.POINTER(C.c_float)]),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -957,6 +969,80 @@ class Context:
         v = [C.c_float(0) for _ in range(3)]
         self._chk(self._L.sitrk_features_kernel_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # -- features from window to window: kept maps, advection, matching (sitrk_keep_*, sitrk_mesh_features_advect, sitrk_features_match)
+    def mesh_features_keep(self, keep, mesh, jrec1, grid, what, thr, sgn=1, conn=8, min_pix=1, maxfeat=65536, at_t1=False, labels=False):
+        """sitrk_mesh_features_keep: mesh_features() with the same arguments and the same dict, and the labels of the features
+        of at least min_pix pixels (-1 elsewhere) kept on the device in slot `keep` (0..KEEP_MAX-1)"""
+        g = self._grid_arg(grid, "mesh_features_keep")
+        what = FEAT_WHAT.get(what, what)
+        maxfeat = int(maxfeat)
+        table = np.zeros((max(maxfeat, 0), FEAT_NCOLS), dtype=np.int64)
+        lab = np.empty((max(g[3], 0), max(g[4], 0)), dtype=np.int32) if labels else None
+        nfeat, ncomp, nactive = _i64(0), _i64(0), _i64(0)
+        self._chk(self._L.sitrk_mesh_features_keep(self._h, int(keep), int(mesh), int(jrec1), 1 if at_t1 else 0, *g, int(what), int(sgn),
+                                                   float(thr), int(conn), int(min_pix), maxfeat, _ptr(lab),
+                                                   _ptr(table) if maxfeat > 0 else None, C.byref(nfeat), C.byref(ncomp), C.byref(nactive)))
+        return self._features_result(table, nfeat, ncomp, nactive, lab)
+
+    def keep_put(self, keep, labels, conn=8, min_pix=1):
+        """sitrk_keep_put: the host map labels (ny,nx), every value -1 or in [0, ny*nx), into slot `keep`"""
+        a = np.asarray(labels)
+        if a.ndim != 2 or a.dtype.kind not in "iu":
+            raise ValueError("keep_put: labels must be an (ny, nx) array of integers, got %s %s" % (a.shape, a.dtype))
+        ny, nx = a.shape
+        if not (ny < 2 ** 31 and nx < 2 ** 31):
+            raise ValueError("keep_put: ny and nx must fit int32, got %d, %d" % (ny, nx))
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise IndexError("keep_put: a value of the map does not fit int32")
+        a = as_c(a, np.int32)
+        self._chk(self._L.sitrk_keep_put(self._h, int(keep), ny, nx, _ptr(a), int(conn), int(min_pix)))
+
+    def keep_get(self, keep, labels=True):
+        """sitrk_keep_get: {"shape": (ny, nx), "conn", "min_pix", "labels": (ny,nx) int32 or None with labels=False} of slot `keep`"""
+        ny, nx, conn, min_pix = _int(0), _int(0), _int(0), _i64(0)
+        self._chk(self._L.sitrk_keep_get(self._h, int(keep), C.byref(ny), C.byref(nx), C.byref(conn), C.byref(min_pix), None))
+        lab = None
+        if labels:
+            lab = np.empty((ny.value, nx.value), dtype=np.int32)
+            self._chk(self._L.sitrk_keep_get(self._h, int(keep), None, None, None, None, _ptr(lab)))
+        return {"shape": (ny.value, nx.value), "conn": conn.value, "min_pix": min_pix.value, "labels": lab}
+
+    def keep_free(self, keep):
+        self._chk(self._L.sitrk_keep_free(self._h, int(keep)))
+
+    def mesh_features_advect(self, keep_from, keep_to, mesh, jrec1, grid):
+        """sitrk_mesh_features_advect, right after the step of jrec1: the map of slot keep_from carried by the cells of the mesh
+        in slot `mesh` from their t0 draw to their t1 draw on the grid, into slot keep_to.  (ncells, ncarried): the cells that
+        carry a label, the pixels that received one."""
+        g = self._grid_arg(grid, "mesh_features_advect")
+        ncells, ncarried = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_mesh_features_advect(self._h, int(keep_from), int(keep_to), int(mesh), int(jrec1), *g, C.byref(ncells),
+                                                     C.byref(ncarried)))
+        return ncells.value, ncarried.value
+
+    def features_match(self, keepA, keepB, reach=0, dj=0, di=0, maxpair=1 << 20):
+        """sitrk_features_match: {"pairs": (rows, 3) int64 rows (a, b, count) in ascending (a, b), at most maxpair of them,
+        "npair": all such rows, "nhit": the pixels of A that meet a feature of B} of the kept maps keepA and keepB, B read at
+        the shift (dj, di) and within `reach` pixels"""
+        maxpair = int(maxpair)
+        pairs = np.zeros((max(maxpair, 0), 3), dtype=np.int64)
+        npair, nhit = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_features_match(self._h, int(keepA), int(keepB), int(dj), int(di), int(reach), maxpair,
+                                               _ptr(pairs) if maxpair > 0 else None, C.byref(npair), C.byref(nhit)))
+        return {"pairs": pairs[:min(npair.value, pairs.shape[0])], "npair": npair.value, "nhit": nhit.value}
+
+    def match_kernel_ms(self):
+        """(emit_ms, sort_ms, rows_ms): GPU time of the phases of the last features_match (sitrk_match_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_match_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def advect_kernel_ms(self):
+        """advect_ms: GPU time of the kernels of the last mesh_features_advect behind its two rasters (sitrk_advect_kernel_ms)"""
+        v = C.c_float(0)
+        self._chk(self._L.sitrk_advect_kernel_ms(self._h, C.byref(v)))
+        return v.value
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

@@ -133,6 +133,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     raster_release(h);
     coarse_release(h);
     label_release(h);
+    track_release(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);

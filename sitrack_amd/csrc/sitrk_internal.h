@@ -11,6 +11,7 @@ namespace sitrk {
 
 hipError_t sort_pairs_u32(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uint32_t *kout,
                           const int32_t *vin, int32_t *vout, size_t n, unsigned end_bit, hipStream_t s);
+hipError_t sort_keys_u64(void *tmp, size_t *tmp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, unsigned end_bit, hipStream_t s);
 
 // Seed-cloud coarsening (sitrk_subsample.hip): cells of side 1/inv_h, ny x nx of them, from (ymin, xmin)
 struct SubGrid {
@@ -87,6 +88,14 @@ struct Mesh {
     int jrec0 = 0;                      // the model record those positions belong to (stepped next when they were taken)
     double rmax_km = 0.0;
     QuadParams par = {0.0, 0.0, 0.0, 0.0, 0.0};
+};
+
+// A kept label map (sitrk_track.hip): a device allocation of its own, neither the transient scratch nor a mesh
+struct KeptMap {
+    int32_t *map = nullptr;             // (ny*nx) -1 or a label in [0, ny*nx); null: the slot is empty
+    size_t cap = 0;                     // pixels the allocation holds
+    int ny = 0, nx = 0, conn = 0;
+    int64_t min_pix = 0;
 };
 
 // Device-resident buoy state, structure of arrays, in SORTED slot order.
@@ -271,6 +280,15 @@ struct sitrk_ctx {
     hipEvent_t label_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool label_timed = false;
 
+    // features from window to window (sitrk_track.hip): the kept label maps, which outlive the buoys and the meshes, and the
+    // allocation the last replaced map left behind, taken again by the next call that fills a slot.  Events: [0]..[3] around the
+    // three phases of the last match -- keys, sort, rows --, [4],[5] around the two kernels of the last advect behind its rasters
+    sitrk::KeptMap keep[SITRK_KEEP_MAX];
+    int32_t *keep_spare = nullptr;
+    size_t keep_spare_cap = 0;
+    hipEvent_t track_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool match_timed = false, advect_timed = false;
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -340,6 +358,15 @@ int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double
 int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g);
 // sitrk_label.hip: destroys the timing events (sitrk_destroy)
 void label_release(sitrk_ctx *h);
+// ... and the body of sitrk_mesh_features behind the handle's check, for sitrk_mesh_features_keep (sitrk_track.hip): keep_map (ny*nx
+// on the device, may be null) receives the labels of the components of at least min_pix pixels, -1 elsewhere
+int mesh_features_body(sitrk_ctx *h, const char *fn, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny,
+                       int nx, int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat, int32_t *labels, int64_t *table,
+                       int64_t *nfeat, int64_t *ncomp, int64_t *nactive, int32_t *keep_map);
+// sitrk_track.hip: queues the kernel behind keep_map on the compute stream and synchronises; frees the kept maps and destroys the
+// timing events (sitrk_destroy)
+int keep_from_labels(sitrk_ctx *h, int64_t npix, const int32_t *labels, const int32_t *flag, int32_t *keep_map);
+void track_release(sitrk_ctx *h);
 // sitrk_coarse.hip: destroys the timing events (sitrk_destroy)
 void coarse_release(sitrk_ctx *h);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)

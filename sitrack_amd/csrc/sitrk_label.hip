@@ -600,12 +600,12 @@ SITRK_API int sitrk_label_raster(sitrk_t *h, int ny, int nx, const int8_t *activ
     return label_run(h, fn, j, b, labels, table, nfeat, ncomp, nactive);
 }
 
-SITRK_API int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny, int nx,
-                                  int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat, int32_t *labels,
-                                  int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive)
+// the body of sitrk_mesh_features behind the handle's check; keep_map (npix, may be null: sitrk_mesh_features_keep of
+// sitrk_track.hip) receives the labels of the components that passed min_pix, -1 elsewhere, once everything else has succeeded
+int sitrk::mesh_features_body(sitrk_ctx *h, const char *fn, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny,
+                              int nx, int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat, int32_t *labels,
+                              int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive, int32_t *keep_map)
 {
-    const char *fn = "sitrk_mesh_features";
-    NEED(h, "null handle");
     RCCHK(mesh_deform_check(h, fn, mesh, jrec1));
     if (at_t1 != 0 && at_t1 != 1) return fail(h, SITRK_EINVAL, "%s: at_t1 must be 0 (t0 positions) or 1 (current positions), got %d", fn, at_t1);
     RCCHK(raster_check_grid(h, fn, y0_km, x0_km, d_km, ny, nx));
@@ -649,7 +649,17 @@ SITRK_API int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, do
     HIPCHK(download(h, cnt, d_cnt, 3));                                // lands with the synchronisation of label_run
     RCCHK(label_run(h, fn, j, b, labels, table, nfeat, ncomp, nactive));
     if (cnt[0]) return fail(h, SITRK_EINDEX, "%s: %llu cell(s) of the mesh have a vertex index outside [0, %lld)", fn, cnt[0], (long long)h->nP);
+    if (keep_map) RCCHK(keep_from_labels(h, npix, b.labels, b.parent, keep_map));     // the flags lie over the parents (label_run)
     return SITRK_OK;
+}
+
+SITRK_API int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny, int nx,
+                                  int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat, int32_t *labels,
+                                  int64_t *table, int64_t *nfeat, int64_t *ncomp, int64_t *nactive)
+{
+    NEED(h, "null handle");
+    return mesh_features_body(h, "sitrk_mesh_features", mesh, jrec1, at_t1, y0_km, x0_km, d_km, ny, nx, what, sgn, thr, conn, min_pix, maxfeat,
+                              labels, table, nfeat, ncomp, nactive, nullptr);
 }
 
 SITRK_API int sitrk_features_kernel_ms(sitrk_t *h, float *mask_ms, float *label_ms, float *table_ms)

@@ -17,4 +17,10 @@ hipError_t sort_pairs_u32(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uin
     return rocprim::radix_sort_pairs(tmp, *tmp_bytes, kin, kout, vin, vout, n, 0u, end_bit, s);
 }
 
+// the same protocol for bare 64-bit keys, on the bits [0, end_bit) (sitrk_track.hip)
+hipError_t sort_keys_u64(void *tmp, size_t *tmp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, unsigned end_bit, hipStream_t s)
+{
+    return rocprim::radix_sort_keys(tmp, *tmp_bytes, kin, kout, n, 0u, end_bit, s);
+}
+
 }  // namespace sitrk

@@ -124,7 +124,18 @@ def parse_args(argv=None):
                          'm<k>_w<k>_features (rows, 12) int64 -- label, npix, jmin, jmax, imin, imax, the sums of j, i, j^2, i^2, j*i and '
                          'the perimeter -- with m<k>_w<k>_features_counts = (nfeat, ncomp, nactive), next to `features` = (what, sgn, '
                          'thr, min_pix, conn); the feature count and the longest feature are logged.  At most 32768 pixels a side')
+    ap.add_argument('--deform-track', type=_deform_track_arg, nargs='?', const=1, default=None, metavar='REACH',
+                    help='with --deform-features on the t0 draw: the features of every window are linked to those of the window before '
+                         '(extra; default none).  The label map of a window is kept on the GPU, carried to the window\'s end by the '
+                         'cells of its own mesh, and compared there with the map of the next window, pixel by pixel and within REACH '
+                         'pixels (0..2, default 1).  Stored as m<k>_w<k>_pairs (npair, 3) int64 -- the label in the window before, '
+                         'the label in this one, the pixels where they meet -- with m<k>_w<k>_pairs_counts = (npair, nhit), and per '
+                         'row of m<k>_w<k>_features m<k>_w<k>_track and m<k>_w<k>_age, next to `track` = (reach,); the features '
+                         'continued, born, ended, merged and split are logged.  At most 8 meshes')
     a = ap.parse_args(argv)
+    refusal = deform_track_refusal(a.deform_track, a.deform_features, a.deform_grid, len(a.deform))
+    if refusal:
+        ap.error(refusal)
     if a.deform_features is not None and a.deform_grid is None:
         ap.error("--deform-features: it works on the grid of --deform-grid; give that flag too")
     if a.deform_grid is not None and not a.deform:
@@ -196,6 +207,28 @@ def _deform_features_arg(text):
         return features.features_arg(text, '--deform-features')
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
+
+
+def _deform_track_arg(text):
+    """--deform-track: REACH, an integer in 0..2"""
+    try:
+        return features.track_arg(text, '--deform-track')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def deform_track_refusal(track, feat, grid, nmesh):
+    """--deform-track: why the flags given cannot be tracked with, or None: it links the features of --deform-features, compares
+    maps of the t0 draw, and takes two kept maps per mesh"""
+    if track is None:
+        return None
+    if feat is None:
+        return "--deform-track: it links the features of --deform-features; give that flag too"
+    if grid is not None and grid[1] == "t1":
+        return "--deform-track: tracking compares the t0 draw of a window with the window before carried to that instant; --deform-grid D_KM@t1 cannot be tracked"
+    if 2 * nmesh > _lib.KEEP_MAX:
+        return "--deform-track: two kept maps per mesh and %d of them: at most %d meshes, got %d" % (_lib.KEEP_MAX, _lib.KEEP_MAX // 2, nmesh)
+    return None
 
 
 def deform_grid(xYf, xXf, d_km):
@@ -834,8 +867,9 @@ class DeformSeries:
       win      the windows [(jrec0, jrec1)];  first / last: model record -> the window it opens / closes
       out      what is kept of every (mesh, window) for the file"""
 
-    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None):
-        self.specs, self.grid, self.grid_at, self.coarse, self.feat = specs, grid, grid_at, coarse, feat
+    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None, track=None):
+        self.specs, self.grid, self.grid_at, self.coarse, self.feat, self.track = specs, grid, grid_at, coarse, feat, track
+        self.links = {}                                  # --deform-track: (mesh, window) -> the links to the window before
         self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
         self.win = deform_windows(Nt, kstrt, window)
         self.first, self.last = {w[0]: k for k, w in enumerate(self.win)}, {w[1]: k for k, w in enumerate(self.win)}
@@ -889,8 +923,9 @@ class DeformSeries:
                          % (kw, km, len(tab), self.grid[2], '/'.join('%d' % n for n in tab[:, 1]), ', '.join('%.4f' % b for b in beta)))
             if self.feat is not None:                    # the features of this mesh's map: 96 bytes per feature come down
                 what, sgn, thr, min_pix, conn = self.feat
+                # --deform-track: kept map 2km = this window's features, 2km + 1 = those of the window before at this window's start
                 f = self.trk.mesh_features(jrec1, self.grid, what=what, thr=thr, sgn=sgn, conn=conn, min_pix=min_pix, slot=km,
-                                           at=self.grid_at)
+                                           at=self.grid_at, keep=None if self.track is None else 2 * km)
                 self.out[pre + "features"] = f["table"]
                 self.out[pre + "features_counts"] = np.array([f["nfeat"], f["ncomp"], f["nactive"]], dtype=np.int64)
                 ft = features.feature_table(f["table"], self.grid)
@@ -898,10 +933,31 @@ class DeformSeries:
                          'longest %s' % (kw, km, f["nfeat"], min_pix, f["ncomp"], f["nactive"],
                                          '' if f["nfeat"] == len(f["table"]) else ', first %d kept' % len(f["table"]),
                                          '%.3f km' % ft["length_km"].max() if len(f["table"]) else 'n/a'))
+                if self.track is not None:
+                    if kw > 0:                           # 24 bytes per pair of features that meet come down
+                        m = self.trk.features_match(2 * km + 1, 2 * km, reach=self.track)
+                        self.out[pre + "pairs"] = m["pairs"]
+                        self.out[pre + "pairs_counts"] = np.array([m["npair"], m["nhit"]], dtype=np.int64)
+                        self.links[(km, kw)] = features.link_features(m["pairs"], self.out["m%d_w%d_features" % (km, kw - 1)], f["table"])
+                    self.trk.features_advect(jrec1, self.grid, 2 * km, 2 * km + 1, slot=km)   # ... to the start of the next window
         self.clk.add("deform_s", t_d)
+
+    def tracks(self):
+        """--deform-track, behind the last window: m<k>_w<k>_track and _age of every feature, and one line per window"""
+        for km in range(len(self.specs)):
+            nrows = [len(self.out["m%d_w%d_features" % (km, kw)]) for kw in range(len(self.win))]
+            links = [self.links[(km, kw)] for kw in range(1, len(self.win))]
+            track, age = features.feature_tracks(links, nrows)
+            for kw in range(len(self.win)):
+                self.out["m%d_w%d_track" % (km, kw)], self.out["m%d_w%d_age" % (km, kw)] = track[kw], age[kw]
+                if kw > 0:
+                    self.say(' *** --deform-track window %d mesh %d: %d continued, %d born, %d ended, %d merged, %d split'
+                             % ((kw, km) + features.track_events(links[kw - 1], track[kw - 1], track[kw])))
 
     def write(self, fname, vTime, kstrt):
         """the run's .npz; vTime: the times of records 0..Nt of the series"""
+        if self.track is not None:
+            self.tracks()
         _savez_deflate(fname, meshes=np.array(self.specs, dtype=np.float64).reshape(-1, 2),
                        windows=np.array(self.win, dtype=np.int64).reshape(-1, 2),
                        time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64),
@@ -909,7 +965,8 @@ class DeformSeries:
                        **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}),
                        **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}),
                        **({"features": np.array((_lib.FEAT_WHAT[self.feat[0]],) + tuple(self.feat[1:]), dtype=np.float64)}
-                          if self.feat else {}))
+                          if self.feat else {}),
+                       **({"track": np.array([self.track], dtype=np.int64)} if self.track is not None else {}))
 
 
 class Outputs:
@@ -1060,7 +1117,7 @@ def main(argv=None):
     bcast = record_broadcaster(a, comm, ctx, tphase)
     ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
-                       say, clk, coarse=a.deform_coarse, feat=a.deform_features) if a.deform else None
+                       say, clk, coarse=a.deform_coarse, feat=a.deform_features, track=a.deform_track) if a.deform else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no

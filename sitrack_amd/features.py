@@ -4,12 +4,17 @@ An extra the reference does not have: the connected components of a mask on a re
 kinematic features of a deformation map -- labelled on the GPU, one row of twelve integers per feature coming down instead of
 the map; the contract is in include/sitrk.h and DESIGN.md 3.17.  There is no host version.  A running tracker labels the map of
 its device-resident meshes with IceTracker.mesh_features(); feature_table() turns the integer rows into areas, centroids,
-lengths, widths and orientations."""
+lengths, widths and orientations.
+
+Features from window to window (sitrack_amd/csrc/sitrk_track.hip): IceTracker.mesh_features(keep=...),
+features_advect() and features_match() keep, carry and compare label maps on the device; MatchLabels() compares two host maps
+the same way; link_features() and feature_tracks() turn the pair tables into parents, children and tracks, on the host and in
+integers."""
 import math
 
 import numpy as np
 
-from ._lib import FEAT_COLS, FEAT_NCOLS, FEAT_WHAT
+from ._lib import FEAT_COLS, FEAT_NCOLS, FEAT_WHAT, KEEP_MAX, MATCH_MAXREACH, MATCH_MAXSHIFT
 
 MAX_SIDE = 32768
 MAX_PIXELS = 2 ** 28
@@ -142,3 +147,181 @@ def feature_table(table, grid):
             "length_km": d * np.sqrt(12. * l1), "width_km": d * np.sqrt(12. * l2),
             "angle": 0.5 * np.arctan2(2. * cji, cii - cjj), "perimeter_km": c["perimeter"] * d,
             "jmin": c["jmin"].copy(), "jmax": c["jmax"].copy(), "imin": c["imin"].copy(), "imax": c["imax"].copy()}
+
+
+# ------------------------------------------------------------------------------------------------ features from window to window
+def check_keep(keep, name="keep", cerr=''):
+    """a slot of the kept maps as an integer in 0..KEEP_MAX-1"""
+    k = _as_int(keep, name, cerr)
+    if not 0 <= k < KEEP_MAX:
+        raise ValueError(cerr + '`%s` must be in 0..%d, got %r' % (name, KEEP_MAX - 1, keep))
+    return k
+
+
+def check_match_args(reach, dj, di, maxpair, cerr=''):
+    """the library's checks of reach, shift and maxpair of sitrk_features_match; returns them as integers"""
+    reach, dj, di, maxpair = (_as_int(v, n, cerr) for v, n in ((reach, "reach"), (dj, "dj"), (di, "di"), (maxpair, "maxpair")))
+    if not 0 <= reach <= MATCH_MAXREACH:
+        raise ValueError(cerr + '`reach` must be in 0..%d pixels, got %r' % (MATCH_MAXREACH, reach))
+    if abs(dj) > MATCH_MAXSHIFT or abs(di) > MATCH_MAXSHIFT:
+        raise ValueError(cerr + 'the shift `dj`, `di` must be within +-%d pixels, got %r, %r' % (MATCH_MAXSHIFT, dj, di))
+    if maxpair < 0:
+        raise ValueError(cerr + '`maxpair` must be >= 0, got %r' % (maxpair,))
+    return reach, dj, di, maxpair
+
+
+def track_arg(text, flag='--deform-track'):
+    """REACH of --deform-track [REACH]: an integer in 0..MATCH_MAXREACH.  ValueError otherwise."""
+    try:
+        reach = int(text)
+    except (TypeError, ValueError):
+        raise ValueError("%s: REACH must be an integer number of pixels, got %r" % (flag, text)) from None
+    if not 0 <= reach <= MATCH_MAXREACH:
+        raise ValueError("%s: REACH must be in 0..%d pixels, got %r" % (flag, MATCH_MAXREACH, text))
+    return reach
+
+
+def _label_map(a, name, cerr):
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype.kind not in "iu":
+        raise ValueError(cerr + '`%s` must be an (ny, nx) array of integers, got %s %s' % (name, a.shape, a.dtype))
+    return a
+
+
+def MatchLabels(mapA, mapB, reach=0, dj=0, di=0, maxpair=1 << 20, ctx=None):
+    """The features of two label maps (ny, nx) -- every value -1 or a label in [0, ny*nx), as LabelRaster gives them -- that meet:
+    for every pixel p of mapA with a label a, the distinct labels b of mapB within `reach` pixels (0..2) of p shifted by (dj, di)
+    count once for the pair (a, b).  Returns {"pairs": (rows, 3) int64 rows (a, b, count) in ascending (a, b), at most maxpair of
+    them, "npair": all such rows, "nhit": the pixels of mapA that meet a feature of mapB}.  With reach = 0 this is the pixel
+    overlap.  Runs on the GPU: two kept maps (slots KEEP_MAX-2 and KEEP_MAX-1 of the context, freed again) and
+    sitrk_features_match.  Raises ValueError on bad arguments before any device work."""
+    from .tracking import default_context
+    cerr = 'ERROR [MatchLabels()]: '
+    a, b = _label_map(mapA, "mapA", cerr), _label_map(mapB, "mapB", cerr)
+    if a.shape != b.shape:
+        raise ValueError(cerr + 'the two maps must have one shape, got %s and %s' % (a.shape, b.shape))
+    check_label_args(a.shape[0], a.shape[1], 8, 1, 0, cerr)
+    reach, dj, di, maxpair = check_match_args(reach, dj, di, maxpair, cerr)
+    c = ctx or default_context()
+    sa, sb = KEEP_MAX - 2, KEEP_MAX - 1
+    try:
+        c.keep_put(sa, a)
+        c.keep_put(sb, b)
+        return c.features_match(sa, sb, reach=reach, dj=dj, di=di, maxpair=maxpair)
+    finally:
+        c.keep_free(sa)
+        c.keep_free(sb)
+
+
+def kept_labels(labels, min_pix=1):
+    """what sitrk_mesh_features_keep keeps of a label map: the label where the pixel's component has at least min_pix pixels,
+    else -1 (host, numpy)"""
+    lab = np.asarray(labels)
+    act = lab >= 0
+    npix = np.bincount(lab[act].astype(np.int64), minlength=max(lab.size, 1))
+    return np.where(act & (npix[np.maximum(lab, 0)] >= min_pix), lab, -1).astype(np.int32)
+
+
+def advect_labels(labels, owner0, owner1, ncells):
+    """the host counterpart of sitrk_mesh_features_advect for maps that are on the host already (numpy): cell q takes the lowest
+    label >= 0 among the pixels with owner0 == q, and gives it to the pixels with owner1 == q; -1 where there is none.  Returns
+    (M (ny, nx) int32, cellfeat (ncells,) int32)."""
+    lab, o0, o1 = np.asarray(labels), np.asarray(owner0), np.asarray(owner1)
+    if not (lab.shape == o0.shape == o1.shape):
+        raise ValueError('ERROR [advect_labels()]: the three maps must have one shape, got %s, %s, %s' % (lab.shape, o0.shape, o1.shape))
+    big = np.iinfo(np.int32).max
+    cellfeat = np.full(int(ncells), big, dtype=np.int32)
+    use = (o0 >= 0) & (lab >= 0)
+    np.minimum.at(cellfeat, o0[use], lab[use].astype(np.int32))
+    cellfeat[cellfeat == big] = -1
+    M = np.where(o1 >= 0, cellfeat[np.maximum(o1, 0)] if ncells else -1, -1).astype(np.int32)
+    return M, cellfeat
+
+
+def link_features(pairs, tableA, tableB, min_overlap=1):
+    """The links between the features of two windows from the rows (a, b, count) of a match of A (the earlier map) against B and
+    the two feature tables (rows, >= 1) whose column 0 is the label in ascending order.  Pairs with count < min_overlap are no
+    links.  Returns a dict of int64 arrays: parent (rowsB,) the row in tableA of the A feature with the largest count into that B
+    feature, ties to the lowest label, -1 for none; child (rowsA,) likewise from the A side, a row of tableB; nparents (rowsB,)
+    and nchildren (rowsA,) the number of links (the merge and the split degree); and dropped: the pairs that name a label absent
+    from its table (a table truncated by maxfeat), which are ignored."""
+    cerr = 'ERROR [link_features()]: '
+    p = np.asarray(pairs)
+    if p.ndim != 2 or p.shape[1] != 3 or (p.size and p.dtype.kind not in "iu"):
+        raise ValueError(cerr + '`pairs` must be (rows, 3) integers, got %s %s' % (p.shape, p.dtype))
+    p = p.astype(np.int64).reshape(-1, 3)
+    labs = []
+    for t, name in ((tableA, "tableA"), (tableB, "tableB")):
+        t = np.asarray(t)
+        if t.ndim != 2 or t.shape[1] < 1 or (t.size and t.dtype.kind not in "iu"):
+            raise ValueError(cerr + '`%s` must be (rows, >= 1) integers, got %s %s' % (name, t.shape, t.dtype))
+        lab = t[:, 0].astype(np.int64)
+        if np.any(lab[1:] <= lab[:-1]):
+            raise ValueError(cerr + 'the labels of `%s` must ascend strictly' % name)
+        labs.append(lab)
+    min_overlap = _as_int(min_overlap, "min_overlap", cerr)
+    la, lb = labs
+
+    def row_of(lab, v):
+        if not len(lab):
+            return np.full(len(v), -1, dtype=np.int64)
+        r = np.minimum(np.searchsorted(lab, v), len(lab) - 1)
+        return np.where(lab[r] == v, r, -1).astype(np.int64)
+
+    p = p[p[:, 2] >= min_overlap]
+    ra, rb = row_of(la, p[:, 0]), row_of(lb, p[:, 1])
+    known = (ra >= 0) & (rb >= 0)
+    dropped = int((~known).sum())
+    ra, rb, cnt = ra[known], rb[known], p[known, 2]
+
+    def best(mine, other, n):
+        """per row of `mine`: the row of `other` with the largest count, the lowest on a tie; and the number of links"""
+        out = np.full(n, -1, dtype=np.int64)
+        order = np.lexsort((other, -cnt, mine))                        # by mine, then falling count, then rising other
+        m = mine[order]
+        first = np.ones(len(m), dtype=bool)
+        first[1:] = m[1:] != m[:-1]
+        out[m[first]] = other[order][first]
+        return out, np.bincount(mine, minlength=n).astype(np.int64)
+
+    parent, nparents = best(rb, ra, len(lb))
+    child, nchildren = best(ra, rb, len(la))
+    return {"parent": parent, "child": child, "nparents": nparents, "nchildren": nchildren, "dropped": dropped}
+
+
+def feature_tracks(links, nrows):
+    """Tracks through the windows of a series: nrows[k] = the features (table rows) of window k, links[k] = link_features() of
+    window k against window k+1 (len(nrows) - 1 of them).  A feature continues the track of its parent iff it is also that
+    parent's child; otherwise it starts a new track.  Track ids are handed out in window order, then row order, from 0.  Returns
+    (track, age): per window an int64 array of track ids and one of ages, the windows the track has lived before this one."""
+    cerr = 'ERROR [feature_tracks()]: '
+    nrows = [_as_int(n, "nrows", cerr) for n in nrows]
+    if len(links) != max(len(nrows) - 1, 0):
+        raise ValueError(cerr + '%d windows need %d links, got %d' % (len(nrows), max(len(nrows) - 1, 0), len(links)))
+    track, age, nxt = [], [], 0
+    for k, n in enumerate(nrows):
+        t, a = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        if k > 0:
+            par, chi = np.asarray(links[k - 1]["parent"]), np.asarray(links[k - 1]["child"])
+            if len(par) != n or len(chi) != nrows[k - 1]:
+                raise ValueError(cerr + 'links[%d] does not fit the rows of windows %d and %d' % (k - 1, k - 1, k))
+            has = par >= 0
+            cont = np.zeros(n, dtype=bool)
+            cont[has] = chi[par[has]] == np.flatnonzero(has)
+            t[cont] = track[k - 1][par[cont]]
+            a[cont] = age[k - 1][par[cont]] + 1
+        new = t < 0
+        t[new] = nxt + np.arange(int(new.sum()), dtype=np.int64)
+        nxt += int(new.sum())
+        track.append(t)
+        age.append(a)
+    return track, age
+
+
+def track_events(link, track_prev, track_next):
+    """(continued, born, ended, merged, split) between two windows: features of the later window that continue a track, that
+    start one, tracks of the earlier window that are not continued, features of the later window with more than one parent,
+    features of the earlier one with more than one child"""
+    cont = int(np.isin(track_next, track_prev).sum()) if len(track_prev) else 0
+    return (cont, len(track_next) - cont, len(track_prev) - cont, int((np.asarray(link["nparents"]) > 1).sum()),
+            int((np.asarray(link["nchildren"]) > 1).sum()))

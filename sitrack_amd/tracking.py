@@ -342,7 +342,8 @@ class IceTracker:
         g = check_levels(check_grid(grid, cerr), nlev, fmin, cerr)
         return name_levels(self.ctx.mesh_coarse(slot, jrec1, g, int(nlev), fmin=float(fmin), boxes=boxes))
 
-    def mesh_features(self, jrec1, grid, what="tot", thr=0., sgn=1, conn=8, min_pix=1, maxfeat=65536, slot=0, at="t0", labels=False):
+    def mesh_features(self, jrec1, grid, what="tot", thr=0., sgn=1, conn=8, min_pix=1, maxfeat=65536, slot=0, at="t0", labels=False,
+                      keep=None):
         """Right after the step of `jrec1`: the features of the map of mesh `slot` on the grid (y0_km, x0_km, d_km, ny, nx) of
         sit.raster_grid (an extra the reference does not have; sitrk_mesh_features): the connected sets, for conn = 4 or 8
         neighbours, of the pixels mesh_raster() gives an owner whose rate passes the test -- what = "div", "shr" or "vor":
@@ -350,8 +351,10 @@ class IceTracker:
         A dict with table (rows, 12) int64 under the names _lib.FEAT_COLS, one row per feature of at least min_pix pixels in
         ascending label, at most maxfeat rows; nfeat (all such features: above maxfeat the table is truncated), ncomp, nactive; and
         labels: None, or with labels=True (ny,nx) int32, -1 or the lowest linear index of the pixel's feature.
-        sit.feature_table(table, grid) turns the rows into areas, lengths and orientations.  The map stays on the device."""
-        from .features import check_label_args, check_test
+        sit.feature_table(table, grid) turns the rows into areas, lengths and orientations.  The map stays on the device.
+        keep = 0..15: the labels of the features of at least min_pix pixels also stay on the device as kept map `keep`, for
+        features_advect() and features_match() (sitrk_mesh_features_keep); everything returned is what it is without it."""
+        from .features import check_keep, check_label_args, check_test
         from .raster import check_grid
         cerr = 'ERROR [IceTracker.mesh_features()]: '
         if at not in ("t0", "t1"):
@@ -359,8 +362,35 @@ class IceTracker:
         g = check_grid(grid, cerr)
         conn, min_pix, maxfeat = check_label_args(g[3], g[4], conn, min_pix, maxfeat, cerr)
         what, sgn, thr = check_test(what, sgn, thr, cerr)
+        if keep is not None:
+            keep = check_keep(keep, "keep", cerr)
+            return self.ctx.mesh_features_keep(keep, slot, jrec1, g, what, thr, sgn=sgn, conn=conn, min_pix=min_pix,
+                                               maxfeat=maxfeat, at_t1=(at == "t1"), labels=labels)
         return self.ctx.mesh_features(slot, jrec1, g, what, thr, sgn=sgn, conn=conn, min_pix=min_pix, maxfeat=maxfeat,
                                       at_t1=(at == "t1"), labels=labels)
+
+    def features_advect(self, jrec1, grid, keep_from, keep_to, slot=0):
+        """Right after the step of `jrec1`: the kept map keep_from carried by the cells of mesh `slot` from where they were at the
+        mesh's t0 to where they are now, into the kept map keep_to (an extra the reference does not have;
+        sitrk_mesh_features_advect): a cell takes the lowest label among the pixels it owns on the t0 draw and gives it to the
+        pixels it owns on the t1 draw.  A dict with ncells, the cells that carry a label, and ncarried, the pixels that received
+        one.  Nothing else leaves the device."""
+        from .features import check_keep
+        from .raster import check_grid
+        cerr = 'ERROR [IceTracker.features_advect()]: '
+        g = check_grid(grid, cerr)
+        keep_from, keep_to = check_keep(keep_from, "keep_from", cerr), check_keep(keep_to, "keep_to", cerr)
+        ncells, ncarried = self.ctx.mesh_features_advect(keep_from, keep_to, slot, jrec1, g)
+        return {"ncells": ncells, "ncarried": ncarried}
+
+    def features_match(self, keepA, keepB, reach=0, dj=0, di=0, maxpair=1 << 20):
+        """The features of the kept maps keepA and keepB that meet (an extra the reference does not have; sitrk_features_match):
+        {"pairs": (rows, 3) int64 rows (a, b, count) in ascending (a, b), "npair", "nhit"} as sit.MatchLabels gives them."""
+        from .features import check_keep, check_match_args
+        cerr = 'ERROR [IceTracker.features_match()]: '
+        reach, dj, di, maxpair = check_match_args(reach, dj, di, maxpair, cerr)
+        keepA, keepB = check_keep(keepA, "keepA", cerr), check_keep(keepB, "keepB", cerr)
+        return self.ctx.features_match(keepA, keepB, reach=reach, dj=dj, di=di, maxpair=maxpair)
 
     def mesh_free(self, slot=0):
         self.ctx.mesh_free(slot)

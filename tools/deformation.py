@@ -2,7 +2,7 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]]]]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]] [--track [REACH]]]]
                                 [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
@@ -22,6 +22,12 @@ mask -- the pixels with an owner whose rate passes the threshold: WHAT = div (di
 neighbours, default 8) of at least MINPIX pixels (default 1) are labelled on the GPU: OUT then holds `features` (rows, 12)
 int64 -- label, npix, jmin, jmax, imin, imax, the sums of j, i, j^2, i^2, j*i, the perimeter --, `features_counts` = (nfeat,
 ncomp, nactive) and `features_arg` = (what, sgn, thr, min_pix, conn).
+`--track [REACH]` with --features links those features to the ones of the next window of as many records, K1 -> K2 = K1 + (K1 - K0),
+for the same cells: the labels are carried to record K1 by their own cells -- a cell takes the lowest label
+among the pixels it owns at K0 and gives it to the pixels it owns at K1, here in numpy --, the next window's map is drawn at K1
+on the same grid, and the two are matched on the GPU within REACH pixels (0..2, default 1; sitrk_features_match).  OUT then
+holds `next_features`, `pairs` (npair, 3) -- label, label in the next window, pixels where they meet --, `pairs_counts` =
+(npair, nhit), `parent` per row of next_features and `child` per row of features (sit.link_features) and `track_arg` = (reach, K2).
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -83,8 +89,21 @@ def main(argv=None):
     ap.add_argument('--features', default=None, metavar='WHAT@THR[@MINPIX[@CONN]]',
                     help='with --grid: also label the connected features of the map where the rate WHAT (div, conv, shr, vor, tot) passes '
                          'THR [1/s] (`features`, `features_counts`, `features_arg` in the output)')
+    ap.add_argument('--track', nargs='?', const='1', default=None, metavar='REACH',
+                    help='with --features: also link the features to those of the next window of as many records, K1 -> K1 + (K1 - K0), '
+                         'within REACH pixels (0..2, default 1) (`next_features`, `pairs`, `pairs_counts`, `parent`, `child`, '
+                         '`track_arg` in the output)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
+    reach = None
+    if a.track is not None:
+        from sitrack_amd.features import track_arg
+        if a.features is None:
+            sys.exit('ERROR: --track: it links the features of --features; give that flag too')
+        try:
+            reach = track_arg(a.track, '--track')
+        except ValueError as e:
+            sys.exit('ERROR: %s' % e)
     feat = None
     if a.features is not None:
         from sitrack_amd.features import features_arg
@@ -125,6 +144,14 @@ def main(argv=None):
         has_mask = f.has_var('mask')
         yx0, ok0 = _record(f, k0, has_mask)
         yx1, ok1 = _record(f, k1, has_mask)
+        if reach is not None:
+            k2 = k1 + (k1 - k0)
+            if not k1 < k2 < nrec:
+                sys.exit('ERROR: --track: the next window ends at record %d, outside the %d records of %s' % (k2, nrec, a.fin))
+            yx2, ok2 = _record(f, k2, has_mask)
+            T2 = float(vtime[k2] - vtime[k1])
+            if not T2 > 0.:
+                sys.exit('ERROR: --track: record %d (time %d) is not later than record %d (time %d)' % (k2, vtime[k2], k1, vtime[k1]))
     if a.cells == 'auto':
         cols = _auto_cells(yx0, ok0 & ok1)
         cell_ids = ids[cols]
@@ -162,17 +189,33 @@ def main(argv=None):
                 if grid[3] > 32768 or grid[4] > 32768:
                     sys.exit('ERROR: --features: %g km over the points is %d x %d pixels, more than 32768 a side' % (a.grid, grid[3], grid[4]))
                 what, sgn, thr, min_pix, conn = feat
-                own = r['owner']
-                at = np.maximum(own, 0)
-                with np.errstate(invalid='ignore'):
-                    if what == 'tot':
-                        hit = r['div'][at] * r['div'][at] + r['shr'][at] * r['shr'][at] >= thr * thr
-                    else:
-                        hit = sgn * r[what][at] >= thr
-                rf = sit.LabelRaster((own >= 0) & hit, conn=conn, min_pix=min_pix, ctx=ctx)
+
+                def labelled(rates, own):
+                    at = np.maximum(own, 0)
+                    with np.errstate(invalid='ignore'):
+                        if what == 'tot':
+                            hit = rates['div'][at] * rates['div'][at] + rates['shr'][at] * rates['shr'][at] >= thr * thr
+                        else:
+                            hit = sgn * rates[what][at] >= thr
+                    return sit.LabelRaster((own >= 0) & hit, conn=conn, min_pix=min_pix, ctx=ctx)
+
+                rf = labelled(r, r['owner'])
                 r['features'] = rf['table']
                 r['features_counts'] = np.array([rf['nfeat'], rf['ncomp'], rf['nactive']], dtype=np.int64)
                 r['features_arg'] = np.array([sit.FEAT_WHAT[what], sgn, thr, min_pix, conn], dtype=np.float64)
+                if reach is not None:
+                    # the features carried by their own cells to record K1, where the next window's map is drawn on the same grid
+                    from sitrack_amd import features as ft
+                    own1 = sit.RasterCells(yx1, cols, grid, draw=r['valid'], ctx=ctx)
+                    carried, _ = ft.advect_labels(ft.kept_labels(rf['labels'], min_pix), r['owner'], own1, len(cols))
+                    rn = sit.DeformCells(yx1, yx2, cols, T2, mask0=ok1, mask1=ok2, ctx=ctx)
+                    rfn = labelled(rn, sit.RasterCells(yx1, cols, grid, draw=rn['valid'], ctx=ctx))
+                    m = sit.MatchLabels(carried, ft.kept_labels(rfn['labels'], min_pix), reach=reach, ctx=ctx)
+                    link = ft.link_features(m['pairs'], rf['table'], rfn['table'])
+                    r['next_features'], r['pairs'] = rfn['table'], m['pairs']
+                    r['pairs_counts'] = np.array([m['npair'], m['nhit']], dtype=np.int64)
+                    r['parent'], r['child'], r['track_arg'] = link['parent'], link['child'], np.array([reach, k2], dtype=np.int64)
+                    events = ft.track_events(link, *ft.feature_tracks([link], [len(rf['table']), len(rfn['table'])])[0])
     finally:
         ctx.close()
     fout = a.fout or os.path.splitext(a.fin)[0] + '_deform.npz'
@@ -189,6 +232,9 @@ def main(argv=None):
         lengths = sit.feature_table(r['features'], tuple(r['grid'][:3]) + (r['owner'].shape[0], r['owner'].shape[1]))['length_km']
         print(' *** --features %s: %d features of >= %d pixels (%d components, %d active pixels), longest %s'
               % (a.features, n[0], feat[3], n[1], n[2], '%.3f km' % lengths.max() if len(lengths) else 'n/a'))
+    if reach is not None:
+        print(' *** --track %d: records %d -> %d against %d -> %d: %d pairs, %d continued, %d born, %d ended, %d merged, %d split'
+              % ((reach, k0, k1, k1, k2, r['pairs_counts'][0]) + events))
     return 0
 
 
