@@ -4,6 +4,7 @@ on inputs with known answers, the masks those tests use, sit.feature_table on sh
 known, and the parser of --deform-features."""
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -148,6 +149,110 @@ def random_mask(ny, nx, density, seed):
     return (np.random.default_rng(seed).random((ny, nx)) < density).astype(np.int8)
 
 
+def interleaved_combs(ny, nx):
+    """two combs that mesh: a spine along row 0 with a tooth down every fourth column, a spine along the last row with a tooth up
+    the columns half way between, every tooth two rows short of the other spine.  Two components of nearly equal size, at conn 4
+    and at conn 8, whose pixels alternate along every row between the spines"""
+    assert ny >= 5 and nx >= 3
+    m = np.zeros((ny, nx), dtype=np.int8)
+    m[0] = m[ny - 1] = 1
+    m[:ny - 2, 0::4] = 1
+    m[2:, 2::4] = 1
+    return m
+
+
+def interleaved_labels(ny, nx):
+    """(labels, [npix of the upper comb, npix of the lower]) of interleaved_combs in closed form: the upper comb is component 0,
+    the lower one is named by the top of its first tooth, (2, 2)"""
+    assert ny >= 5 and nx >= 3
+    lab = np.full((ny, nx), -1, dtype=np.int32)
+    lab[0] = 0
+    lab[:ny - 2, 0::4] = 0
+    lab[ny - 1] = 2 * nx + 2
+    lab[2:, 2::4] = 2 * nx + 2
+    return lab, [nx + (ny - 3) * ((nx + 3) // 4), nx + (ny - 3) * ((nx + 1) // 4)]
+
+
+def full_row(ny, nx):
+    """the table row of a raster that is one component, in closed form"""
+    sj, si = ny * (ny - 1) // 2, nx * (nx - 1) // 2
+    return [0, ny * nx, 0, ny - 1, 0, nx - 1, nx * sj, ny * si, nx * ((ny - 1) * ny * (2 * ny - 1) // 6),
+            ny * ((nx - 1) * nx * (2 * nx - 1) // 6), sj * si, 2 * (ny + nx)]
+
+
+def bars(ny, nx):
+    """the rows j with j % 3 != 2: bars of two whole rows, and a last one of one row where ny % 3 == 1"""
+    m = np.zeros((ny, nx), dtype=np.int8)
+    m[np.arange(ny) % 3 != 2] = 1
+    return m
+
+
+def bars_expected(ny, nx):
+    """(labels, table) of bars(ny, nx) in closed form, at conn 4 and 8 alike: bar k is rows 3k .. 3k + h - 1, h = 2 or, for a
+    last bar cut by the rim, 1; its label is 3k * nx and every column of its row is a polynomial in k, h, nx"""
+    k = np.arange((ny + 2) // 3, dtype=np.int64)
+    j0 = 3 * k
+    h = np.minimum(2, ny - j0)
+    sj, sjj = h * j0 + (h - 1), h * j0 * j0 + (h - 1) * (2 * j0 + 1)  # over the bar's rows: j0 (+ j0 + 1), and the squares
+    si, sii = nx * (nx - 1) // 2, (nx - 1) * nx * (2 * nx - 1) // 6    # over a row's columns
+    one = np.ones_like(k)
+    table = np.stack([j0 * nx, h * nx, j0, j0 + h - 1, 0 * one, (nx - 1) * one, nx * sj, h * si, nx * sjj, h * sii, sj * si,
+                      2 * nx + 2 * h], axis=1).astype(np.int64)
+    j = np.arange(ny)
+    rows = np.where(j % 3 != 2, (j // 3) * 3 * nx, -1).astype(np.int32)
+    labels = np.repeat(rows[:, None], nx, axis=1)
+    return labels, table
+
+
+# ------------------------------------------------------------------------------------------------ rasters of a production size
+# The kernels of sitrk_label.hip and sitrk_track.hip size their launches on the host from a handful of constants, and take other
+# paths on a large raster than on a small one: more than one grid-stride trip, spans of more than kLbMinTrips pieces, borders of
+# more than one merge trip.  The three shapes below are the smallest that reach those paths with ragged ends everywhere;
+# test_the_large_shapes_reach_the_paths_they_are_for recomputes the launches from the source's own constants, so that a retuned
+# constant fails a test instead of taking the coverage away.
+TRIP2 = (727, 733)       # 2 grid-stride trips (the second of 8603 pixels), 4 merge levels both ways, borders of 2-3 merge trips
+SPAN5 = (1461, 1459)     # spans of 5 pieces, the last wave with 2; 5 grid-stride trips; 5 merge levels; 44-bit sort keys
+DEEP = (4099, 4201)      # spans of 33 pieces, shorter than a row; 7 merge levels; closed-form masks only
+
+
+def kernel_constants():
+    """the launch constants of the two sources, read from their text: name -> int"""
+    out = {}
+    for fn, names in (("sitrk_label.hip", ("kLbFlagBlocks", "kLbSpanWaves", "kLbMinTrips", "kLbThreads")),
+                      ("sitrk_track.hip", ("kTrBlocks", "kTrThreads"))):
+        src = open(os.path.join(ROOT, "sitrack_amd", "csrc", fn)).read()
+        for name in names:
+            found = re.findall(r"constexpr\s+[\w\s]+?\b%s\s*=\s*(\d+(?:\s*\*\s*\d+)*)\s*;" % name, src)
+            assert len(found) == 1, (fn, name, found)
+            out[name] = math.prod(int(f) for f in found[0].split("*"))
+    return out
+
+
+def launch_shape(ny, nx, c, tile=64):
+    """what the host of label_run / Strided / sitrk_features_match derives for a raster, restated from their formulas"""
+    npix = ny * nx
+    up = lambda a, b: -(-a // b)
+
+    def strided(blocks_max, threads):                                  # (trips, pixels of the last trip)
+        blocks = max(1, min(up(npix, threads), blocks_max))
+        trips = up(npix, blocks * threads)
+        return trips, npix - (trips - 1) * blocks * threads
+
+    def merge(n):                                                      # (levels, merge trips of the longest border) along one side
+        halves = [tile << k for k in range(16) if (tile << k) < n]
+        return len(halves), max([up(min(2 * h, n), c["kLbThreads"]) for h in halves], default=0)
+
+    pieces = up(npix, 64)
+    wtrips = max(up(pieces, c["kLbSpanWaves"]), c["kLbMinTrips"])
+    waves = up(pieces, wtrips)
+    nb = 1
+    while (1 << nb) < npix:
+        nb += 1
+    return {"npix": npix, "flag": strided(c["kLbFlagBlocks"], c["kLbThreads"]), "strided": strided(c["kTrBlocks"], c["kTrThreads"]),
+            "wtrips": wtrips, "waves": waves, "last_wave_pieces": pieces - (waves - 1) * wtrips, "last_piece_pixels": npix - (pieces - 1) * 64,
+            "merge_j": merge(ny), "merge_i": merge(nx), "nb": nb}
+
+
 def same_result(got, want_labels, min_pix=1, maxfeat=None, what=""):
     """a result dict of the binding against the restatement on the expected labels: labels (when returned), table, counts"""
     tab, ncomp, nact = table_ref(want_labels, min_pix)
@@ -246,6 +351,78 @@ def test_scipy_agrees_where_it_is_installed():
             assert n == table_ref(mine)[1]
             for k in range(1, n + 1):
                 assert len(np.unique(mine[lab == k])) == 1 and mine[lab == k][0] == np.flatnonzero((lab == k).ravel())[0]
+
+
+def test_interleaved_combs_are_two_components_of_known_sizes():
+    for ny, nx in ((5, 3), (6, 4), (9, 13), (31, 66), (67, 131), (40, 257)):
+        m = interleaved_combs(ny, nx)
+        want, sizes = interleaved_labels(ny, nx)
+        assert np.array_equal(want >= 0, m != 0) and m.sum() == sum(sizes) and abs(sizes[0] - sizes[1]) <= ny - 3, (ny, nx)
+        for conn in (4, 8):
+            lab = label_ref(m, conn)
+            t, ncomp, nact = table_ref(lab)
+            assert np.array_equal(lab, want), (ny, nx, conn)
+            assert ncomp == 2 and t[:, 0].tolist() == [0, 2 * nx + 2] and t[:, 1].tolist() == sizes and nact == sum(sizes), (ny, nx, conn)
+            assert t[:, 2:6].tolist() == [[0, ny - 3, 0, nx - 1], [2, ny - 1, 0, nx - 1]]
+        # between the spines the two alternate along every row: no two pixels of one comb follow each other
+        inner = want[2:ny - 2]
+        assert (inner[:, 0::4] == 0).all() and (inner[:, 2::4] == 2 * nx + 2).all() and (inner[:, 1::2] == -1).all()
+    ndi = pytest.importorskip("scipy.ndimage")
+    for conn, st in ((4, None), (8, np.ones((3, 3)))):
+        lab, n = ndi.label(interleaved_combs(67, 131), structure=st)
+        want, sizes = interleaved_labels(67, 131)
+        assert n == 2 and np.array_equal(lab == 1, want == 0) and np.array_equal(lab == 2, want == 2 * 131 + 2)
+        assert np.bincount(lab.ravel())[1:].tolist() == sizes
+
+
+def test_closed_forms_of_the_full_raster_and_of_the_bars():
+    for ny, nx in ((1, 1), (3, 8), (7, 5), (66, 131)):
+        assert table_ref(label_ref(np.ones((ny, nx)), 4))[0].tolist() == [full_row(ny, nx)], (ny, nx)
+    for ny, nx in ((1, 1), (2, 3), (3, 1), (6, 5), (7, 5), (8, 5), (67, 131), (130, 70)):  # ny % 3 = 0, 1, 2: no, a short, a whole last bar
+        m = bars(ny, nx)
+        labels, table = bars_expected(ny, nx)
+        assert labels.dtype == np.int32 and table.dtype == np.int64 and table.shape == ((ny + 2) // 3, 12)
+        for conn in (4, 8):
+            lab = label_ref(m, conn)
+            assert np.array_equal(lab, labels), (ny, nx, conn)
+            t, ncomp, nact = table_ref(lab)
+            assert np.array_equal(t, table) and ncomp == len(table) and nact == m.sum() == table[:, 1].sum(), (ny, nx, conn)
+        assert (table[-1, 1] == nx) == (ny % 3 == 1)
+
+
+def test_the_large_shapes_reach_the_paths_they_are_for():
+    """TRIP2, SPAN5 and DEEP against the constants as the sources have them now.  If this fails after a constant was retuned, the
+    shapes have to follow it: the GPU tests that use them would still pass, on paths they were not written for."""
+    c = kernel_constants()
+    assert c["kLbThreads"] % 64 == 0 and c["kTrThreads"] % 64 == 0 and _lib.LABEL_TILE == 64
+    s = {name: launch_shape(ny, nx, c) for name, (ny, nx) in (("TRIP2", TRIP2), ("SPAN5", SPAN5), ("DEEP", DEEP))}
+    for name, (ny, nx) in (("TRIP2", TRIP2), ("SPAN5", SPAN5), ("DEEP", DEEP)):
+        v = s[name]
+        assert ny % 2 == 1 and nx % 2 == 1 and ny != nx and v["npix"] % 64 != 0 and v["npix"] <= 1 << 28, (name, v)
+        assert v["npix"] % c["kLbThreads"] != 0 and v["npix"] % c["kTrThreads"] != 0, (name, v)   # a ragged last workgroup
+        for trips, last in (v["flag"], v["strided"]):                  # more than one grid-stride trip, the last one not whole
+            assert trips >= 2 and 0 < last < v["npix"] // trips, (name, v)
+        assert 1 <= v["last_wave_pieces"] < v["wtrips"] and 0 < v["last_piece_pixels"] < 64, (name, v)
+        for levels, border_trips in (v["merge_j"], v["merge_i"]):      # a merge border of more than one trip, both ways
+            assert levels >= 4 and border_trips >= 2, (name, v)
+        assert 2 * v["nb"] > 34, (name, v)                             # wider sort keys than the small rasters have
+    # TRIP2 is the raster of two trips and spans of the least length; SPAN5 and DEEP have longer spans, DEEP's shorter than a row
+    assert s["TRIP2"]["flag"][0] == 2 and s["TRIP2"]["strided"][0] == 2 and s["TRIP2"]["wtrips"] == c["kLbMinTrips"]
+    assert s["TRIP2"]["merge_j"][1] >= 3 and s["TRIP2"]["merge_i"][1] >= 3
+    assert c["kLbMinTrips"] < s["SPAN5"]["wtrips"] < s["DEEP"]["wtrips"] and 64 * s["DEEP"]["wtrips"] < DEEP[1]
+    assert s["SPAN5"]["flag"][0] > 2 and s["SPAN5"]["merge_j"][0] > s["TRIP2"]["merge_j"][0] and s["DEEP"]["merge_j"][0] > s["SPAN5"]["merge_j"][0]
+    assert s["TRIP2"]["nb"] < s["SPAN5"]["nb"] < s["DEEP"]["nb"]
+    # the small shapes of the GPU tests stay below every one of these thresholds: one trip, the least span
+    for ny, nx in ((1, 1), (1, 300), (63, 65), (67, 131), (200, 333), (3, 517), (32768, 1)):
+        v = launch_shape(ny, nx, c)
+        assert v["flag"][0] == 1 and v["strided"][0] == 1 and v["wtrips"] == c["kLbMinTrips"], (ny, nx, v)
+    # with the constants as they are today, the figures the three shapes were chosen for
+    if (c["kLbFlagBlocks"], c["kLbSpanWaves"], c["kLbMinTrips"], c["kLbThreads"], c["kTrBlocks"], c["kTrThreads"]) == (2048, 8192, 4, 256, 2048, 256):
+        assert s["TRIP2"] == {"npix": 532891, "flag": (2, 8603), "strided": (2, 8603), "wtrips": 4, "waves": 2082, "last_wave_pieces": 3,
+                              "last_piece_pixels": 27, "merge_j": (4, 3), "merge_i": (4, 3), "nb": 20}
+        assert s["SPAN5"] == {"npix": 2131599, "flag": (5, 34447), "strided": (5, 34447), "wtrips": 5, "waves": 6662, "last_wave_pieces": 2,
+                              "last_piece_pixels": 15, "merge_j": (5, 6), "merge_i": (5, 6), "nb": 22}
+        assert (s["DEEP"]["npix"], s["DEEP"]["wtrips"], s["DEEP"]["merge_j"][0], s["DEEP"]["merge_i"][0], s["DEEP"]["nb"]) == (17219899, 33, 7, 7, 25)
 
 
 # ------------------------------------------------------------------------------------------------ feature_table

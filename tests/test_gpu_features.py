@@ -3,7 +3,9 @@ tests/test_features.py.  All integer: every comparison is array_equal, there is 
 smallest at which each phase can go wrong -- one pixel, one row, a tile less and more than a tile, partial tiles on both rims
 with three merge levels, many tiles long and less than one high -- and the masks the worst cases for propagation: a one-pixel
 serpentine through every row, a comb, a spiral, diagonals that are dust at conn 4, and random masks near the two percolation
-thresholds."""
+thresholds.  Those rasters all fit one grid-stride trip and spans of the least length; the tests on TRIP2, SPAN5 and DEEP
+(tests/test_features.py) take the same masks, and two combs that mesh, to the sizes at which the host gives the kernels several
+trips, longer spans, merge borders of more than one trip and seven merge levels both ways."""
 import ctypes as C
 import functools
 import os
@@ -16,7 +18,8 @@ import sitrack_amd as sit
 from sitrack_amd import _lib
 from sitrack_amd import driver as drv
 from test_driver import make_case
-from test_features import (checkerboard, comb, diagonals, label_ref, random_mask, same_result, serpentine, spiral, table_ref)
+from test_features import (DEEP, SPAN5, TRIP2, bars, bars_expected, checkerboard, comb, diagonals, full_row, interleaved_combs,
+                           interleaved_labels, label_ref, random_mask, same_result, serpentine, spiral, table_ref)
 from test_gpu_mesh import JREC0, K, advance, start
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +77,8 @@ def make_mask(kind, ny, nx):
         m = spiral(ny, nx, cut=wind)
     elif kind == "diagonals":
         m = diagonals(ny, nx)
+    elif kind == "interleaved":
+        m = interleaved_combs(ny, nx)
     else:
         density, seed = kind
         m = random_mask(ny, nx, density, seed)
@@ -143,6 +148,70 @@ def test_random_masks_near_the_percolation_thresholds(ctx, ny, nx):
                 big = tab[np.argmax(tab[:, 1])]
                 tiles = {(j // T, i // T) for j, i in zip(*np.nonzero(lab == big[0]))}
                 assert len(tab) > 100 and len(tiles) > 4, (kind, conn, len(tab), len(tiles))
+
+
+# ------------------------------------------------------------------------------------------------ rasters of a production size
+# TRIP2 and SPAN5 (tests/test_features.py, where a CPU test holds them to the constants of the source) are past the sizes at
+# which the host gives the kernels more than one grid-stride trip, spans of more than kLbMinTrips pieces and merge borders of
+# more than one trip; the shapes above are all below them.  The same check_case, the same restatement, array_equal only.
+LARGE = (TRIP2, SPAN5)
+
+
+@pytest.mark.parametrize("density,conn", [(0.41, 8), (0.59, 4)])
+@pytest.mark.parametrize("ny,nx", LARGE)
+def test_random_masks_on_large_rasters(ctx, ny, nx, density, conn):
+    """near the percolation threshold of the connectivity: tens of thousands of components, the largest over most of the raster"""
+    kind = (density, 1)
+    tab = check_case(ctx, kind, ny, nx, conn)
+    lab = want_labels(kind, ny, nx, conn)
+    big = tab[np.argmax(tab[:, 1])]
+    jj, ii = np.nonzero(lab == big[0])
+    tiles = len(np.unique((jj // T) * (nx // T + 1) + ii // T))
+    # 10 000 components and 100 tiles at SPAN5, as measured on the restatement with room to spare (29 021 and 61 327 components,
+    # 347 and 206 tiles); both scale with the area, and TRIP2 has a quarter of it
+    scale = (ny * nx) / (SPAN5[0] * SPAN5[1])
+    assert len(tab) > 10000 * scale and tiles > 100 * scale, (kind, conn, len(tab), tiles)
+
+
+# (the comb has a million runs at SPAN5, and its restatement takes too long there: it runs at TRIP2)
+WINDING_LARGE = [(s, k) for s in LARGE for k in ("serpentine", "spiral", "interleaved")] + [(TRIP2, "comb"), (TRIP2, "comb_cut")]
+
+
+@pytest.mark.parametrize("conn", [4, 8])
+@pytest.mark.parametrize("shape,kind", WINDING_LARGE, ids=["%dx%d-%s" % (s + (k,)) for s, k in WINDING_LARGE])
+def test_winding_masks_on_large_rasters(ctx, shape, kind, conn):
+    """one component through every tile -- the longest parent chains the merge can leave --, and two that alternate along every
+    row, so that in every piece of every span the flatten and table kernels choose which of two rows stays in registers"""
+    ny, nx = shape
+    tab = check_case(ctx, kind, ny, nx, conn)
+    if kind == "interleaved":
+        lab, sizes = interleaved_labels(ny, nx)
+        assert np.array_equal(want_labels(kind, ny, nx, conn), lab) and tab[:, :2].tolist() == [[0, sizes[0]], [2 * nx + 2, sizes[1]]]
+    elif kind == "comb_cut":
+        assert len(tab) == 2 and make_mask(kind, ny, nx).sum() == make_mask("comb", ny, nx).sum() - 1
+    else:
+        assert len(tab) == 1 and tab[0, 1] == make_mask(kind, ny, nx).sum() and tab[0, 2:6].tolist() == [0, ny - 1, 0, nx - 1]
+
+
+def test_closed_form_masks_on_the_deepest_raster(ctx):
+    """DEEP: spans of 33 pieces that end inside a row, seven merge levels both ways, 33 grid-stride trips.  Expected values in
+    closed form (their formulas are checked against the restatement on small rasters in tests/test_features.py)"""
+    ny, nx = DEEP
+    whole = np.ones((ny, nx), dtype=np.int8)
+    striped = bars(ny, nx)
+    labels, table = bars_expected(ny, nx)
+    assert len(table) == 1367 and table[-1, 1] == nx and striped.sum() == table[:, 1].sum()      # the last bar is one row
+    for conn in (4, 8):
+        got = ctx.label_raster(whole, conn=conn)
+        assert got["table"].tolist() == [full_row(ny, nx)] and (got["nfeat"], got["ncomp"], got["nactive"]) == (1, 1, ny * nx), conn
+        assert got["labels"].dtype == np.int32 and not got["labels"].any(), conn
+        got = ctx.label_raster(striped, conn=conn)
+        assert got["table"].dtype == np.int64 and np.array_equal(got["table"], table), conn
+        assert (got["nfeat"], got["ncomp"], got["nactive"]) == (len(table), len(table), int(table[:, 1].sum())), conn
+        assert got["labels"].dtype == np.int32 and np.array_equal(got["labels"], labels), conn
+        bare = ctx.label_raster(striped, conn=conn, min_pix=nx + 1, maxfeat=1000, labels=False)   # without the short bar, truncated
+        assert bare["labels"] is None and np.array_equal(bare["table"], table[:1000]), conn
+        assert (bare["nfeat"], bare["ncomp"], bare["nactive"]) == (len(table) - 1, len(table), int(table[:, 1].sum())), conn
 
 
 def test_longest_sides(ctx):

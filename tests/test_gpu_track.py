@@ -1,7 +1,9 @@
 """Features from window to window on the GPU (sitrk_mesh_features_keep / sitrk_keep_* / sitrk_mesh_features_advect /
 sitrk_features_match) against the restatements of tests/test_track.py.  All integer: every comparison is
 array_equal, there is no tolerance anywhere.  The rasters are those of tests/test_gpu_features.py -- one pixel, one row, around a
-tile, partial tiles, many tiles long --, the maps the labels of its masks, and the mesh that of tests/test_gpu_mesh.py."""
+tile, partial tiles, many tiles long --, the maps the labels of its masks, and the mesh that of tests/test_gpu_mesh.py.  Every
+kernel launched through `Strided` takes one trip on those; the tests on TRIP2 and SPAN5 (tests/test_features.py) give it two and
+five, and sort keys of 40 and 44 bits."""
 import ctypes as C
 import functools
 import os
@@ -14,7 +16,9 @@ import sitrack_amd as sit
 from sitrack_amd import _lib
 from sitrack_amd import driver as drv
 from test_driver import make_case
-from test_features import checkerboard, comb, label_ref, random_mask, serpentine, table_ref
+from test_features import (SPAN5, TRIP2, checkerboard, comb, kernel_constants, label_ref, launch_shape, random_mask, same_result,
+                           serpentine, table_ref)
+from test_gpu_features import want_labels
 from test_gpu_mesh import JREC0, K, advance, start
 from test_track import advect_ref, kept_ref, match_ref, permuted
 
@@ -142,7 +146,124 @@ def test_match_forms_of_the_call(ctx):
         ctx.keep_free(slot)
 
 
+# ------------------------------------------------------------------------------------------------ match, on large rasters
+# TRIP2 and SPAN5 of tests/test_features.py: more than one trip of every kernel that `Strided` launches, and keys of 40 and 44
+# bits where the rasters above stop at 34.  The maps are the labels of the random masks of tests/test_gpu_features.py (from its
+# cache: each is restated once for both files) and copies under other names, whose values use all of [0, npix) and so every bit
+# of the nb that the keys are packed and unpacked with.
+@functools.lru_cache(maxsize=None)
+def large_maps(ny, nx):
+    lo, hi = want_labels((0.41, 1), ny, nx, 8), want_labels((0.59, 1), ny, nx, 4)
+    out = [("random 0.41/8 against 0.59/4", lo, hi), ("not canonical", permuted(lo, 11), permuted(hi, 12))]
+    for _, a, b in out:
+        a.setflags(write=False)
+        b.setflags(write=False)
+    assert max(int(m.max()).bit_length() for m in out[1][1:]) == (ny * nx - 1).bit_length()           # the top bit is used
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def want_large_match(ny, nx, k, reach, dj, di):
+    _, a, b = large_maps(ny, nx)[k]
+    return match_ref(a, b, reach, dj, di)
+
+
+def check_match(ctx, ny, nx, k, reach, dj, di):
+    """slots 0 and 1 hold the maps k of the raster: one call against the restatement; returns its pairs"""
+    pairs, nhit = want_large_match(ny, nx, k, reach, dj, di)
+    got = ctx.features_match(0, 1, reach=reach, dj=dj, di=di)
+    what = (ny, nx, k, reach, dj, di, got["npair"], len(pairs), got["nhit"], nhit)
+    assert got["pairs"].dtype == np.int64 and got["pairs"].shape == pairs.shape and np.array_equal(got["pairs"], pairs), what
+    assert (got["npair"], got["nhit"]) == (len(pairs), nhit), what
+    return pairs
+
+
+@pytest.mark.parametrize("reach", REACHES)
+@pytest.mark.parametrize("k", [0, 1])
+def test_match_on_a_raster_of_two_trips(ctx, k, reach):
+    ny, nx = TRIP2
+    _, a, b = large_maps(ny, nx)[k]
+    ctx.keep_put(0, a)
+    ctx.keep_put(1, b)
+    for dj, di in ((0, 0), (1, -2), (-ny, 0)):
+        pairs = check_match(ctx, ny, nx, k, reach, dj, di)
+        if dj == -ny:                                                  # outside the raster, but for the last rows of A within the reach
+            assert (len(pairs) == 0) == (reach == 0), (k, reach, len(pairs))
+        else:
+            assert len(pairs) > 10000, (k, reach, dj, di, len(pairs))
+    ctx.keep_free(0)
+    ctx.keep_free(1)
+
+
+@pytest.mark.parametrize("reach", [0, 2])
+@pytest.mark.parametrize("k", [0, 1])
+def test_match_on_a_raster_of_five_trips(ctx, k, reach):
+    ny, nx = SPAN5
+    _, a, b = large_maps(ny, nx)[k]
+    ctx.keep_put(0, a)
+    ctx.keep_put(1, b)
+    pairs = check_match(ctx, ny, nx, k, reach, 1, -2)
+    assert len(pairs) > 50000 and pairs[:, 2].sum() > 500000, (k, reach, len(pairs))      # tens of thousands of rows from 10^5..10^6 keys
+    if k == 1:
+        assert int(pairs[:, :2].max()).bit_length() == (ny * nx - 1).bit_length()
+    if reach == 2:                                                     # truncated: the first rows only, the rest of the buffer untouched
+        lib, h, p = ctx._L, ctx._h, _lib._ptr
+        nhit = want_large_match(ny, nx, k, reach, 1, -2)[1]
+        cut = len(pairs) // 3
+        buf = np.full((cut + 3, 3), 77, dtype=np.int64)
+        np_, nh = _lib._i64(-5), _lib._i64(-5)
+        assert lib.sitrk_features_match(h, 0, 1, 1, -2, reach, cut, p(buf), C.byref(np_), C.byref(nh)) == 0
+        assert np.array_equal(buf[:cut], pairs[:cut]) and (buf[cut:] == 77).all() and (np_.value, nh.value) == (len(pairs), nhit)
+    ctx.keep_free(0)
+    ctx.keep_free(1)
+
+
+def test_keep_put_counts_the_bad_values_of_every_trip(ctx):
+    """keep_range_kernel carries a wave's count from trip to trip: values outside [-1, npix) at the first and the last pixel of each
+    of the two trips of TRIP2 are all counted, and the slot stays what it was"""
+    ny, nx = TRIP2
+    npix = ny * nx
+    good = large_maps(ny, nx)[1][1]
+    ctx.keep_put(2, good, conn=4, min_pix=3)
+    c = kernel_constants()
+    first = c["kTrThreads"] * c["kTrBlocks"]                           # the first pixel of the second trip
+    assert first < npix - 1 < 2 * first
+    for where, values in (((0, first - 1, first, npix - 1), (npix, -2, npix + 7, -2 ** 31)), ((first,), (npix,)), ((npix - 1,), (2 ** 31 - 1,))):
+        bad = good.copy().reshape(-1)
+        bad[list(where)] = values
+        with pytest.raises(IndexError, match=r"%d value\(s\) of the map lie outside \[-1, %d\)" % (len(where), npix)):
+            ctx.keep_put(2, bad.reshape(ny, nx))
+    edge = good.copy().reshape(-1)                                     # the largest and the smallest value that pass, at the same pixels
+    edge[[0, first - 1, first, npix - 1]] = (npix - 1, -1, npix - 1, -1)
+    ctx.keep_put(3, edge.reshape(ny, nx))
+    assert np.array_equal(ctx.keep_get(3)["labels"].reshape(-1), edge)
+    k = ctx.keep_get(2)
+    assert (k["shape"], k["conn"], k["min_pix"]) == ((ny, nx), 4, 3) and np.array_equal(k["labels"], good)
+    ctx.keep_free(2)
+    ctx.keep_free(3)
+
+
+def test_self_match_on_a_raster_of_five_trips(ctx):
+    ny, nx = SPAN5
+    for k, (_, _, b) in enumerate(large_maps(ny, nx)):                 # the labels at conn 4, and the same partition under other names
+        ctx.keep_put(0, b)
+        tab, _, nact = table_ref(b)
+        got = ctx.features_match(0, 0)
+        assert len(tab) > 50000 and got["npair"] == len(tab) and got["nhit"] == nact, k
+        assert np.array_equal(got["pairs"], np.stack([tab[:, 0], tab[:, 0], tab[:, 1]], axis=1)), k
+    ctx.keep_free(0)
+
+
 # ------------------------------------------------------------------------------------------------ keep
+def refined(grid, more_than):
+    """the grid over the extent of `grid` with pixels small enough for more than `more_than` of them, both sides odd"""
+    y0, x0, d, ny, nx = grid
+    f = 1.01 * float(np.sqrt(more_than / (ny * nx)))
+    fine = (y0, x0, d / f, int(np.ceil(ny * f)) | 1, int(np.ceil(nx * f)) | 1)
+    assert fine[3] * fine[4] > more_than and fine[3] % 2 == 1 and fine[4] % 2 == 1 and fine[3] != fine[4]
+    return fine
+
+
 def mesh_case():
     """the tracker of the mesh tests with a mesh of more than 256 cells advanced six records, a grid finer than its cells that
     it reaches beyond on two sides, and the threshold that half of the owned pixels pass, from the device's own rates"""
@@ -241,7 +362,63 @@ def test_keep_is_mesh_features_plus_the_kept_map():
         trk.close()
 
 
+def test_keep_on_a_raster_of_long_spans():
+    """the mesh path on more than 2^21 pixels: label_mask_kernel, the label pipeline with spans of five pieces on real rates, and
+    keep_labels_kernel"""
+    trk, jrec1, coarse, thr = mesh_case()
+    try:
+        ctx = trk.ctx
+        grid = refined(coarse, SPAN5[0] * SPAN5[1])
+        c = kernel_constants()
+        shape = launch_shape(grid[3], grid[4], c)
+        assert shape["wtrips"] > c["kLbMinTrips"] and shape["flag"][0] > 2 and shape["npix"] % 64 != 0, shape
+        kw = dict(what="tot", thr=thr, conn=4, labels=True)
+        want = trk.mesh_features(jrec1, grid, **kw)
+        got = trk.mesh_features(jrec1, grid, keep=3, **kw)
+        assert np.array_equal(got["labels"], want["labels"]) and np.array_equal(got["table"], want["table"])
+        assert all(got[n] == want[n] for n in ("nfeat", "ncomp", "nactive")) and want["ncomp"] == want["nfeat"] > 3
+        owner = trk.mesh_raster(jrec1, grid, fields=False)["owner"]
+        assert 0.3 < want["nactive"] / (owner >= 0).sum() < 0.7         # about half of the owned pixels pass
+        same_result(want, label_ref(want["labels"] >= 0, 4), what="the labels of the device's own mask")
+        k = ctx.keep_get(3)
+        assert (k["shape"], k["conn"], k["min_pix"]) == ((grid[3], grid[4]), 4, 1) and np.array_equal(k["labels"], want["labels"])
+        # a min_pix that drops half of the components, from the table itself
+        cut = int(np.sort(want["table"][:, 1])[len(want["table"]) // 2]) + 1
+        assert 1 < cut <= want["table"][:, 1].max()
+        bare = trk.mesh_features(jrec1, grid, what="tot", thr=thr, conn=4, min_pix=cut, keep=3)
+        kept = ctx.keep_get(3)
+        assert bare["labels"] is None and 0 < bare["nfeat"] < want["nfeat"] and kept["min_pix"] == cut
+        assert np.array_equal(kept["labels"], kept_ref(want["labels"], cut)) and 0 < (kept["labels"] >= 0).sum() < want["nactive"]
+    finally:
+        trk.close()
+
+
 # ------------------------------------------------------------------------------------------------ advect
+def test_advect_on_a_raster_of_two_trips():
+    trk, jrec1, coarse, thr = mesh_case()
+    try:
+        ctx = trk.ctx
+        nQ = len(trk.mesh_cells())
+        grid = refined(coarse, TRIP2[0] * TRIP2[1])
+        shape = launch_shape(grid[3], grid[4], kernel_constants())
+        assert shape["strided"][0] >= 2 and shape["npix"] % 64 != 0, shape
+        o0 =trk.mesh_raster(jrec1, grid, at="t0", fields=False)["owner"]
+        o1 = trk.mesh_raster(jrec1, grid, at="t1", fields=False)["owner"]
+        assert (o0 >= 0).any() and (o1 >= 0).any() and not np.array_equal(o0, o1)
+        f = trk.mesh_features(jrec1, grid, what="tot", thr=thr, min_pix=2, labels=True, keep=0)
+        L = ctx.keep_get(0)["labels"]
+        assert np.array_equal(L, kept_ref(f["labels"], 2)) and (L >= 0).any()
+        odd = np.random.default_rng(3).integers(-1, L.size, L.shape).astype(np.int32)       # any values of [-1, npix)
+        ctx.keep_put(7, odd, conn=4, min_pix=1)
+        for src, dst, m in ((0, 1, L), (7, 8, odd)):
+            M, ncells, ncarried = advect_ref(m, o0, o1, nQ)
+            assert trk.features_advect(jrec1, grid, src, dst) == {"ncells": ncells, "ncarried": ncarried}
+            assert np.array_equal(ctx.keep_get(dst)["labels"], M) and np.array_equal(ctx.keep_get(src)["labels"], m)
+            assert ncells > 50 and ncarried > 10000 and not np.array_equal(M, m)
+    finally:
+        trk.close()
+
+
 def test_advect_equals_the_restatement_on_the_downloaded_owners():
     trk, jrec1, fine, thr = mesh_case()
     try:
