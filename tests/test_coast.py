@@ -46,6 +46,26 @@ def coast_segments_ref(Yf, Xf, tmask):
     return np.array(ids, dtype=np.int32), np.array(ab, dtype=np.float64).reshape(-1, 2, 2), ndropped
 
 
+def coast_segments_vec(Yf, Xf, tmask):
+    """coast_segments_ref in whole-array numpy, for coasts too long for the loop: the same three values.  The loop form stays the
+    statement of the contract; this one is trusted only through test_vectorised_segments_equal_the_loop_form."""
+    Yf, Xf = np.asarray(Yf, dtype=np.float64), np.asarray(Xf, dtype=np.float64)
+    land = np.asarray(tmask) == 0
+    Nj, Ni = land.shape
+    coast = [np.zeros((Nj, Ni), dtype=bool), np.zeros((Nj, Ni), dtype=bool)]
+    coast[0][1:, :-1] = land[1:, :-1] != land[1:, 1:]         # k = 0: T(j,i) | T(j,i+1), j >= 1, from F(j-1,i)
+    coast[1][:-1, 1:] = land[:-1, 1:] != land[1:, 1:]         # k = 1: T(j,i) | T(j+1,i), i >= 1, from F(j,i-1)
+    ids, ab = [], []
+    for k, (dj, di) in enumerate(((1, 0), (0, 1))):
+        j, i = np.nonzero(coast[k])
+        ids.append(2 * (j * Ni + i) + k)
+        ab.append(np.stack([Yf[j - dj, i - di], Xf[j - dj, i - di], Yf[j, i], Xf[j, i]], axis=1).reshape(-1, 2, 2))
+    ids, ab = np.concatenate(ids), np.concatenate(ab)
+    fin = np.isfinite(ab).all(axis=(1, 2))
+    order = np.argsort(ids[fin], kind="stable")
+    return ids[fin][order].astype(np.int32), np.ascontiguousarray(ab[fin][order]), int((~fin).sum())
+
+
 def d2_ref(yx, ab):
     """d2 of every point (n,2) to every segment (m,2,2) -> (n,m): the contract's expression, one numpy operation per symbol
     (numpy rounds each once and fuses none)"""
@@ -61,9 +81,10 @@ def d2_ref(yx, ab):
     return cy * cy + cx * cx
 
 
-def coast_dist_ref(yx, ids, ab, rmax=None):
+def coast_dist_ref(yx, ids, ab, rmax=None, batch=512):
     """(d2min, seg, dist) by brute force over ALL segments: the minimum, the lowest id that attains it (ids ascend, argmin takes
-    the first), its numpy sqrt; rmax, no coast and non-finite queries as the header states them."""
+    the first), its numpy sqrt; rmax, no coast and non-finite queries as the header states them.  `batch` queries at a time: one
+    temporary is batch x len(ids) doubles."""
     yx = np.asarray(yx, dtype=np.float64)
     n = len(yx)
     d2min = np.full(n, np.inf); seg = np.full(n, -1, dtype=np.int32)
@@ -71,8 +92,8 @@ def coast_dist_ref(yx, ids, ab, rmax=None):
         return d2min, seg, d2min.copy()
     ok = np.isfinite(yx).all(axis=1)
     d2min[~ok] = np.nan
-    for b in range(0, n, 512):
-        sl = np.flatnonzero(ok[b:b + 512]) + b
+    for b in range(0, n, batch):
+        sl = np.flatnonzero(ok[b:b + batch]) + b
         if len(sl) == 0:
             continue
         d2 = d2_ref(yx[sl], ab)
@@ -90,6 +111,23 @@ def island_grid(Nj=24, Ni=28, dkm=4., warp=0.):
     g = syn.make_grid(Nj, Ni, dkm=dkm, warp=warp, rim=0)
     g["tmask"][10:13, 12:16] = 0
     return g
+
+
+def messy_grid(warp):
+    """24 x 28: an island, a one-cell island, land with a one-cell lake, a peninsula that reaches the rim, land along one rim row"""
+    g = syn.make_grid(24, 28, dkm=4., warp=warp, rim=0)
+    t = g["tmask"]
+    t[10:13, 12:16] = 0
+    t[4, 5] = 0
+    t[16:21, 18:24] = 0; t[18, 20] = 1
+    t[6:9, 0:6] = 0
+    t[-1, :] = 0
+    return g
+
+
+def checkerboard(Nj, Ni):
+    jj, ii = np.indices((Nj, Ni))
+    return ((jj + ii) % 2).astype(np.int8)
 
 
 # --------------------------------------------------------------------------- the restatement on hand-checkable values
@@ -119,6 +157,48 @@ def test_rim_is_no_coast_and_row_zero_has_no_k0_edges():
     assert len(coast_segments_ref(g["Yf"], g["Xf"], g["tmask"])[0]) == 0
     g["tmask"][:] = 1
     assert len(coast_segments_ref(g["Yf"], g["Xf"], g["tmask"])[0]) == 0
+
+
+def test_vectorised_segments_equal_the_loop_form():
+    cases = []
+    for warp in (0., 0.8):
+        g = messy_grid(warp)
+        cases.append((g["Yf"], g["Xf"], g["tmask"]))
+    g = syn.make_grid(24, 28, dkm=4., warp=0.8, rim=0)
+    cases.append((g["Yf"], g["Xf"], checkerboard(24, 28)))
+    g = messy_grid(0.8)
+    Yf = g["Yf"].copy()
+    Yf[12, 15] = np.nan                                        # the case of the GPU test: two coast segments end there
+    cases.append((Yf, g["Xf"], g["tmask"]))
+    for seed, (Nj, Ni, warp, p) in enumerate([(17, 23, 0.8, 0.5), (30, 9, 0.3, 0.2), (2, 2, 0., 0.5), (2, 40, 1.0, 0.5), (33, 2, 0.6, 0.7)]):
+        rng = np.random.default_rng(40 + seed)
+        g = syn.make_grid(Nj, Ni, dkm=4., warp=warp, rim=0)
+        Yf, Xf = g["Yf"].copy(), g["Xf"].copy()
+        if seed % 2:                                           # a few F-points without a position, NaN or inf, in either array
+            Yf.flat[rng.choice(Nj * Ni, 3, replace=False)] = np.nan
+            Xf.flat[rng.choice(Nj * Ni, 3, replace=False)] = np.inf
+        cases.append((Yf, Xf, (rng.random((Nj, Ni)) >= p).astype(np.int8)))
+    dropped = 0
+    for Yf, Xf, tmask in cases:
+        ids, ab, nd = coast_segments_ref(Yf, Xf, tmask)
+        ids_v, ab_v, nd_v = coast_segments_vec(Yf, Xf, tmask)
+        assert ids_v.dtype == np.int32 and ab_v.dtype == np.float64 and ab_v.shape == (len(ids), 2, 2)
+        assert np.array_equal(ids_v, ids) and np.array_equal(ab_v, ab) and nd_v == nd
+        dropped += nd
+    assert dropped >= 4
+
+
+def test_batched_brute_force_is_the_same_brute_force():
+    g = messy_grid(0.8)
+    ids, ab, _ = coast_segments_ref(g["Yf"], g["Xf"], g["tmask"])
+    rng = np.random.default_rng(3)
+    yx = np.stack([rng.uniform(g["Yf"].min(), g["Yf"].max(), 700), rng.uniform(g["Xf"].min(), g["Xf"].max(), 700)], axis=1)
+    yx[[5, 640]] = [[np.nan, 0.], [0., np.inf]]
+    for rmax in (None, 9.):
+        want = coast_dist_ref(yx, ids, ab, rmax)
+        for batch in (1000, 32, 7):
+            got = coast_dist_ref(yx, ids, ab, rmax, batch=batch)
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(got, want))
 
 
 def test_distances_by_hand():

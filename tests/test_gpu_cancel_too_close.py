@@ -13,6 +13,7 @@ from sitrack_amd import ncio
 from sitrack_amd import synthetic as syn
 
 from test_cancel_too_close import g11_cases, haversine, load_generator, nearest, random_cloud, restate
+from test_cloud_trips import NP_TRIP, TRIP, cancel_trip_case
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +130,54 @@ def test_einval_nonfinite_names_first_index(ctx, where, bad):
     v[7] = 0
     nn, _ = ctx.nearest_buoy(la, lo, v, 5.)
     assert nn[3] == -1 and nn[7] == -1
+
+
+def _small_call_still_right(ctx):
+    la, lo = np.array([80., 80., 80.00001, 70.]), np.array([10., 10., 10., 10.])
+    v = np.array([1, 0, 1, 1], np.int8)
+    nn, d = ctx.nearest_buoy(la, lo, v, 5.)
+    assert list(nn) == [2, -1, 0, -1] and np.isinf(d[1]) and np.isinf(d[3])
+    keep, nclose = ctx.cancel_too_close(la, lo, v, [3, 3, 3, 3], [0, 0, 0, 0], 5.)
+    assert list(keep) == [True, False, False, True] and nclose == 2
+
+
+def test_einval_names_the_first_index_of_the_second_trip(ctx):
+    """the first bad index lies past one trip of unit_bbox_kernel's capped grid"""
+    n = NP_TRIP
+    la, lo = np.full(n, 80.), np.linspace(0., 359., n)
+    ones, zeros = np.ones(n, np.int32), np.zeros(n, np.int32)
+    la[TRIP + 3] = np.nan
+    lo[TRIP + 700] = np.nan
+    v = np.ones(n, np.int8)
+    for valid in (None, v):
+        with pytest.raises(_lib.SitrkError, match="index %d$" % (TRIP + 3)):
+            ctx.nearest_buoy(la, lo, valid, 5.)
+        with pytest.raises(_lib.SitrkError, match="index %d$" % (TRIP + 3)):
+            ctx.cancel_too_close(la, lo, valid, ones, zeros, 5.)
+    _small_call_still_right(ctx)
+    v[TRIP + 3] = 0                             # an invalid buoy may hold anything: the next one is named
+    with pytest.raises(_lib.SitrkError, match="index %d$" % (TRIP + 700)):
+        ctx.nearest_buoy(la, lo, v, 5.)
+    with pytest.raises(_lib.SitrkError, match="index %d$" % (TRIP + 700)):
+        ctx.cancel_too_close(la, lo, v, ones, zeros, 5.)
+    _small_call_still_right(ctx)
+    la[9] = -np.inf                             # an earlier one, in the first trip
+    with pytest.raises(_lib.SitrkError, match="index 9$"):
+        ctx.nearest_buoy(la, lo, v, 5.)
+    with pytest.raises(_lib.SitrkError, match="index 9$"):
+        ctx.cancel_too_close(la, lo, v, ones, zeros, 5.)
+    _small_call_still_right(ctx)
+
+
+def test_cancel_too_close_with_valid_buoys_on_both_sides_of_the_trip(ctx):
+    """n past one trip of unit_bbox_kernel's capped grid, about 4000 valid buoys astride it: the flag, scan, scatter and host stage
+    against the restatement's parts over the full index space (tests/test_cloud_trips.py builds and checks the case)"""
+    la, lo, valid, nall, nbef, rd, alive, nclose_r, close, nn_r = cancel_trip_case()
+    keep, nclose = ctx.cancel_too_close(la, lo, valid, nall, nbef, rd)
+    assert len(keep) == NP_TRIP and nclose == nclose_r
+    assert np.array_equal(keep, alive), np.flatnonzero(keep != alive)[:8]
+    nn, d = ctx.nearest_buoy(la, lo, valid, rd)
+    assert np.array_equal(nn, nn_r) and np.array_equal(np.isfinite(d), close)
 
 
 def test_einval_null_arrays(ctx):

@@ -13,7 +13,8 @@ import sitrack_amd as sit
 from sitrack_amd import ncio
 from sitrack_amd import synthetic as syn
 
-from test_coast import coast_segments_ref, coast_dist_ref, d2_ref, island_grid
+from test_coast import checkerboard, coast_segments_ref, coast_dist_ref, d2_ref, island_grid, messy_grid
+from test_cloud_trips import COAST_BATCH, TRIP, coast_trip_grid, coast_trip_queries, coast_trip_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -25,18 +26,6 @@ def ctx():
     c = sit.Context(0)
     yield c
     c.close()
-
-
-def messy_grid(warp):
-    """24 x 28: an island, a one-cell island, land with a one-cell lake, a peninsula that reaches the rim, land along one rim row"""
-    g = syn.make_grid(24, 28, dkm=4., warp=warp, rim=0)
-    t = g["tmask"]
-    t[10:13, 12:16] = 0
-    t[4, 5] = 0
-    t[16:21, 18:24] = 0; t[18, 20] = 1
-    t[6:9, 0:6] = 0
-    t[-1, :] = 0
-    return g
 
 
 def query_mix(g, ab, n, seed=11):
@@ -77,9 +66,9 @@ def pair_d2(yx, ab):
     return cy * cy + cx * cx
 
 
-def check_against(dist, seg, yx, ids, ab, rmax=None, label=""):
+def check_against(dist, seg, yx, ids, ab, rmax=None, label="", batch=512):
     """every query against the brute force over all segments"""
-    d2r, segr, distr = coast_dist_ref(yx, ids, ab, rmax)
+    d2r, segr, distr = coast_dist_ref(yx, ids, ab, rmax, batch=batch)
     assert seg.dtype == np.int32 and dist.dtype == np.float64
     assert np.array_equal(seg, segr), (label, np.flatnonzero(seg != segr)[:5])
     fin = segr >= 0
@@ -216,12 +205,41 @@ def test_no_coast(ctx, value):
 # --------------------------------------------------------------------------- 4. dense coast
 def test_dense_coast_checkerboard(ctx):
     g = syn.make_grid(24, 28, dkm=4., warp=0.8, rim=0)
-    jj, ii = np.indices((24, 28))
-    g["tmask"][:] = ((jj + ii) % 2).astype(np.int8)
+    g["tmask"][:] = checkerboard(24, 28)
     ids, ab = build_and_check_segments(ctx, g)
     assert len(ids) == 23 * 27 * 2                              # every interior edge
     yx = query_mix(g, ab, 4096)
     check_against(*ctx.coast_dist(yx), yx, ids, ab, label="checkerboard")
+
+
+def test_mid_size_random_coast(ctx):
+    """about 28 000 segments: more than 100 workgroups, thousands of bins, a sort that moves every segment"""
+    g = syn.make_grid(160, 176, dkm=4., warp=0.8, rim=0)
+    g["tmask"][:] = (np.random.default_rng(31).random((160, 176)) >= 0.5).astype(np.int8)
+    ids, ab = build_and_check_segments(ctx, g)
+    assert 100 * 256 < len(ids) < 2 * 159 * 175
+    yx = query_mix(g, ab, 2048)[2::4]                           # 512 of every kind the mix holds
+    assert len(yx) == 512 and not np.isfinite(yx).all()
+    check_against(*ctx.coast_dist(yx), yx, ids, ab, label="random coast", batch=64)
+    d, s = ctx.coast_dist(yx, 12.)                              # three cells
+    check_against(d, s, yx, ids, ab, rmax=12., label="random coast, rmax 12", batch=64)
+    assert 25 < (s >= 0).sum() < 500
+
+
+def test_coast_past_one_trip_of_the_stats_kernel(ctx):
+    """more segments than one trip of coast_stats_kernel's capped grid, the longest of them known to the second trip alone: `pad`,
+    and with it every query's search radius, depends on it (tests/test_cloud_trips.py checks what the input holds)"""
+    Yf, Xf, tmask = coast_trip_grid()
+    ids_r, ab_r, nd_r = coast_trip_segments()
+    assert len(ids_r) > TRIP
+    assert ctx.coast_build(Yf, Xf, tmask) == (len(ids_r), nd_r)
+    ids, ab = ctx.coast_segments()
+    assert ids.dtype == np.int32 and np.array_equal(ids, ids_r) and np.array_equal(ab, ab_r)
+    yx, designed, dense = coast_trip_queries()
+    assert len(yx) <= 128
+    dist, seg = ctx.coast_dist(yx)
+    d2r, segr = check_against(dist, seg, yx, ids_r, ab_r, label="past one trip", batch=COAST_BATCH)
+    assert (np.searchsorted(ids_r, seg[designed]) >= TRIP).all() and (np.searchsorted(ids_r, seg[dense]) < TRIP).all()
 
 
 # --------------------------------------------------------------------------- 5. long segments

@@ -10,6 +10,7 @@ from sitrack_amd import _lib
 from test_deform import DAY3, check_linear_field, jittered_lattice, linear_move
 from test_gpu_deform import tracked_case
 from test_delaunay import UNIT, cocircular_points, delaunay_fast, delaunay_literal, delaunay_ref, lattice_case, quantise
+from test_cloud_trips import NP_TRIP, TRIP, delaunay_trip_case
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +152,36 @@ def test_large_cloud_with_clusters_holes_and_a_sparse_region(ctx, large_case):
     # the sparse region has vertices and no triangle
     sparse = np.flatnonzero(yx[:, 1] > 300. + 560.)
     assert len(sparse) == 400 and (v[sparse] == 1).all() and not np.isin(t, sparse).any()
+
+
+def test_vertices_on_both_sides_of_the_quantise_kernels_trip(ctx):
+    """nP past one trip of dl_quant_kernel's capped grid, few vertices: the second trip's points need their xy and vertex bytes and
+    their part in nv, the bounding box and the mask (tests/test_cloud_trips.py checks what the input holds)"""
+    yx, mask, rmax, want = delaunay_trip_case()
+    t, v = same_as(ctx, yx, rmax, mask, want=want)
+    assert len(yx) == NP_TRIP and (v[TRIP:] == 1).sum() >= 1000 and (t >= TRIP).all(axis=1).sum() >= 100
+
+
+def test_out_of_range_index_in_the_second_trip():
+    rng = np.random.default_rng(12)
+    yx = rng.uniform(0., 30., (NP_TRIP, 2))
+    small = rng.uniform(0., 30., (200, 2))
+    want = delaunay_ref(small, 4.)
+    ctx = _lib.Context(0)
+    try:
+        yx[[TRIP + 1234, TRIP + 77], 1] = 2.0 ** 31
+        with pytest.raises(_lib.SitrkError, match=r"beyond 2\^30 km at index %d$" % (TRIP + 77)):
+            ctx.delaunay(yx, 4.)
+        yx[5, 0] = -2.0 ** 31
+        with pytest.raises(_lib.SitrkError, match=r"beyond 2\^30 km at index 5$"):
+            ctx.delaunay(yx, 4.)
+        m = np.ones(NP_TRIP, dtype=np.int8)
+        m[5] = 0
+        with pytest.raises(_lib.SitrkError, match=r"beyond 2\^30 km at index %d$" % (TRIP + 77)):
+            ctx.delaunay(yx, 4., mask=m)
+        same_as(ctx, small, 4., want=want)
+    finally:
+        ctx.close()
 
 
 def test_device_resident_buoys():

@@ -14,6 +14,7 @@ from sitrack_amd import ncio
 from sitrack_amd import synthetic as syn
 
 from test_subsample import greedy_reference, characterisation_violations, hand_cases, fma_case, d2
+from test_cloud_trips import NP_TRIP, TRIP
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -108,6 +109,25 @@ def test_bad_arguments_return_einval(ctx):
     assert L.sitrk_subsample_cloud(h, 5, p(yx), 1.0, p(keep), C.byref(nk), None) == 0 and nk.value == 1       # five duplicates
     with pytest.raises(sit.SitrkError):
         ctx.set_tuning(subsample_block=300)
+
+
+def test_einval_names_the_first_index_of_the_second_trip(ctx):
+    """the first bad index lies past one trip of bbox_kernel's capped grid"""
+    yx = np.random.default_rng(5).uniform(-300., 300., (NP_TRIP, 2))
+    _, small, rd, want = hand_cases()[-1]
+    yx[TRIP + 3, 0] = np.nan
+    yx[TRIP + 700, 1] = np.nan
+    with pytest.raises(sit.SitrkError, match="non-finite coordinate at index %d$" % (TRIP + 3)):
+        ctx.subsample_cloud(yx, 3.0)
+    assert np.array_equal(ctx.subsample_cloud(np.array(small), rd)[0], np.array(want, dtype=bool))
+    yx[TRIP + 3, 0] = 0.                          # there is no validity mask: mended, the next one is named
+    with pytest.raises(sit.SitrkError, match="non-finite coordinate at index %d$" % (TRIP + 700)):
+        ctx.subsample_cloud(yx, 3.0)
+    yx[TRIP + 3, 0] = np.nan
+    yx[9, 1] = np.inf                             # an earlier one, in the first trip
+    with pytest.raises(sit.SitrkError, match="non-finite coordinate at index 9$"):
+        ctx.subsample_cloud(yx, 3.0)
+    assert np.array_equal(ctx.subsample_cloud(np.array(small), rd)[0], np.array(want, dtype=bool))
 
 
 def test_tracker_state_is_untouched_by_a_coarsening_on_the_same_handle():
