@@ -122,6 +122,7 @@ int sitrk_set_substeps(sitrk_t *h, int nsub);
  * its buoy in registers across the records); "subsample_block" (256..4096, powers of two, default 1024): points per workgroup of
  * sitrk_subsample_cloud's resolve kernel; "coast_bin" (1..64, default 4): bin side of the next sitrk_coast_build, in quarters of
  * sqrt(bounding-box area / segments); "delaunay_bin" (1..4, default 3): cells per reach of the next sitrk_delaunay;
+ * "skeleton_batch" (1..8, default 8): sub-iterations per launch of the thinning kernel of the next skeleton call;
  * "lanes" (1/2, default 2) / "lane_min_wg" (>= 1, default 7168): with lanes = 2, sitrk_run splits the cell-sorted buoys into two
  * contiguous lanes (cut at a multiple of 256 * 8 * xcd_group buoys) and queues each lane's fused launches on a stream of its own
  * -- lane 0 on the compute stream, lane 1 on the ingest stream, its first launch half as long, so that the lanes' launch
@@ -749,6 +750,55 @@ int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int di, int r
                          int64_t *nhit);
 int sitrk_match_kernel_ms(sitrk_t *h, float *emit_ms, float *sort_ms, float *rows_ms);
 int sitrk_advect_kernel_ms(sitrk_t *h, float *advect_ms);
+
+/* ---- skeletons of a label map: thinning, a table per feature, end points and junctions ---------------
+ * An EXTRA the reference does not have: the features of a label map thinned to lines one pixel wide on the device, so that a
+ * feature's length along itself, its number of arms and the places where arms meet come down instead of the map (DESIGN.md
+ * 3.19).  No parity claim is made against any other code; the contract below is this library's own.  Everything is integer and
+ * nothing is defined by an order of evaluation, so nothing is unpinned and two calls return the same bits.
+ * INPUT.  A label map L (ny,nx) int32 within the limits of sitrk_label_raster, every value -1 or in [0, ny*nx): whatever
+ * sitrk_keep_put accepts; it need not be a canonical labelling.  The mask is L >= 0; p = j*nx + i.
+ * THINNING: Guo and Hall's two-sub-iteration algorithm (A1, 1989) on the mask, pixels outside the raster counting as 0.  For pixel
+ * (j,i) of the current state S name its neighbours  p2 = S[j-1,i], p3 = S[j-1,i+1], p4 = S[j,i+1], p5 = S[j+1,i+1], p6 = S[j+1,i],
+ * p7 = S[j+1,i-1], p8 = S[j,i-1], p9 = S[j-1,i-1]  and define
+ *     C = (!p2 & (p3|p4)) + (!p4 & (p5|p6)) + (!p6 & (p7|p8)) + (!p8 & (p9|p2))
+ *     N = min((p9|p2)+(p3|p4)+(p5|p6)+(p7|p8), (p2|p3)+(p4|p5)+(p6|p7)+(p8|p9))
+ *     m = (p6|p7|!p9) & p8  for sub-iteration k = 0, 2, 4, ...;   m = (p2|p3|!p5) & p4  for k = 1, 3, 5, ...
+ * Sub-iteration k removes, all at once and from the state before it, every set pixel with  C == 1 && 2 <= N <= 3 && m == 0.
+ * The device applies sub-iterations 0 .. max_sub-1 with 1 <= max_sub <= 2^20; those behind the fixpoint change nothing, so it
+ * may stop early.  *nsub = 1 + the index of the last sub-iteration that removed a pixel, 0 if none did; *converged = 1 iff
+ * max_sub >= nsub + 2: one quiet sub-iteration of each kind has then been seen.  THE SKELETON K is the state after those
+ * sub-iterations.  The labels play no part in the thinning: features that touch are thinned as one.
+ * CLASSIFICATION.  With the ring r0..r7 = p2, p3, p4, p5, p6, p7, p8, p9 taken from K, X(p) = the number of k with r[k] == 0 and
+ * r[(k+1)%8] == 1.  A skeleton pixel is an END iff X == 1 and a JUNCTION iff X >= 3.
+ * LINKS.  A link joins two skeleton pixels of one label.  An orthogonal link is (j,i)-(j,i+1) or (j,i)-(j+1,i).  A diagonal link
+ * is (j,i)-(j+1,i+1) with neither (j,i+1) nor (j+1,i) in K, or (j,i)-(j+1,i-1) with neither (j,i-1) nor (j+1,i) in K; the blocking
+ * pixels count whatever their label.  Each link is attributed once, to its first pixel.  A straight row of n pixels has n-1 links.
+ * THE TABLE: table (maxfeat, SITRK_SKEL_NCOLS) int64, one row per distinct value >= 0 of L in ascending value; only the first
+ * maxfeat rows are written (maxfeat >= 0; table may be NULL iff maxfeat == 0), the rest is left as it was.  Columns: [0] the value;
+ * [1] the pixels of L with it; [2] nskel, its skeleton pixels; [3] nend; [4] njunc; [5] north; [6] ndiag.  *nfeat counts all rows.
+ * THE NODES: nodes (maxnode, 3) int64, the rows (p, L[p], X(p)) of every skeleton pixel with X != 2 -- isolated pixels, X == 0,
+ * included -- in ascending p; only the first maxnode rows are written (nodes may be NULL iff maxnode == 0).  *nnode counts all.
+ * skel (ny,nx) int8, 1 on K and 0 elsewhere, may be NULL: nothing of raster size comes down then.  *nskel = the pixels of K.  Any
+ * count pointer may be NULL.
+ * sitrk_skeleton_raster: a host map.  Synchronous on the handle's stream; uses the context's transient scratch only.  A value
+ * outside [-1, ny*nx) is SITRK_EINDEX with the number of offending values in sitrk_last_error, as in sitrk_keep_put.
+ * sitrk_keep_skeleton: the kept map of slot keep, which it leaves as it was; SITRK_EINVAL for a slot out of range or empty.  With a
+ * slot filled by sitrk_mesh_features_keep the rows of the table carry the labels and npix of that call's feature table in the
+ * same order, given an equal maxfeat.
+ * SITRK_EINVAL before any device work for a raster, max_sub, maxfeat or maxnode out of range and for missing pointers.  The
+ * result never depends on the knob "skeleton_batch".
+ * sitrk_skeleton_kernel_ms: GPU time [ms] of the phases of the last of the two calls on this handle, from HIP events -- the
+ * thinning (its launches and the waits for their counters), the table (classification, counts, scan, rows), the nodes; any
+ * pointer may be NULL, SITRK_EINVAL before any such call. */
+#define SITRK_SKEL_NCOLS 7
+int sitrk_skeleton_raster(sitrk_t *h, int ny, int nx, const int32_t *map, int max_sub, int64_t maxfeat, int64_t maxnode,
+                          int8_t *skel, int64_t *table, int64_t *nodes, int64_t *nfeat, int64_t *nnode, int64_t *nskel,
+                          int *nsub, int *converged);
+int sitrk_keep_skeleton(sitrk_t *h, int keep, int max_sub, int64_t maxfeat, int64_t maxnode,
+                        int8_t *skel, int64_t *table, int64_t *nodes, int64_t *nfeat, int64_t *nnode, int64_t *nskel,
+                        int *nsub, int *converged);
+int sitrk_skeleton_kernel_ms(sitrk_t *h, float *thin_ms, float *table_ms, float *nodes_ms);
 
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,

@@ -34,6 +34,9 @@ LABEL_TILE = 64                              # SITRK_LABEL_TILE
 KEEP_MAX = 16                                # SITRK_KEEP_MAX
 MATCH_MAXREACH = 2                           # SITRK_MATCH_MAXREACH
 MATCH_MAXSHIFT = 32768                       # |dj|, |di| of sitrk_features_match
+SKEL_NCOLS = 7                               # SITRK_SKEL_NCOLS, in this order:
+SKEL_COLS = ("label", "npix", "nskel", "nend", "njunc", "north", "ndiag")
+SKEL_MAXSUB = 1 << 20                        # max_sub of the skeleton calls
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -124,6 +127,11 @@ _SIGNATURES = {
     "sitrk_features_match": (_int, [_vp, _int, _int, _int, _int, _int, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_match_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
     "sitrk_advect_kernel_ms": (_int, [_vp, C.POINTER(C.c_float)]),
+    "sitrk_skeleton_raster": (_int, [_vp, _int, _int, _vp, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                                     C.POINTER(_int), C.POINTER(_int)]),
+    "sitrk_keep_skeleton": (_int, [_vp, _int, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                                   C.POINTER(_int), C.POINTER(_int)]),
+    "sitrk_skeleton_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -1043,6 +1051,48 @@ class Context:
         v = C.c_float(0)
         self._chk(self._L.sitrk_advect_kernel_ms(self._h, C.byref(v)))
         return v.value
+
+    # -- skeletons of a label map (sitrk_skeleton_raster, sitrk_keep_skeleton)
+    def _skeleton_call(self, fn, head, shape, max_sub, maxfeat, maxnode, skel):
+        maxfeat, maxnode = int(maxfeat), int(maxnode)
+        table = np.zeros((max(maxfeat, 0), SKEL_NCOLS), dtype=np.int64)
+        nodes = np.zeros((max(maxnode, 0), 3), dtype=np.int64)
+        sk = np.empty(shape, dtype=np.int8) if skel else None
+        nfeat, nnode, nskel, nsub, conv = _i64(0), _i64(0), _i64(0), _int(0), _int(0)
+        self._chk(fn(self._h, *head, int(max_sub), maxfeat, maxnode, _ptr(sk), _ptr(table) if maxfeat > 0 else None,
+                     _ptr(nodes) if maxnode > 0 else None, C.byref(nfeat), C.byref(nnode), C.byref(nskel), C.byref(nsub), C.byref(conv)))
+        return {"table": table[:min(nfeat.value, table.shape[0])], "nodes": nodes[:min(nnode.value, nodes.shape[0])],
+                "nfeat": nfeat.value, "nnode": nnode.value, "nskel": nskel.value, "nsub": nsub.value, "converged": conv.value,
+                "skel": sk}
+
+    def skeleton_raster(self, map, max_sub=4096, maxfeat=65536, maxnode=1 << 20, skel=True):
+        """sitrk_skeleton_raster: the mask map >= 0 of the host label map (ny,nx), every value -1 or in [0, ny*nx), thinned by at
+        most max_sub sub-iterations of Guo and Hall's algorithm.  A dict with table (rows, 7) int64 under the names SKEL_COLS --
+        one row per distinct label in ascending order, the first maxfeat of them --, nodes (rows, 3) int64 rows (p, label, X) of
+        the skeleton pixels with X != 2 in ascending p, the first maxnode of them, the counts nfeat, nnode, nskel, nsub,
+        converged, and skel: (ny,nx) int8, None with skel=False."""
+        a = np.asarray(map)
+        if a.ndim != 2 or a.dtype.kind not in "iu":
+            raise ValueError("skeleton_raster: map must be an (ny, nx) array of integers, got %s %s" % (a.shape, a.dtype))
+        ny, nx = a.shape
+        if not (ny < 2 ** 31 and nx < 2 ** 31):
+            raise ValueError("skeleton_raster: ny and nx must fit int32, got %d, %d" % (ny, nx))
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise IndexError("skeleton_raster: a value of the map does not fit int32")
+        a = as_c(a, np.int32)
+        return self._skeleton_call(self._L.sitrk_skeleton_raster, (ny, nx, _ptr(a)), (ny, nx), max_sub, maxfeat, maxnode, skel)
+
+    def keep_skeleton(self, keep, max_sub=4096, maxfeat=65536, maxnode=1 << 20, skel=False):
+        """sitrk_keep_skeleton: skeleton_raster() of the kept map of slot `keep`, which stays on the device and as it was; the
+        same dict"""
+        shape = self.keep_get(keep, labels=False)["shape"] if skel else None
+        return self._skeleton_call(self._L.sitrk_keep_skeleton, (int(keep),), shape, max_sub, maxfeat, maxnode, skel)
+
+    def skeleton_kernel_ms(self):
+        """(thin_ms, table_ms, nodes_ms): GPU time of the phases of the last skeleton call (sitrk_skeleton_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_skeleton_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

@@ -134,6 +134,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     coarse_release(h);
     label_release(h);
     track_release(h);
+    skeleton_release(h);
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
@@ -312,6 +313,8 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
         h->delaunay_bin = value;
         return SITRK_OK;
     }
+    else if (!strcmp(knob, "skeleton_batch"))        // sub-iterations per launch of the next skeleton call
+        return skeleton_set_batch(h, value);
     else if (!strcmp(knob, "raster_count")) {        // the next raster calls count their claims and atomics (sitrk_raster_stats)
         if (value < 0 || value > 1) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: raster_count must be 0 or 1");
         h->raster_count = value;

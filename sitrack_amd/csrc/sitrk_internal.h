@@ -289,6 +289,11 @@ struct sitrk_ctx {
     hipEvent_t track_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool match_timed = false, advect_timed = false;
 
+    // skeletons of a label map (sitrk_skeleton.hip): events around the three phases of the last call -- thinning, table, nodes
+    hipEvent_t skel_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool skel_timed = false;
+    int skeleton_batch = 0;             // knob: sub-iterations per launch of the thinning kernel, 1..8; 0 = as shipped (never changes results)
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -367,6 +372,9 @@ int mesh_features_body(sitrk_ctx *h, const char *fn, int mesh, int jrec1, int at
 // timing events (sitrk_destroy)
 int keep_from_labels(sitrk_ctx *h, int64_t npix, const int32_t *labels, const int32_t *flag, int32_t *keep_map);
 void track_release(sitrk_ctx *h);
+// sitrk_skeleton.hip: destroys the timing events (sitrk_destroy); the knob skeleton_batch behind its range check (sitrk_set_tuning)
+void skeleton_release(sitrk_ctx *h);
+int skeleton_set_batch(sitrk_ctx *h, int value);
 // sitrk_coarse.hip: destroys the timing events (sitrk_destroy)
 void coarse_release(sitrk_ctx *h);
 // sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)

@@ -132,8 +132,20 @@ def parse_args(argv=None):
                          'the label in this one, the pixels where they meet -- with m<k>_w<k>_pairs_counts = (npair, nhit), and per '
                          'row of m<k>_w<k>_features m<k>_w<k>_track and m<k>_w<k>_age, next to `track` = (reach,); the features '
                          'continued, born, ended, merged and split are logged.  At most 8 meshes')
+    ap.add_argument('--deform-skeleton', type=_deform_skeleton_arg, nargs='?', const=features.SKEL_DEFAULT_MAXSUB, default=None,
+                    metavar='MAXSUB',
+                    help='with --deform-features: the features of every window are thinned to their skeletons on the GPU (extra; '
+                         'default none), by at most MAXSUB sub-iterations (1..2^20, default 4096) of Guo and Hall\'s algorithm on the '
+                         'kept label map.  Stored as m<k>_w<k>_skeleton (rows, 7) int64 -- label, npix, skeleton pixels, ends, '
+                         'junctions, orthogonal and diagonal links, one row per row of m<k>_w<k>_features --, m<k>_w<k>_skeleton_nodes '
+                         '(rows, 3) int64 -- pixel, label, X of every end (X = 1), junction (X >= 3) and isolated pixel (X = 0) -- with '
+                         'm<k>_w<k>_skeleton_counts = (nfeat, nnode, nskel, nsub, converged), next to `skeleton` = (max_sub,); the '
+                         'feature count and the longest skeleton are logged')
     a = ap.parse_args(argv)
     refusal = deform_track_refusal(a.deform_track, a.deform_features, a.deform_grid, len(a.deform))
+    if refusal:
+        ap.error(refusal)
+    refusal = deform_skeleton_refusal(a.deform_skeleton, a.deform_features)
     if refusal:
         ap.error(refusal)
     if a.deform_features is not None and a.deform_grid is None:
@@ -215,6 +227,23 @@ def _deform_track_arg(text):
         return features.track_arg(text, '--deform-track')
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
+
+
+def _deform_skeleton_arg(text):
+    """--deform-skeleton: MAXSUB, an integer in 1..2^20"""
+    try:
+        return features.skeleton_arg(text, '--deform-skeleton')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def deform_skeleton_refusal(skel, feat):
+    """--deform-skeleton: why the flags given cannot be thinned with, or None: it thins the features of --deform-features"""
+    if skel is None:
+        return None
+    if feat is None:
+        return "--deform-skeleton: it thins the features of --deform-features; give that flag too"
+    return None
 
 
 def deform_track_refusal(track, feat, grid, nmesh):
@@ -867,8 +896,10 @@ class DeformSeries:
       win      the windows [(jrec0, jrec1)];  first / last: model record -> the window it opens / closes
       out      what is kept of every (mesh, window) for the file"""
 
-    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None, track=None):
+    def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None, track=None,
+                 skel=None):
         self.specs, self.grid, self.grid_at, self.coarse, self.feat, self.track = specs, grid, grid_at, coarse, feat, track
+        self.skel = skel                                 # --deform-skeleton: max_sub
         self.links = {}                                  # --deform-track: (mesh, window) -> the links to the window before
         self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
         self.win = deform_windows(Nt, kstrt, window)
@@ -924,8 +955,10 @@ class DeformSeries:
             if self.feat is not None:                    # the features of this mesh's map: 96 bytes per feature come down
                 what, sgn, thr, min_pix, conn = self.feat
                 # --deform-track: kept map 2km = this window's features, 2km + 1 = those of the window before at this window's start
+                # --deform-skeleton without it: the last kept map, for this call only
+                slot = 2 * km if self.track is not None else _lib.KEEP_MAX - 1 if self.skel is not None else None
                 f = self.trk.mesh_features(jrec1, self.grid, what=what, thr=thr, sgn=sgn, conn=conn, min_pix=min_pix, slot=km,
-                                           at=self.grid_at, keep=None if self.track is None else 2 * km)
+                                           at=self.grid_at, keep=slot)
                 self.out[pre + "features"] = f["table"]
                 self.out[pre + "features_counts"] = np.array([f["nfeat"], f["ncomp"], f["nactive"]], dtype=np.int64)
                 ft = features.feature_table(f["table"], self.grid)
@@ -933,6 +966,23 @@ class DeformSeries:
                          'longest %s' % (kw, km, f["nfeat"], min_pix, f["ncomp"], f["nactive"],
                                          '' if f["nfeat"] == len(f["table"]) else ', first %d kept' % len(f["table"]),
                                          '%.3f km' % ft["length_km"].max() if len(f["table"]) else 'n/a'))
+                if self.skel is not None:                # this window's kept map thinned: 56 bytes per feature, 24 per node come down
+                    try:
+                        s = self.trk.features_skeleton(slot, max_sub=self.skel)
+                    finally:
+                        if self.track is None:
+                            self.ctx.keep_free(slot)
+                    self.out[pre + "skeleton"] = s["table"]
+                    self.out[pre + "skeleton_nodes"] = s["nodes"]
+                    self.out[pre + "skeleton_counts"] = np.array([s["nfeat"], s["nnode"], s["nskel"], s["nsub"], s["converged"]], dtype=np.int64)
+                    sk = features.skeleton_table(s["table"], self.grid)
+                    self.say(' *** --deform-skeleton window %d mesh %d: %d features, %d skeleton pixels, %d nodes%s in %d sub-iterations, '
+                             'longest %s' % (kw, km, s["nfeat"], s["nskel"], s["nnode"],
+                                             '' if s["nnode"] == len(s["nodes"]) else ' (first %d kept)' % len(s["nodes"]), s["nsub"],
+                                             '%.3f km' % sk["length_km"].max() if len(s["table"]) else 'n/a'))
+                    if not s["converged"]:
+                        self.say(' *** WARNING --deform-skeleton window %d mesh %d: the thinning had not ended after %d sub-iterations; '
+                                 'the skeleton is not final' % (kw, km, self.skel))
                 if self.track is not None:
                     if kw > 0:                           # 24 bytes per pair of features that meet come down
                         m = self.trk.features_match(2 * km + 1, 2 * km, reach=self.track)
@@ -966,7 +1016,8 @@ class DeformSeries:
                        **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}),
                        **({"features": np.array((_lib.FEAT_WHAT[self.feat[0]],) + tuple(self.feat[1:]), dtype=np.float64)}
                           if self.feat else {}),
-                       **({"track": np.array([self.track], dtype=np.int64)} if self.track is not None else {}))
+                       **({"track": np.array([self.track], dtype=np.int64)} if self.track is not None else {}),
+                       **({"skeleton": np.array([self.skel], dtype=np.int64)} if self.skel is not None else {}))
 
 
 class Outputs:
@@ -1117,7 +1168,8 @@ def main(argv=None):
     bcast = record_broadcaster(a, comm, ctx, tphase)
     ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
-                       say, clk, coarse=a.deform_coarse, feat=a.deform_features, track=a.deform_track) if a.deform else None
+                       say, clk, coarse=a.deform_coarse, feat=a.deform_features, track=a.deform_track,
+                       skel=a.deform_skeleton) if a.deform else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no

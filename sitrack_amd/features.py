@@ -9,12 +9,16 @@ lengths, widths and orientations.
 Features from window to window (sitrack_amd/csrc/sitrk_track.hip): IceTracker.mesh_features(keep=...),
 features_advect() and features_match() keep, carry and compare label maps on the device; MatchLabels() compares two host maps
 the same way; link_features() and feature_tracks() turn the pair tables into parents, children and tracks, on the host and in
-integers."""
+integers.
+
+Skeletons (sitrack_amd/csrc/sitrk_skeleton.hip): SkeletonRaster() and IceTracker.features_skeleton() thin the
+features of a label map to lines one pixel wide on the device; skeleton_table() turns the integer rows into lengths along the
+features, node_yx() the node list into positions."""
 import math
 
 import numpy as np
 
-from ._lib import FEAT_COLS, FEAT_NCOLS, FEAT_WHAT, KEEP_MAX, MATCH_MAXREACH, MATCH_MAXSHIFT
+from ._lib import FEAT_COLS, FEAT_NCOLS, FEAT_WHAT, KEEP_MAX, MATCH_MAXREACH, MATCH_MAXSHIFT, SKEL_COLS, SKEL_MAXSUB, SKEL_NCOLS
 
 MAX_SIDE = 32768
 MAX_PIXELS = 2 ** 28
@@ -325,3 +329,83 @@ def track_events(link, track_prev, track_next):
     cont = int(np.isin(track_next, track_prev).sum()) if len(track_prev) else 0
     return (cont, len(track_next) - cont, len(track_prev) - cont, int((np.asarray(link["nparents"]) > 1).sum()),
             int((np.asarray(link["nchildren"]) > 1).sum()))
+
+
+# ------------------------------------------------------------------------------------------------ skeletons
+SKEL_DEFAULT_MAXSUB = 4096
+
+
+def check_skeleton_args(max_sub, maxfeat, maxnode, cerr=''):
+    """the library's checks of max_sub, maxfeat and maxnode of the skeleton calls; returns them as integers"""
+    max_sub, maxfeat, maxnode = (_as_int(v, n, cerr) for v, n in ((max_sub, "max_sub"), (maxfeat, "maxfeat"), (maxnode, "maxnode")))
+    if not 1 <= max_sub <= SKEL_MAXSUB:
+        raise ValueError(cerr + '`max_sub` must be in 1..%d sub-iterations, got %r' % (SKEL_MAXSUB, max_sub))
+    if maxfeat < 0:
+        raise ValueError(cerr + '`maxfeat` must be >= 0, got %r' % (maxfeat,))
+    if maxnode < 0:
+        raise ValueError(cerr + '`maxnode` must be >= 0, got %r' % (maxnode,))
+    return max_sub, maxfeat, maxnode
+
+
+def skeleton_arg(text, flag='--deform-skeleton'):
+    """MAXSUB of --deform-skeleton [MAXSUB]: an integer in 1..2^20.  ValueError otherwise."""
+    try:
+        max_sub = int(text)
+    except (TypeError, ValueError):
+        raise ValueError("%s: MAXSUB must be an integer number of sub-iterations, got %r" % (flag, text)) from None
+    if not 1 <= max_sub <= SKEL_MAXSUB:
+        raise ValueError("%s: MAXSUB must be in 1..%d sub-iterations, got %r" % (flag, SKEL_MAXSUB, text))
+    return max_sub
+
+
+def SkeletonRaster(map_or_mask, conn=8, max_sub=SKEL_DEFAULT_MAXSUB, maxfeat=65536, maxnode=1 << 20, ctx=None):
+    """The skeleton of the features of a raster (ny, nx).  A bool or int8 array is a mask and is labelled first with
+    LabelRaster(mask, conn); an int32 array is taken as a label map, every value -1 or a label in [0, ny*nx).  The mask of the
+    labelled pixels is thinned by Guo and Hall's two-sub-iteration algorithm, at most `max_sub` sub-iterations of it.  Returns
+    {"table", "nodes", "nfeat", "nnode", "nskel", "nsub", "converged", "skel", "labels"}: table (rows, 7) int64 under the names
+    _lib.SKEL_COLS, one row per label in ascending order, at most maxfeat rows; nodes (rows, 3) int64 rows (p, label, X) of the
+    skeleton pixels that are no plain line pixel (X = 1 an end, X >= 3 a junction, X = 0 an isolated pixel) in ascending
+    p = j*nx + i, at most maxnode rows; skel (ny, nx) int8; labels the map that was thinned.  converged = 0: max_sub was too
+    small to see the thinning end.  Runs on the GPU.  Raises ValueError on bad arguments before any device work."""
+    from .tracking import default_context
+    cerr = 'ERROR [SkeletonRaster()]: '
+    a = np.asarray(map_or_mask)
+    if a.ndim != 2 or a.dtype not in (np.dtype(bool), np.dtype(np.int8), np.dtype(np.int32)):
+        raise ValueError(cerr + 'expected an (ny, nx) mask of bool or int8, or a label map of int32, got %s %s' % (a.shape, a.dtype))
+    conn, _, _ = check_label_args(a.shape[0], a.shape[1], conn, 1, 0, cerr)
+    max_sub, maxfeat, maxnode = check_skeleton_args(max_sub, maxfeat, maxnode, cerr)
+    c = ctx or default_context()
+    if a.dtype != np.dtype(np.int32):
+        a = c.label_raster(a, conn=conn, min_pix=1, maxfeat=0, labels=True)["labels"]
+    r = c.skeleton_raster(a, max_sub=max_sub, maxfeat=maxfeat, maxnode=maxnode, skel=True)
+    r["labels"] = a
+    return r
+
+
+def skeleton_table(table, grid):
+    """Per row of a skeleton table on the grid (y0_km, x0_km, d_km, ny, nx), a dict of (rows,) arrays: label, npix, nskel, n_end,
+    n_junc, north, ndiag and length_km = d*(north + sqrt(2)*ndiag), the length along the skeleton.  It counts LINKS, not pixels:
+    a straight row of n skeleton pixels is (n - 1)*d long, an isolated pixel 0."""
+    from .raster import check_grid
+    cerr = 'ERROR [skeleton_table()]: '
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != SKEL_NCOLS or t.dtype.kind not in "iu":
+        raise ValueError(cerr + '`table` must be (rows, %d) integers, got %s %s' % (SKEL_NCOLS, t.shape, t.dtype))
+    _, _, d, _, _ = check_grid(grid, cerr)
+    c = dict(zip(SKEL_COLS, (t[:, k].copy() for k in range(SKEL_NCOLS))))
+    return {"label": c["label"], "npix": c["npix"], "nskel": c["nskel"], "n_end": c["nend"], "n_junc": c["njunc"],
+            "north": c["north"], "ndiag": c["ndiag"], "length_km": d * (c["north"] + math.sqrt(2.) * c["ndiag"])}
+
+
+def node_yx(nodes, grid):
+    """(rows, 2) [y, x] km: the pixel centres of the rows (p, label, X) of a node list on the grid (y0_km, x0_km, d_km, ny, nx)"""
+    from .raster import check_grid
+    cerr = 'ERROR [node_yx()]: '
+    n = np.asarray(nodes)
+    if n.ndim != 2 or n.shape[1] != 3 or (n.size and n.dtype.kind not in "iu"):
+        raise ValueError(cerr + '`nodes` must be (rows, 3) integers, got %s %s' % (n.shape, n.dtype))
+    y0, x0, d, ny, nx = check_grid(grid, cerr)
+    p = n[:, 0].astype(np.int64)
+    if np.any((p < 0) | (p >= ny * nx)):
+        raise ValueError(cerr + 'a node lies outside the %d x %d grid' % (ny, nx))
+    return np.stack([y0 + (p // nx + 0.5) * d, x0 + (p % nx + 0.5) * d], axis=1)

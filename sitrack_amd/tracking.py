@@ -392,6 +392,17 @@ class IceTracker:
         keepA, keepB = check_keep(keepA, "keepA", cerr), check_keep(keepB, "keepB", cerr)
         return self.ctx.features_match(keepA, keepB, reach=reach, dj=dj, di=di, maxpair=maxpair)
 
+    def features_skeleton(self, keep, max_sub=4096, maxfeat=65536, maxnode=1 << 20, skel=False):
+        """The skeleton of the features of the kept map `keep` (an extra the reference does not have; sitrk_keep_skeleton): the
+        dict of sit.SkeletonRaster without "labels" -- table, nodes, nfeat, nnode, nskel, nsub, converged and skel, None unless
+        skel=True.  The kept map stays on the device and as it was; with a map kept by mesh_features(keep=...) the rows of the
+        table follow those of its feature table.  sit.skeleton_table(table, grid) turns the rows into lengths."""
+        from .features import check_keep, check_skeleton_args
+        cerr = 'ERROR [IceTracker.features_skeleton()]: '
+        keep = check_keep(keep, "keep", cerr)
+        max_sub, maxfeat, maxnode = check_skeleton_args(max_sub, maxfeat, maxnode, cerr)
+        return self.ctx.keep_skeleton(keep, max_sub=max_sub, maxfeat=maxfeat, maxnode=maxnode, skel=skel)
+
     def mesh_free(self, slot=0):
         self.ctx.mesh_free(slot)
 

@@ -2,7 +2,7 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]] [--track [REACH]]]]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]] [--track [REACH]] [--skeleton [MAXSUB]]]]
                                 [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
@@ -28,6 +28,11 @@ among the pixels it owns at K0 and gives it to the pixels it owns at K1, here in
 on the same grid, and the two are matched on the GPU within REACH pixels (0..2, default 1; sitrk_features_match).  OUT then
 holds `next_features`, `pairs` (npair, 3) -- label, label in the next window, pixels where they meet --, `pairs_counts` =
 (npair, nhit), `parent` per row of next_features and `child` per row of features (sit.link_features) and `track_arg` = (reach, K2).
+`--skeleton [MAXSUB]` with --features thins those features to their skeletons on the GPU (sitrk_skeleton_raster),
+by at most MAXSUB sub-iterations (1..2^20, default 4096): OUT then holds `skeleton` (rows, 7) int64 -- label, npix, skeleton
+pixels, ends, junctions, orthogonal and diagonal links, one row per row of `features` --, `skeleton_nodes` (rows, 3) int64 --
+pixel, label, X of every end, junction and isolated pixel --, `skeleton_counts` = (nfeat, nnode, nskel, nsub, converged) and
+`skeleton_arg` = (max_sub,).
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -93,8 +98,20 @@ def main(argv=None):
                     help='with --features: also link the features to those of the next window of as many records, K1 -> K1 + (K1 - K0), '
                          'within REACH pixels (0..2, default 1) (`next_features`, `pairs`, `pairs_counts`, `parent`, `child`, '
                          '`track_arg` in the output)')
+    ap.add_argument('--skeleton', nargs='?', const='4096', default=None, metavar='MAXSUB',
+                    help='with --features: also thin the features to their skeletons, by at most MAXSUB sub-iterations (1..2^20, default '
+                         '4096) (`skeleton`, `skeleton_nodes`, `skeleton_counts`, `skeleton_arg` in the output)')
     ap.add_argument('--device', type=int, default=0)
     a = ap.parse_args(argv)
+    max_sub = None
+    if a.skeleton is not None:
+        from sitrack_amd.features import skeleton_arg
+        if a.features is None:
+            sys.exit('ERROR: --skeleton: it thins the features of --features; give that flag too')
+        try:
+            max_sub = skeleton_arg(a.skeleton, '--skeleton')
+        except ValueError as e:
+            sys.exit('ERROR: %s' % e)
     reach = None
     if a.track is not None:
         from sitrack_amd.features import track_arg
@@ -203,6 +220,12 @@ def main(argv=None):
                 r['features'] = rf['table']
                 r['features_counts'] = np.array([rf['nfeat'], rf['ncomp'], rf['nactive']], dtype=np.int64)
                 r['features_arg'] = np.array([sit.FEAT_WHAT[what], sgn, thr, min_pix, conn], dtype=np.float64)
+                if max_sub is not None:
+                    from sitrack_amd import features as ft
+                    rs = ctx.skeleton_raster(ft.kept_labels(rf['labels'], min_pix), max_sub=max_sub, skel=False)
+                    r['skeleton'], r['skeleton_nodes'] = rs['table'], rs['nodes']
+                    r['skeleton_counts'] = np.array([rs['nfeat'], rs['nnode'], rs['nskel'], rs['nsub'], rs['converged']], dtype=np.int64)
+                    r['skeleton_arg'] = np.array([max_sub], dtype=np.int64)
                 if reach is not None:
                     # the features carried by their own cells to record K1, where the next window's map is drawn on the same grid
                     from sitrack_amd import features as ft
@@ -232,6 +255,13 @@ def main(argv=None):
         lengths = sit.feature_table(r['features'], tuple(r['grid'][:3]) + (r['owner'].shape[0], r['owner'].shape[1]))['length_km']
         print(' *** --features %s: %d features of >= %d pixels (%d components, %d active pixels), longest %s'
               % (a.features, n[0], feat[3], n[1], n[2], '%.3f km' % lengths.max() if len(lengths) else 'n/a'))
+    if max_sub is not None:
+        n = r['skeleton_counts']
+        lengths = sit.skeleton_table(r['skeleton'], tuple(r['grid'][:3]) + (r['owner'].shape[0], r['owner'].shape[1]))['length_km']
+        print(' *** --skeleton %d: %d features, %d skeleton pixels, %d nodes in %d sub-iterations, longest %s'
+              % (max_sub, n[0], n[2], n[1], n[3], '%.3f km' % lengths.max() if len(lengths) else 'n/a'))
+        if not n[4]:
+            print(' *** WARNING --skeleton: the thinning had not ended after %d sub-iterations; the skeleton is not final' % max_sub)
     if reach is not None:
         print(' *** --track %d: records %d -> %d against %d -> %d: %d pairs, %d continued, %d born, %d ended, %d merged, %d split'
               % ((reach, k0, k1, k1, k2, r['pairs_counts'][0]) + events))
