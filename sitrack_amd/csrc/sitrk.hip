@@ -127,14 +127,14 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     free_buoys(h);
     deform_release(h, true);
     coast_release(h, false, true);
-    quadmesh_release(h);
-    delaunay_release(h);
     mesh_release(h, true);
-    raster_release(h);
-    coarse_release(h);
-    label_release(h);
     track_release(h);
-    skeleton_release(h);
+    h->quad_timer.release();            // the modules whose timer is all they hold
+    h->dl_timer.release();
+    h->raster_timer.release();
+    h->coarse_timer.release();
+    h->label_timer.release();
+    h->skel_timer.release();
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);

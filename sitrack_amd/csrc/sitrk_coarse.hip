@@ -27,6 +27,7 @@
 
 #include "sitrk_cellmath.h"
 #include "sitrk_internal.h"
+#include "sitrk_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -142,30 +143,6 @@ __global__ __launch_bounds__(kCoThreads) void coarse_bounds_kernel(int64_t n, ui
     if (s == n - 1 || keys[s + 1] != k) end[k] = (int32_t)(s + 1);
 }
 
-// t[k] over all lanes of the workgroup in a fixed order: the xor butterfly inside a wave, then waves 0..3 in order (the pattern of
-// block_sum10 in sitrk_mesh.hip).  Lane k < 8 returns sum k, every other lane 0.  Every lane of the workgroup must call it.
-__device__ __forceinline__ double block_sum8(double (&t)[kCoCols], double (*sm)[kCoCols])
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kCoCols; k++) t[k] = t[k] + __shfl_xor(t[k], o);            // both partners form the same sum
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kCoCols; k++) sm[wave][k] = t[k];
-    }
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x < kCoCols) {
-        s = sm[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kCoThreads / 64; w++) s = s + sm[w][threadIdx.x];
-    }
-    return s;
-}
-
 // the eight table terms of one box v = n, A, AUx, AUy, AVx, AVy; amin = fmin*(L*L) of its level; all zero for a lane without a box
 __device__ __forceinline__ void table_terms(bool live, const double (&v)[6], double amin, double (&t)[kCoCols])
 {
@@ -212,7 +189,7 @@ __global__ __launch_bounds__(kCoThreads) void coarse_level0_kernel(int64_t npix,
     }
     double t[kCoCols];
     table_terms(live, v, amin, t);
-    const double s = block_sum8(t, sm);
+    const double s = block_sum<kCoCols, kCoThreads>(t, sm);
     if (threadIdx.x < kCoCols) partials[(int64_t)blockIdx.x * kCoCols + threadIdx.x] = s;
 }
 
@@ -244,7 +221,7 @@ __global__ __launch_bounds__(kCoThreads) void coarse_up_kernel(int nyc, int nxc,
     }
     double t[kCoCols];
     table_terms(live, v, amin, t);
-    const double s = block_sum8(t, sm);
+    const double s = block_sum<kCoCols, kCoThreads>(t, sm);
     if (threadIdx.x < kCoCols) partials[(int64_t)blockIdx.x * kCoCols + threadIdx.x] = s;
 }
 
@@ -261,7 +238,7 @@ __global__ __launch_bounds__(kCoThreads) void coarse_table_kernel(const int64_t 
 #pragma unroll
         for (int k = 0; k < kCoCols; k++) t[k] = t[k] + partials[(first + row) * kCoCols + k];
     }
-    const double s = block_sum8(t, sm);
+    const double s = block_sum<kCoCols, kCoThreads>(t, sm);
     if (threadIdx.x < kCoCols) table[(int64_t)blockIdx.x * kCoCols + threadIdx.x] = s;
 }
 
@@ -379,30 +356,28 @@ int coarse_run(sitrk_ctx *h, const char *fn, const CoarseJob &j, const CoarseGri
                double *boxes, double *table, int64_t *nin, int64_t *nout)
 {
     const int64_t npix = L.off[1];
-    for (hipEvent_t &e : h->coarse_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    h->coarse_timed = false;
+    RCCHK(h->coarse_timer.begin(h));
     int64_t rows[2 * SITRK_COARSE_MAXLEV] = {0};
     for (int l = 0; l < L.nlev; l++) { rows[2 * l] = L.row[l]; rows[2 * l + 1] = L.row[l + 1] - L.row[l]; }
     HIPCHK(upload(h, b.rows, rows, 2 * SITRK_COARSE_MAXLEV));
     HIPCHK(hipMemsetAsync(b.total, 0, 3 * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(b.start, 0, (size_t)npix * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(b.end, 0, (size_t)npix * sizeof(int32_t), h->stream));
-    HIPCHK(hipEventRecord(h->coarse_ev[0], h->stream));
+    RCCHK(h->coarse_timer.mark(h, 0));
     if (j.nC > 0) {
         if (j.block) launch_terms<4, 1>(h, j, g, b);
         else if (j.nv == 3) launch_terms<3, 0>(h, j, g, b);
         else launch_terms<4, 0>(h, j, g, b);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->coarse_ev[1], h->stream));
+    RCCHK(h->coarse_timer.mark(h, 1));
     if (j.nC > 0) {
         unsigned end_bit = 1;                                          // the keys run 0 .. npix, npix <= 2^24
         while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)npix) end_bit++;
         size_t tb = b.sort_bytes;
         HIPCHK(sort_pairs_u32(b.sort_tmp, &tb, b.k0, b.k1, b.v0, b.v1, (size_t)j.nC, end_bit, h->stream));
     }
-    HIPCHK(hipEventRecord(h->coarse_ev[2], h->stream));
+    RCCHK(h->coarse_timer.mark(h, 2));
     if (j.nC > 0) {
         hipLaunchKernelGGL(coarse_bounds_kernel, dim3((unsigned)nblk(j.nC)), dim3(kCoThreads), 0, h->stream, j.nC, (uint32_t)npix, b.k1, b.start,
                            b.end);
@@ -411,22 +386,22 @@ int coarse_run(sitrk_ctx *h, const char *fn, const CoarseJob &j, const CoarseGri
     hipLaunchKernelGGL(coarse_level0_kernel, dim3((unsigned)nblk(npix)), dim3(kCoThreads), 0, h->stream, npix, j.nC, b.start, b.end, b.v1, b.terms,
                        L.amin[0], b.pyr, b.partials);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->coarse_ev[3], h->stream));
+    RCCHK(h->coarse_timer.mark(h, 3));
     for (int l = 1; l < L.nlev; l++) {
         const int64_t nbox = (int64_t)L.ny[l] * L.nx[l];
         hipLaunchKernelGGL(coarse_up_kernel, dim3((unsigned)nblk(nbox)), dim3(kCoThreads), 0, h->stream, L.ny[l - 1], L.nx[l - 1],
                            b.pyr + 6 * L.off[l - 1], L.ny[l], L.nx[l], L.amin[l], b.pyr + 6 * L.off[l], b.partials + kCoCols * L.row[l]);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->coarse_ev[4], h->stream));
+    RCCHK(h->coarse_timer.mark(h, 4));
     hipLaunchKernelGGL(coarse_table_kernel, dim3((unsigned)L.nlev), dim3(kCoThreads), 0, h->stream, b.rows, b.partials, b.table);
     HIPCHK(hipGetLastError());
     if (j.nC > 0) {
         hipLaunchKernelGGL(coarse_count_kernel, dim3(1), dim3(kCoThreads), 0, h->stream, nblk(j.nC), b.counts, b.total);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->coarse_ev[5], h->stream));
-    h->coarse_timed = true;
+    RCCHK(h->coarse_timer.mark(h, 5));
+    h->coarse_timer.done();
     unsigned long long total[3] = {0, 0, 0};
     HIPCHK(download(h, total, b.total, 3));
     HIPCHK(download(h, table, b.table, (size_t)kCoCols * L.nlev));
@@ -439,15 +414,6 @@ int coarse_run(sitrk_ctx *h, const char *fn, const CoarseJob &j, const CoarseGri
 }
 
 }  // namespace
-
-void coarse_release(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->coarse_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->coarse_timed = false;
-}
 
 }  // namespace sitrk
 
@@ -514,13 +480,8 @@ SITRK_API int sitrk_mesh_coarse(sitrk_t *h, int mesh, int jrec1, double y0_km, d
     const CoarseLevels L = coarse_levels(ny, nx, d_km, nlev, fmin);
     CoarseBuf b;
     RCCHK(coarse_sort_bytes(h, nQ, &b.sort_bytes));
-    Carver size;
-    coarse_carve(size, b, nQ, L);
     MeshDeformDev m;
-    RCCHK(mesh_deform_core(h, mesh, jrec1, false, true, false, size.off, &m));
-    Carver place;
-    place.base = m.extra;
-    coarse_carve(place, b, nQ, L);
+    RCCHK(carve_behind_mesh(h, mesh, jrec1, false, true, false, [&](Carver &c) { coarse_carve(c, b, nQ, L); }, &m));
     CoarseJob j;
     j.nC = m.nQ; j.nP = h->nP; j.nv = 4; j.block = true; j.cells = m.quads; j.p0 = m.t0; j.p1 = m.p1; j.flag = m.status; j.only_status1 = true;
     j.T = (double)((int64_t)jrec1 - h->mesh[mesh].jrec0 + 1) * h->rdt;                 // one rounded product, as sitrk_mesh_deform
@@ -531,9 +492,8 @@ SITRK_API int sitrk_mesh_coarse(sitrk_t *h, int mesh, int jrec1, double y0_km, d
 SITRK_API int sitrk_coarse_kernel_ms(sitrk_t *h, float *terms_ms, float *sort_ms, float *level0_ms, float *pyramid_ms, float *table_ms)
 {
     NEED(h, "null handle");
-    NEED(h->coarse_timed, "sitrk_coarse_kernel_ms: no coarse-graining call has run its kernels yet");
+    NEED(h->coarse_timer.complete, "sitrk_coarse_kernel_ms: no coarse-graining call has run its kernels yet");
     float *out[5] = {terms_ms, sort_ms, level0_ms, pyramid_ms, table_ms};
-    for (int k = 0; k < 5; k++)
-        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], h->coarse_ev[k], h->coarse_ev[k + 1]));
+    for (int k = 0; k < 5; k++) RCCHK(h->coarse_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }

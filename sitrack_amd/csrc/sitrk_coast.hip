@@ -291,11 +291,7 @@ void coast_free(sitrk_ctx *h)
 void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy)
 {
     if (!grid_changed || h->coast.from_grid) coast_free(h);
-    if (destroy)
-        for (hipEvent_t &e : h->coast.ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+    if (destroy) h->coast.timer.release();
 }
 
 }  // namespace sitrk
@@ -324,8 +320,7 @@ SITRK_API int sitrk_coast_build(sitrk_t *h, int Nj, int Ni, const double *Yf, co
     HIPCHK(hipStreamSynchronize(st));                           // no query of the previous index is in flight
     coast_free(h);
     CoastState &cs = h->coast;
-    for (hipEvent_t &e : cs.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    RCCHK(cs.timer.create(h));
 
     // ---- the segments, in id order
     const size_t ncell = (size_t)Nj * Ni, nedge = 2 * ncell;
@@ -455,12 +450,12 @@ static int coast_run(sitrk_ctx *h, int64_t n, const pt *d_yx, const int32_t *per
                      double *dist, int32_t *seg)
 {
     CoastState &cs = h->coast;
-    HIPCHK(hipEventRecord(cs.ev[0], h->stream));
+    RCCHK(cs.timer.mark(h, 0));
     hipLaunchKernelGGL(coast_query_kernel, dim3(nblk(n)), dim3(kCoastThreads), 0, h->stream, cs.ix, n, d_yx, perm, rmax, r2, d_dist,
                        seg ? d_seg : (int32_t *)nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(cs.ev[1], h->stream));
-    cs.timed = true;
+    RCCHK(cs.timer.mark(h, 1));
+    cs.timer.done();
     HIPCHK(download(h, dist, d_dist, (size_t)n));
     if (seg) HIPCHK(download(h, seg, d_seg, (size_t)n));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -502,7 +497,6 @@ SITRK_API int sitrk_coast_dist_buoys(sitrk_t *h, double rmax_km, double *dist, i
 SITRK_API int sitrk_coast_kernel_ms(sitrk_t *h, float *query_ms)
 {
     NEED(h, "null handle");
-    NEED(h->coast.timed, "sitrk_coast_kernel_ms: no distance call has run its kernel yet");
-    if (query_ms) HIPCHK(hipEventElapsedTime(query_ms, h->coast.ev[0], h->coast.ev[1]));
-    return SITRK_OK;
+    NEED(h->coast.timer.complete, "sitrk_coast_kernel_ms: no distance call has run its kernel yet");
+    return h->coast.timer.elapsed(h, 0, query_ms);
 }

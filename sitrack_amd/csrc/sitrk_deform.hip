@@ -92,11 +92,7 @@ void deform_release(sitrk_ctx *h, bool destroy)
     if (h->deform_t0) (void)hipFree(h->deform_t0);
     h->deform_t0 = nullptr;
     h->deform_marked = false;
-    if (destroy)
-        for (hipEvent_t &e : h->deform_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+    if (destroy) h->deform_timer.release();
 }
 
 int deform_points_now(sitrk_ctx *h, pt *out)
@@ -127,14 +123,13 @@ static int deform_check(sitrk_ctx *h, const char *fn, int64_t nC, int nv, const 
     return SITRK_OK;
 }
 
-// the cell list goes up and the bad-index count is zeroed in front of the kernels; deform_ev[0] marks where the kernels start
+// the cell list goes up and the bad-index count is zeroed in front of the kernels; event 0 of the timer marks where the kernels start
 static int deform_begin(sitrk_ctx *h, int32_t *d_cells, const int32_t *cells, size_t count)
 {
-    for (hipEvent_t &e : h->deform_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    RCCHK(h->deform_timer.create(h));
     HIPCHK(upload(h, d_cells, cells, count));
     HIPCHK(hipMemsetAsync(h->counter, 0, sizeof(unsigned long long), h->stream));
-    HIPCHK(hipEventRecord(h->deform_ev[0], h->stream));
+    RCCHK(h->deform_timer.mark(h, 0));
     return SITRK_OK;
 }
 
@@ -143,7 +138,7 @@ static int deform_begin(sitrk_ctx *h, int32_t *d_cells, const int32_t *cells, si
 static int deform_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_p0, const pt *d_p1, int64_t nC, int nv, const int32_t *d_cells,
                       double T, double *d_out, int8_t *d_valid, double *out, int8_t *valid, int64_t *nvalid)
 {
-    HIPCHK(hipEventRecord(h->deform_ev[1], h->stream));
+    RCCHK(h->deform_timer.mark(h, 1));
     if (nv == 3)
         hipLaunchKernelGGL((deform_cells_kernel<3>), dim3(nblk(nC)), dim3(kDefThreads), 0, h->stream, nC, nP, d_cells, d_p0, d_p1, T, d_out,
                            d_valid, h->counter);
@@ -151,8 +146,8 @@ static int deform_run(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_p0, 
         hipLaunchKernelGGL((deform_cells_kernel<4>), dim3(nblk(nC)), dim3(kDefThreads), 0, h->stream, nC, nP, d_cells, d_p0, d_p1, T, d_out,
                            d_valid, h->counter);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->deform_ev[2], h->stream));
-    h->deform_timed = true;
+    RCCHK(h->deform_timer.mark(h, 2));
+    h->deform_timer.done();
     unsigned long long bad = 0;
     HIPCHK(download(h, &bad, h->counter, 1));
     HIPCHK(download(h, out, d_out, (size_t)5 * nC));
@@ -240,8 +235,8 @@ SITRK_API int sitrk_deform_since_mark(sitrk_t *h, int jrec1, int64_t nC, int nv,
 SITRK_API int sitrk_deform_kernel_ms(sitrk_t *h, float *points_ms, float *cells_ms)
 {
     NEED(h, "null handle");
-    NEED(h->deform_timed, "sitrk_deform_kernel_ms: no deformation call has run its kernels yet");
-    if (points_ms) HIPCHK(hipEventElapsedTime(points_ms, h->deform_ev[0], h->deform_ev[1]));
-    if (cells_ms) HIPCHK(hipEventElapsedTime(cells_ms, h->deform_ev[1], h->deform_ev[2]));
+    NEED(h->deform_timer.complete, "sitrk_deform_kernel_ms: no deformation call has run its kernels yet");
+    RCCHK(h->deform_timer.elapsed(h, 0, points_ms));
+    RCCHK(h->deform_timer.elapsed(h, 1, cells_ms));
     return SITRK_OK;
 }

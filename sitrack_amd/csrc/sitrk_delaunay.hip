@@ -356,15 +356,6 @@ hipError_t sort_rows_u64(void *tmp, size_t *tmp_bytes, const unsigned long long 
 
 }  // namespace
 
-void delaunay_release(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->dl_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->dl_timed = false;
-}
-
 }  // namespace sitrk
 
 using namespace sitrk;
@@ -413,12 +404,10 @@ void sitrk::dl_carve(Carver &c, DlBuffers &b, int64_t nP)
 int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, const int8_t *d_mask, const DlBuffers &b, double rmax_km,
                    int64_t *nT)
 {
-    const hipStream_t st = h->stream;
-    h->dl_timed = false;
-    for (hipEvent_t &e : h->dl_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    const hipStream_t st = h->stream;                    // the stream the timer marks
+    RCCHK(h->dl_timer.begin(h));
     HIPCHK(hipMemsetAsync(h->counter, 0, 4 * sizeof(unsigned long long), st));
-    HIPCHK(hipEventRecord(h->dl_ev[0], st));
+    RCCHK(h->dl_timer.mark(h, 0));
     hipLaunchKernelGGL(dl_init_kernel, dim3(1), dim3(64), 0, st, b.red);
     hipLaunchKernelGGL(dl_quant_kernel, dim3(nblk(nP) < 2048u ? nblk(nP) : 2048u), dim3(kDlThreads), 0, st, nP, d_pts, d_mask, b.xy, b.vertex, b.red);
     HIPCHK(hipGetLastError());
@@ -456,12 +445,12 @@ int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, co
         hipLaunchKernelGGL(dl_gather_kernel, dim3(nblk(nP)), dim3(kDlThreads), 0, st, g, nP, b.xy, b.k1, b.perm, b.xys, b.cbeg);
         hipLaunchKernelGGL(dl_dup_kernel, dim3(nblk(nv)), dim3(kDlThreads), 0, st, g, nv, b.xys, b.k1, b.perm, b.cbeg, b.xyv, b.vertex);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->dl_ev[1], st));
+        RCCHK(h->dl_timer.mark(h, 1));
         const int64_t cap_rows = 2 * nP;
         hipLaunchKernelGGL(dl_tri_kernel, dim3(nblk(nv)), dim3(kDlThreads), 0, st, g, nv, b.xyv, b.k1, b.perm, b.cbeg, cap_rows, b.rkey0,
                            b.rval0, h->counter);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->dl_ev[2], st));
+        RCCHK(h->dl_timer.mark(h, 2));
         HIPCHK(download(h, cnt, h->counter, 3));
         HIPCHK(hipStreamSynchronize(st));
         if (cnt[0] > (unsigned long long)cap_rows)
@@ -474,8 +463,8 @@ int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, co
             hipLaunchKernelGGL(dl_rows_kernel, dim3(nblk((int64_t)cnt[0])), dim3(kDlThreads), 0, st, (int64_t)cnt[0], b.rkey1, b.rval1, b.tris);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(h->dl_ev[3], st));
-        h->dl_timed = true;
+        RCCHK(h->dl_timer.mark(h, 3));
+        h->dl_timer.done();
     }
     h->dl_tests = cnt[1];
     h->dl_exact = cnt[2];
@@ -535,10 +524,9 @@ SITRK_API int sitrk_delaunay_buoys(sitrk_t *h, double rmax_km, int64_t cap, int3
 SITRK_API int sitrk_delaunay_kernel_ms(sitrk_t *h, float *bin_ms, float *tri_ms, float *compact_ms)
 {
     NEED(h, "null handle");
-    NEED(h->dl_timed, "sitrk_delaunay_kernel_ms: no delaunay call has run all its kernels yet");
-    if (bin_ms) HIPCHK(hipEventElapsedTime(bin_ms, h->dl_ev[0], h->dl_ev[1]));
-    if (tri_ms) HIPCHK(hipEventElapsedTime(tri_ms, h->dl_ev[1], h->dl_ev[2]));
-    if (compact_ms) HIPCHK(hipEventElapsedTime(compact_ms, h->dl_ev[2], h->dl_ev[3]));
+    NEED(h->dl_timer.complete, "sitrk_delaunay_kernel_ms: no delaunay call has run all its kernels yet");
+    float *out[3] = {bin_ms, tri_ms, compact_ms};
+    for (int k = 0; k < 3; k++) RCCHK(h->dl_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }
 

@@ -6,8 +6,23 @@
 
 #include "../../include/sitrk.h"
 #include "sitrk_geom.h"
+#include "sitrk_launch.h"
 
 namespace sitrk {
+
+// The timing events of one timed range of a module's last call -- event k and k + 1 lie around phase k -- and whether that call
+// recorded them all.  The sitrk_*_kernel_ms entry points refuse to read a timer that is not complete.
+template <int N>
+struct PhaseTimer {
+    hipEvent_t ev[N] = {};
+    bool complete = false;
+    int create(sitrk_ctx *h);                           // creates the events at the first use
+    int begin(sitrk_ctx *h);                            // ... and clears the flag
+    int mark(sitrk_ctx *h, int k);                      // records event k on the compute stream
+    void done() { complete = true; }
+    int elapsed(sitrk_ctx *h, int k, float *ms);        // phase k in ms; a null ms is skipped
+    void release();                                     // destroys the events, clears the flag
+};
 
 hipError_t sort_pairs_u32(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uint32_t *kout,
                           const int32_t *vin, int32_t *vout, size_t n, unsigned end_bit, hipStream_t s);
@@ -68,8 +83,7 @@ struct CoastState {
     pt *seg = nullptr;                  // the arrays of CoastIndex
     int32_t *sid = nullptr, *start = nullptr;
     CoastIndex ix;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // around the query kernel of the last distance call
-    bool timed = false;
+    PhaseTimer<2> timer;                // around the query kernel of the last distance call
 };
 
 // Quadrangles from triangles (sitrk_quadmesh.hip): the acceptance parameters as the kernels take them
@@ -242,56 +256,49 @@ struct sitrk_ctx {
     sitrk::pt *deform_t0 = nullptr;
     bool deform_marked = false;
     int deform_jrec0 = 0;
-    hipEvent_t deform_ev[3] = {nullptr, nullptr, nullptr};   // around the scatter pass and the cell kernel of the last deform call
-    bool deform_timed = false;
+    sitrk::PhaseTimer<3> deform_timer;  // around the scatter pass and the cell kernel of the last deform call
 
     sitrk::CoastState coast;            // distance to the coastline (sitrk_coast.hip)
 
     // quadrangles from triangles (sitrk_quadmesh.hip): events around the phases of the last call -- adjacency, scores, rounds, compaction
-    hipEvent_t quad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool quad_timed = false;
+    sitrk::PhaseTimer<5> quad_timer;
 
     // bounded Delaunay triangulation (sitrk_delaunay.hip): events around the phases of the last call -- binning, triangles,
     // compaction -- and its in-circle tests, all of them / those that took the 128-bit path
-    hipEvent_t dl_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool dl_timed = false;
+    sitrk::PhaseTimer<4> dl_timer;
     unsigned long long dl_tests = 0, dl_exact = 0;
 
-    // device-resident quadrangle meshes (sitrk_mesh.hip): freed with the buoys, whose indices they hold.  Events: [0],[1] around
-    // the device chain of the last build; [2]..[5] around the pass over the buoys, the cell kernel and the final sum of the last deform
+    // device-resident quadrangle meshes (sitrk_mesh.hip): freed with the buoys, whose indices they hold.  Events around the device
+    // chain of the last build, and around the pass over the buoys, the cell kernel and the final sum of the last deform
     sitrk::Mesh mesh[SITRK_MESH_MAX];
-    hipEvent_t mesh_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool mesh_build_timed = false, mesh_deform_timed = false;
+    sitrk::PhaseTimer<2> mesh_build_timer;
+    sitrk::PhaseTimer<4> mesh_deform_timer;
 
     // rasterised cells (sitrk_raster.hip): events around the fill with the cell kernel and around the gather kernel of the last
     // call; with the knob raster_count its centres found inside a drawn cell (= the atomics issued)
-    hipEvent_t raster_ev[3] = {nullptr, nullptr, nullptr};
-    bool raster_timed = false;
+    sitrk::PhaseTimer<3> raster_timer;
     int raster_count = 0;               // knob: count them (a measurement build of the cell kernel; never changes results)
     bool raster_counted = false;
     unsigned long long raster_claims = 0;
 
     // coarse-grained deformation (sitrk_coarse.hip): events around the five phases of the last call -- terms, sort, level 0,
     // pyramid, table
-    hipEvent_t coarse_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool coarse_timed = false;
+    sitrk::PhaseTimer<6> coarse_timer;
 
     // labelled features (sitrk_label.hip): events around the three phases of the last call -- mask, labels, table
-    hipEvent_t label_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool label_timed = false;
+    sitrk::PhaseTimer<4> label_timer;
 
     // features from window to window (sitrk_track.hip): the kept label maps, which outlive the buoys and the meshes, and the
-    // allocation the last replaced map left behind, taken again by the next call that fills a slot.  Events: [0]..[3] around the
-    // three phases of the last match -- keys, sort, rows --, [4],[5] around the two kernels of the last advect behind its rasters
+    // allocation the last replaced map left behind, taken again by the next call that fills a slot.  Events around the three
+    // phases of the last match -- keys, sort, rows --, and around the kernels of the last advect behind its rasters
     sitrk::KeptMap keep[SITRK_KEEP_MAX];
     int32_t *keep_spare = nullptr;
     size_t keep_spare_cap = 0;
-    hipEvent_t track_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool match_timed = false, advect_timed = false;
+    sitrk::PhaseTimer<4> match_timer;
+    sitrk::PhaseTimer<2> advect_timer;
 
     // skeletons of a label map (sitrk_skeleton.hip): events around the three phases of the last call -- thinning, table, nodes
-    hipEvent_t skel_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool skel_timed = false;
+    sitrk::PhaseTimer<4> skel_timer;
     int skeleton_batch = 0;             // knob: sub-iterations per launch of the thinning kernel, 1..8; 0 = as shipped (never changes results)
 
     // scratch for fetch / locate
@@ -310,15 +317,15 @@ int ensure_scratch(sitrk_ctx *h, size_t bytes);
 // sitrk_sample.hip reads a resident slot: the compute stream ordered behind an upload of `slot` still in flight on the copy
 // stream (sitrk.hip); *field = device address of field 0 u / 1 v / 2 siconc of the slot's slab
 int slot_order_read(sitrk_ctx *h, int slot, int field, const void **field_dev);
-// sitrk_deform.hip: frees the snapshot of sitrk_deform_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timing
-// events too
+// sitrk_deform.hip: frees the snapshot of sitrk_deform_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timer
+// too
 void deform_release(sitrk_ctx *h, bool destroy);
 // ... and queues its pass over the buoys on the compute stream: out (nP) = every buoy's position in the caller's order, NaN in y
 // for a buoy that is not alive now (sitrk_quadmesh.hip)
 int deform_points_now(sitrk_ctx *h, pt *out);
 // ... and the pass of sitrk_deform_since_mark: NaN in y also for a buoy whose record window does not cover [jrec0, jrec1] (sitrk_mesh.hip)
 int deform_points_span(sitrk_ctx *h, int jrec0, int jrec1, pt *out);
-// sitrk_mesh.hip: frees every mesh (free_buoys of sitrk.hip); destroy = the timing events too
+// sitrk_mesh.hip: frees every mesh (free_buoys of sitrk.hip); destroy = the timers too
 void mesh_release(sitrk_ctx *h, bool destroy);
 // ... and the body of sitrk_mesh_deform behind its argument checks (mesh_deform_check), everything left in the transient scratch:
 // the pass over the buoys, the cell kernel and, when asked for, the final sum are queued on the compute stream and the pointers
@@ -337,11 +344,9 @@ struct MeshDeformDev {
 int mesh_deform_check(sitrk_ctx *h, const char *fn, int mesh, int jrec1);
 int mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want_status, bool want_stats, size_t extra,
                      MeshDeformDev *r);
-// sitrk_raster.hip: destroys the timing events (sitrk_destroy)
-void raster_release(sitrk_ctx *h);
-// ... and the device side of its entry points, for a caller that goes on with the raster on the device (sitrk_label.hip): the grid's
-// checks, and the fill, cell and gather kernels queued on the compute stream.  cnt: three counters -- cells with a bad index, owned
-// pixels, and with the knob raster_count the centres inside a drawn cell.  out (5,nC) may be null when fields is
+// sitrk_raster.hip: the device side of its entry points, for a caller that goes on with the raster on the device (sitrk_label.hip):
+// the grid's checks, and the fill, cell and gather kernels queued on the compute stream.  cnt: three counters -- cells with a bad
+// index, owned pixels, and with the knob raster_count the centres inside a drawn cell.  out (5,nC) may be null when fields is
 struct RasterGrid {
     double y0, x0, d;
     int ny, nx;
@@ -361,27 +366,22 @@ struct RasterJob {
 };
 int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double d, int ny, int nx);
 int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g);
-// sitrk_label.hip: destroys the timing events (sitrk_destroy)
-void label_release(sitrk_ctx *h);
+// ... and the shape of a raster that is labelled, kept or thinned: ny, nx in 1..32768 and at most 2^28 pixels
+int check_raster_shape(sitrk_ctx *h, const char *fn, int ny, int nx);
+// sitrk_label.hip: the temporary storage, a multiple of 256 bytes, of a rocprim::exclusive_scan over n int32 values
+int scan_i32_bytes(sitrk_ctx *h, int64_t n, size_t *bytes);
 // ... and the body of sitrk_mesh_features behind the handle's check, for sitrk_mesh_features_keep (sitrk_track.hip): keep_map (ny*nx
 // on the device, may be null) receives the labels of the components of at least min_pix pixels, -1 elsewhere
 int mesh_features_body(sitrk_ctx *h, const char *fn, int mesh, int jrec1, int at_t1, double y0_km, double x0_km, double d_km, int ny,
                        int nx, int what, int sgn, double thr, int conn, int64_t min_pix, int64_t maxfeat, int32_t *labels, int64_t *table,
                        int64_t *nfeat, int64_t *ncomp, int64_t *nactive, int32_t *keep_map);
-// sitrk_track.hip: queues the kernel behind keep_map on the compute stream and synchronises; frees the kept maps and destroys the
-// timing events (sitrk_destroy)
+// sitrk_track.hip: queues the kernel behind keep_map on the compute stream and synchronises; frees the kept maps and releases the
+// timers (sitrk_destroy)
 int keep_from_labels(sitrk_ctx *h, int64_t npix, const int32_t *labels, const int32_t *flag, int32_t *keep_map);
 void track_release(sitrk_ctx *h);
-// sitrk_skeleton.hip: destroys the timing events (sitrk_destroy); the knob skeleton_batch behind its range check (sitrk_set_tuning)
-void skeleton_release(sitrk_ctx *h);
+// sitrk_skeleton.hip: the knob skeleton_batch behind its range check (sitrk_set_tuning)
 int skeleton_set_batch(sitrk_ctx *h, int value);
-// sitrk_coarse.hip: destroys the timing events (sitrk_destroy)
-void coarse_release(sitrk_ctx *h);
-// sitrk_quadmesh.hip: destroys the timing events (sitrk_destroy)
-void quadmesh_release(sitrk_ctx *h);
-// sitrk_delaunay.hip: destroys the timing events (sitrk_destroy)
-void delaunay_release(sitrk_ctx *h);
-// sitrk_coast.hip: frees the coast index (sitrk_destroy: the timing events too); grid_changed = only an index that was built from
+// sitrk_coast.hip: frees the coast index (sitrk_destroy: the timer too); grid_changed = only an index that was built from
 // the context's grid (sitrk_set_grid)
 void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy);
 
@@ -409,6 +409,46 @@ static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 namespace sitrk {
 
+template <int N>
+int PhaseTimer<N>::create(sitrk_ctx *h)
+{
+    for (hipEvent_t &e : ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    return SITRK_OK;
+}
+
+template <int N>
+int PhaseTimer<N>::begin(sitrk_ctx *h)
+{
+    RCCHK(create(h));
+    complete = false;
+    return SITRK_OK;
+}
+
+template <int N>
+int PhaseTimer<N>::mark(sitrk_ctx *h, int k)
+{
+    HIPCHK(hipEventRecord(ev[k], h->stream));
+    return SITRK_OK;
+}
+
+template <int N>
+int PhaseTimer<N>::elapsed(sitrk_ctx *h, int k, float *ms)
+{
+    if (ms) HIPCHK(hipEventElapsedTime(ms, ev[k], ev[k + 1]));
+    return SITRK_OK;
+}
+
+template <int N>
+void PhaseTimer<N>::release()
+{
+    for (hipEvent_t &e : ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    complete = false;
+}
+
 // Scratch carver: hands out typed pieces of one allocation in order, each rounded up to 256 bytes.  A layout is a callable that
 // takes its pieces from the Carver it is given; carve_scratch() runs it twice -- over a null base, where only the offsets add up,
 // to size h->scratch, then over h->scratch to place the pointers -- so the total requested and the placement come out of the
@@ -432,6 +472,21 @@ static int carve_scratch(sitrk_ctx *h, Layout &&layout)
     RCCHK(ensure_scratch(h, size.off));
     Carver place;
     place.base = (char *)h->scratch;
+    layout(place);
+    return SITRK_OK;
+}
+
+// The same two passes for a layout that lies behind the buffers of a mesh's deformation: the layout is sized, mesh_deform_core
+// carves that many bytes behind its own buffers and queues its kernels, and the layout is placed at m->extra
+template <typename Layout>
+static int carve_behind_mesh(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bool want_status, bool want_stats, Layout &&layout,
+                             MeshDeformDev *m)
+{
+    Carver size;
+    layout(size);
+    RCCHK(mesh_deform_core(h, mesh, jrec1, want_out, want_status, want_stats, size.off, m));
+    Carver place;
+    place.base = m->extra;
     layout(place);
     return SITRK_OK;
 }

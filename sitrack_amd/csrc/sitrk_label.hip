@@ -45,8 +45,6 @@ constexpr int kLbThreads = 256;
 constexpr int kLbTile = SITRK_LABEL_TILE;
 constexpr int kLbRowsPerWave = kLbTile / (kLbThreads / 64);
 constexpr int kLbCols = SITRK_FEAT_NCOLS;
-constexpr int kLbMaxSide = 32768;
-constexpr int64_t kLbMaxPixels = (int64_t)1 << 28;
 constexpr unsigned kLbFlagBlocks = 2048;           // 256 CUs x 8 resident workgroups
 constexpr int64_t kLbSpanWaves = 4 * 2048;         // ... and their waves, each with a span of pixels of its own
 constexpr int kLbMinTrips = 4;                     // pieces of 64 pixels in a span, on small rasters too
@@ -446,8 +444,6 @@ __global__ __launch_bounds__(kLbThreads) void label_table_kernel(int32_t npix, i
     if (lane == 0 && carry_r >= 0) table_flush(table, carry_r, carry_s, carry_lo_j, carry_hi_j, carry_lo_i, carry_hi_i);
 }
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + kLbThreads - 1) / kLbThreads); }
-
 // the scratch of one call behind whatever makes its mask.  `flag` lies over `parent` and `row` over `cnt`: the parents are dead
 // once the labels are flat, the counters once the flags are set
 struct LabelBuf {
@@ -471,20 +467,9 @@ void label_carve(Carver &c, LabelBuf &b, const LabelJob &j)
     c.take(b.table, (size_t)j.maxfeat * kLbCols); c.take(b.tot, kTotN); c.take(b.scan_tmp, b.scan_bytes);
 }
 
-int label_scan_bytes(sitrk_ctx *h, int64_t npix, size_t *bytes)
-{
-    *bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, *bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)npix, rocprim::plus<int32_t>(),
-                                   h->stream));
-    *bytes = align256(*bytes);
-    return SITRK_OK;
-}
-
 int label_check(sitrk_ctx *h, const char *fn, int ny, int nx, int conn, int64_t min_pix, int64_t maxfeat, const int64_t *table)
 {
-    if (ny < 1 || nx < 1 || ny > kLbMaxSide || nx > kLbMaxSide)
-        return fail(h, SITRK_EINVAL, "%s: ny and nx must be in 1..%d (got %d, %d)", fn, kLbMaxSide, ny, nx);
-    if ((int64_t)ny * nx > kLbMaxPixels) return fail(h, SITRK_EINVAL, "%s: ny*nx = %lld exceeds 2^28 pixels", fn, (long long)ny * nx);
+    RCCHK(check_raster_shape(h, fn, ny, nx));
     if (conn != 4 && conn != 8) return fail(h, SITRK_EINVAL, "%s: conn must be 4 (edge neighbours) or 8 (edge and corner neighbours), got %d", fn, conn);
     if (min_pix < 1) return fail(h, SITRK_EINVAL, "%s: min_pix must be >= 1 (got %lld)", fn, (long long)min_pix);
     if (maxfeat < 0) return fail(h, SITRK_EINVAL, "%s: maxfeat must be >= 0 (got %lld)", fn, (long long)maxfeat);
@@ -492,15 +477,8 @@ int label_check(sitrk_ctx *h, const char *fn, int ny, int nx, int conn, int64_t 
     return SITRK_OK;
 }
 
-int label_events(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->label_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    h->label_timed = false;
-    return SITRK_OK;
-}
-
-// everything behind the mask on the device, between label_ev[1] and label_ev[3]: queues the kernels and the downloads, synchronises
+// everything behind the mask on the device, phases 1 and 2 of the label timer (the caller has begun it and marked the mask's
+// phase): queues the kernels and the downloads, synchronises
 int label_run(sitrk_ctx *h, const char *fn, const LabelJob &j, const LabelBuf &b, int32_t *labels, int64_t *table, int64_t *nfeat,
               int64_t *ncomp, int64_t *nactive)
 {
@@ -509,7 +487,7 @@ int label_run(sitrk_ctx *h, const char *fn, const LabelJob &j, const LabelBuf &b
     int32_t *flag = b.parent, *row = b.cnt;
     HIPCHK(hipMemsetAsync(b.tot, 0, kTotN * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(b.cnt, 0, (size_t)npix * sizeof(int32_t), h->stream));
-    HIPCHK(hipEventRecord(h->label_ev[1], h->stream));
+    RCCHK(h->label_timer.mark(h, 1));
     const dim3 tiles((unsigned)((j.nx + kLbTile - 1) / kLbTile), (unsigned)((j.ny + kLbTile - 1) / kLbTile));
     hipLaunchKernelGGL(label_tile_kernel, tiles, dim3(kLbThreads), 0, h->stream, j.ny, j.nx, conn8, b.mask, b.parent, b.tot);
     HIPCHK(hipGetLastError());
@@ -521,30 +499,26 @@ int label_run(sitrk_ctx *h, const char *fn, const LabelJob &j, const LabelBuf &b
                            b.tot);
         HIPCHK(hipGetLastError());
     }
-    // the waves of the flatten and table kernels: `wtrips` pieces of 64 pixels each, at least kLbMinTrips, at most kLbSpanWaves waves
-    const int64_t pieces = (npix + 63) / 64;
-    const int64_t want = (pieces + kLbSpanWaves - 1) / kLbSpanWaves;
-    const int wtrips = (int)(want > kLbMinTrips ? want : kLbMinTrips);
-    const unsigned wblocks = (unsigned)(((pieces + wtrips - 1) / wtrips + kLbThreads / 64 - 1) / (kLbThreads / 64));
-    hipLaunchKernelGGL(label_flatten_kernel, dim3(wblocks), dim3(kLbThreads), 0, h->stream, (int32_t)npix, wtrips, b.parent, b.labels, b.cnt,
-                       b.tot);
+    const WaveSpans ws(npix, kLbThreads, kLbSpanWaves, kLbMinTrips);   // the waves of the flatten and table kernels
+    hipLaunchKernelGGL(label_flatten_kernel, dim3(ws.blocks), dim3(kLbThreads), 0, h->stream, (int32_t)npix, ws.trips, b.parent, b.labels,
+                       b.cnt, b.tot);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->label_ev[2], h->stream));
-    const unsigned fblocks = nblk(npix) < kLbFlagBlocks ? nblk(npix) : kLbFlagBlocks;
-    const int trips = (int)((npix + (int64_t)fblocks * kLbThreads - 1) / ((int64_t)fblocks * kLbThreads));
-    hipLaunchKernelGGL(label_flag_kernel, dim3(fblocks), dim3(kLbThreads), 0, h->stream, npix, trips, j.min_pix, b.labels, b.cnt, flag, b.tot);
+    RCCHK(h->label_timer.mark(h, 2));
+    const Strided fs(npix, kLbThreads, kLbFlagBlocks);
+    hipLaunchKernelGGL(label_flag_kernel, dim3(fs.blocks), dim3(kLbThreads), 0, h->stream, npix, fs.trips, j.min_pix, b.labels, b.cnt, flag,
+                       b.tot);
     HIPCHK(hipGetLastError());
     size_t tb = b.scan_bytes;
     HIPCHK(rocprim::exclusive_scan(b.scan_tmp, tb, flag, row, 0, (size_t)npix, rocprim::plus<int32_t>(), h->stream));
-    hipLaunchKernelGGL(label_rows_kernel, dim3(nblk(npix)), dim3(kLbThreads), 0, h->stream, npix, j.maxfeat, flag, row, b.table, b.tot);
+    hipLaunchKernelGGL(label_rows_kernel, dim3(nblk(npix, kLbThreads)), dim3(kLbThreads), 0, h->stream, npix, j.maxfeat, flag, row, b.table, b.tot);
     HIPCHK(hipGetLastError());
     if (j.maxfeat > 0) {
-        hipLaunchKernelGGL(label_table_kernel, dim3(wblocks), dim3(kLbThreads), 0, h->stream, (int32_t)npix, wtrips, j.ny, j.nx, j.maxfeat, b.labels,
-                           flag, row, b.table);
+        hipLaunchKernelGGL(label_table_kernel, dim3(ws.blocks), dim3(kLbThreads), 0, h->stream, (int32_t)npix, ws.trips, j.ny, j.nx, j.maxfeat,
+                           b.labels, flag, row, b.table);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->label_ev[3], h->stream));
-    h->label_timed = true;
+    RCCHK(h->label_timer.mark(h, 3));
+    h->label_timer.done();
     unsigned long long tot[kTotN] = {0, 0, 0, 0};
     HIPCHK(download(h, tot, b.tot, kTotN));
     if (labels) HIPCHK(download(h, labels, b.labels, (size_t)npix));
@@ -565,13 +539,12 @@ int label_run(sitrk_ctx *h, const char *fn, const LabelJob &j, const LabelBuf &b
 
 }  // namespace
 
-void label_release(sitrk_ctx *h)
+int scan_i32_bytes(sitrk_ctx *h, int64_t n, size_t *bytes)
 {
-    for (hipEvent_t &e : h->label_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->label_timed = false;
+    *bytes = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, *bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)n, rocprim::plus<int32_t>(), h->stream));
+    *bytes = align256(*bytes);
+    return SITRK_OK;
 }
 
 }  // namespace sitrk
@@ -592,10 +565,10 @@ SITRK_API int sitrk_label_raster(sitrk_t *h, int ny, int nx, const int8_t *activ
     LabelJob j;
     j.ny = ny; j.nx = nx; j.conn = conn; j.min_pix = min_pix; j.maxfeat = maxfeat;
     LabelBuf b;
-    RCCHK(label_scan_bytes(h, (int64_t)ny * nx, &b.scan_bytes));
+    RCCHK(scan_i32_bytes(h, (int64_t)ny * nx, &b.scan_bytes));
     RCCHK(carve_scratch(h, [&](Carver &c) { label_carve(c, b, j); }));
-    RCCHK(label_events(h));
-    HIPCHK(hipEventRecord(h->label_ev[0], h->stream));
+    RCCHK(h->label_timer.begin(h));
+    RCCHK(h->label_timer.mark(h, 0));
     HIPCHK(upload(h, b.mask, active, (size_t)ny * nx));
     return label_run(h, fn, j, b, labels, table, nfeat, ncomp, nactive);
 }
@@ -623,26 +596,21 @@ int sitrk::mesh_features_body(sitrk_ctx *h, const char *fn, int mesh, int jrec1,
     j.ny = ny; j.nx = nx; j.conn = conn; j.min_pix = min_pix; j.maxfeat = maxfeat;
     LabelBuf b;
     HIPCHK(hipSetDevice(h->device));
-    RCCHK(label_scan_bytes(h, npix, &b.scan_bytes));
+    RCCHK(scan_i32_bytes(h, npix, &b.scan_bytes));
     int32_t *d_owner; unsigned long long *d_cnt;
     auto layout = [&](Carver &c) { c.take(d_owner, npix); c.take(d_cnt, 3); label_carve(c, b, j); };
-    Carver size;
-    layout(size);
     MeshDeformDev m;
-    RCCHK(mesh_deform_core(h, mesh, jrec1, true, true, false, size.off, &m));
-    Carver place;
-    place.base = m.extra;
-    layout(place);
+    RCCHK(carve_behind_mesh(h, mesh, jrec1, true, true, false, layout, &m));
     RasterJob r;
     r.nC = m.nQ; r.nP = h->nP; r.nv = 4; r.flag = m.status; r.owner = d_owner; r.cnt = d_cnt;
     if (at_t1) { r.cells = m.quads; r.pts = m.p1; r.only_status1 = true; }
     else { r.block = true; r.pts = m.t0; }
     const RasterGrid g = {y0_km, x0_km, d_km, ny, nx};
     RCCHK(raster_run(h, r, g));
-    RCCHK(label_events(h));
-    HIPCHK(hipEventRecord(h->label_ev[0], h->stream));
+    RCCHK(h->label_timer.begin(h));
+    RCCHK(h->label_timer.mark(h, 0));
     const double thr2 = thr * thr;
-    hipLaunchKernelGGL(label_mask_kernel, dim3(nblk(npix)), dim3(kLbThreads), 0, h->stream, npix, m.nQ, d_owner, m.out, what, (double)sgn, thr,
+    hipLaunchKernelGGL(label_mask_kernel, dim3(nblk(npix, kLbThreads)), dim3(kLbThreads), 0, h->stream, npix, m.nQ, d_owner, m.out, what, (double)sgn, thr,
                        thr2, b.mask);
     HIPCHK(hipGetLastError());
     unsigned long long cnt[3] = {0, 0, 0};
@@ -665,9 +633,8 @@ SITRK_API int sitrk_mesh_features(sitrk_t *h, int mesh, int jrec1, int at_t1, do
 SITRK_API int sitrk_features_kernel_ms(sitrk_t *h, float *mask_ms, float *label_ms, float *table_ms)
 {
     NEED(h, "null handle");
-    NEED(h->label_timed, "sitrk_features_kernel_ms: no labelling call has run its kernels yet");
+    NEED(h->label_timer.complete, "sitrk_features_kernel_ms: no labelling call has run its kernels yet");
     float *out[3] = {mask_ms, label_ms, table_ms};
-    for (int k = 0; k < 3; k++)
-        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], h->label_ev[k], h->label_ev[k + 1]));
+    for (int k = 0; k < 3; k++) RCCHK(h->label_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }

@@ -21,6 +21,7 @@
 
 #include "sitrk_cellmath.h"
 #include "sitrk_internal.h"
+#include "sitrk_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -46,30 +47,6 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_t0_kernel(int64_t nQ, const
     const int4 q = quads[c];
     const pt a0 = pts[q.x], a1 = pts[q.y], a2 = pts[q.z], a3 = pts[q.w];
     t0[4 * c] = a0; t0[4 * c + 1] = a1; t0[4 * c + 2] = a2; t0[4 * c + 3] = a3;
-}
-
-// t[k] over all lanes of the workgroup in a fixed order: the xor butterfly inside a wave, then waves 0..3 in order.  Lane k < 10
-// returns sum k, every other lane 0.  Every lane of the workgroup must call it.
-__device__ __forceinline__ double block_sum10(double (&t)[kMeshStats], double (*sm)[kMeshStats])
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kMeshStats; k++) t[k] = t[k] + __shfl_xor(t[k], o);          // both partners form the same sum
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kMeshStats; k++) sm[wave][k] = t[k];
-    }
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x < kMeshStats) {
-        s = sm[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kMeshThreads / 64; w++) s = s + sm[w][threadIdx.x];
-    }
-    return s;
 }
 
 __global__ __launch_bounds__(kMeshThreads) void mesh_cells_kernel(int64_t nQ, const int4 *__restrict__ quads, const pt *__restrict__ t0,
@@ -116,7 +93,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_cells_kernel(int64_t nQ, co
     t[7] = s1 ? m1 : 0.0;
     t[8] = s1 ? m2 : 0.0;
     t[9] = s1 ? m3 : 0.0;
-    const double s = block_sum10(t, sm);
+    const double s = block_sum<kMeshStats, kMeshThreads>(t, sm);
     if (threadIdx.x < kMeshStats) partials[(int64_t)blockIdx.x * kMeshStats + threadIdx.x] = s;
 }
 
@@ -130,7 +107,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_sum_kernel(int64_t nrows, c
 #pragma unroll
         for (int k = 0; k < kMeshStats; k++) t[k] = t[k] + partials[row * kMeshStats + k];
     }
-    const double s = block_sum10(t, sm);
+    const double s = block_sum<kMeshStats, kMeshThreads>(t, sm);
     if (threadIdx.x < kMeshStats) stats[threadIdx.x] = s;
 }
 
@@ -148,13 +125,10 @@ void mesh_free_one(Mesh &m)
 void mesh_release(sitrk_ctx *h, bool destroy)
 {
     for (Mesh &m : h->mesh) mesh_free_one(m);
-    h->mesh_deform_timed = false;
+    h->mesh_deform_timer.complete = false;
     if (destroy) {
-        for (hipEvent_t &e : h->mesh_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        h->mesh_build_timed = false;
+        h->mesh_build_timer.release();
+        h->mesh_deform_timer.release();
     }
 }
 
@@ -172,13 +146,6 @@ static int mesh_check(sitrk_ctx *h, const char *fn, int mesh, bool need_built)
     return SITRK_OK;
 }
 
-static int mesh_events(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->mesh_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    return SITRK_OK;
-}
-
 SITRK_API int sitrk_mesh_build(sitrk_t *h, int mesh, int jrec0, double rmax_km, const int8_t *mask, double cos_lo, double cos_hi,
                                double ratio_min, double area_min, double area_max, int64_t *nT, int64_t *nQ, int *rounds)
 {
@@ -193,8 +160,7 @@ SITRK_API int sitrk_mesh_build(sitrk_t *h, int mesh, int jrec0, double rmax_km, 
     if (nQ) *nQ = 0;
     if (rounds) *rounds = 0;
     HIPCHK(hipSetDevice(h->device));
-    RCCHK(mesh_events(h));
-    h->mesh_build_timed = false;
+    RCCHK(h->mesh_build_timer.begin(h));
     const QuadParams par = quad_params(cos_lo, cos_hi, ratio_min, area_min, area_max);
     // one layout for the whole chain: the points, the mask, the buffers of both cores (nT <= 2 nP - 5 triangles)
     pt *d_pts; int8_t *d_mask;
@@ -203,7 +169,7 @@ SITRK_API int sitrk_mesh_build(sitrk_t *h, int mesh, int jrec0, double rmax_km, 
     RCCHK(dl_sort_bytes(h, nP, &db.sort_bytes));
     RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_pts, nP); c.take(d_mask, nP); dl_carve(c, db, nP); quad_carve(c, qb, 2 * nP); }));
     if (mask) HIPCHK(upload(h, d_mask, mask, nP));
-    HIPCHK(hipEventRecord(h->mesh_ev[0], h->stream));
+    RCCHK(h->mesh_build_timer.mark(h, 0));
     RCCHK(deform_points_now(h, d_pts));                  // NaN in y: not alive now
     if (mask) {
         hipLaunchKernelGGL(mesh_mask_kernel, dim3(nblk(nP)), dim3(kMeshThreads), 0, h->stream, nP, d_mask, d_pts);
@@ -236,9 +202,9 @@ SITRK_API int sitrk_mesh_build(sitrk_t *h, int mesh, int jrec0, double rmax_km, 
             return fail(h, SITRK_EHIP, "%s: copying the quadrangles -> %s", fn, hipGetErrorString(e));
         }
     }
-    HIPCHK(hipEventRecord(h->mesh_ev[1], h->stream));
+    RCCHK(h->mesh_build_timer.mark(h, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->mesh_build_timed = true;
+    h->mesh_build_timer.done();
     mesh_free_one(h->mesh[mesh]);
     h->mesh[mesh] = m;
     if (nT) *nT = nt;
@@ -296,7 +262,6 @@ int sitrk::mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bo
     const int64_t nQ = m.nQ, nP = h->nP;
     const double T = (double)((int64_t)jrec1 - m.jrec0 + 1) * h->rdt;                  // one rounded product
     HIPCHK(hipSetDevice(h->device));
-    RCCHK(mesh_events(h));
     const int64_t nb = nblk(nQ);
     pt *d_p1; double *d_out, *d_part, *d_stats; int8_t *d_status; char *d_extra;
     RCCHK(carve_scratch(h, [&](Carver &c) {
@@ -307,20 +272,20 @@ int sitrk::mesh_deform_core(sitrk_ctx *h, int mesh, int jrec1, bool want_out, bo
     *r = MeshDeformDev();
     r->extra = d_extra;
     if (nQ == 0) return SITRK_OK;
-    h->mesh_deform_timed = false;
-    HIPCHK(hipEventRecord(h->mesh_ev[2], h->stream));
+    RCCHK(h->mesh_deform_timer.begin(h));
+    RCCHK(h->mesh_deform_timer.mark(h, 0));
     RCCHK(deform_points_span(h, m.jrec0, jrec1, d_p1));
-    HIPCHK(hipEventRecord(h->mesh_ev[3], h->stream));
+    RCCHK(h->mesh_deform_timer.mark(h, 1));
     hipLaunchKernelGGL(mesh_cells_kernel, dim3((unsigned)nb), dim3(kMeshThreads), 0, h->stream, nQ, (const int4 *)m.quads, m.t0, d_p1, T, m.par,
                        want_out ? d_out : nullptr, want_status ? d_status : nullptr, want_stats ? d_part : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->mesh_ev[4], h->stream));
+    RCCHK(h->mesh_deform_timer.mark(h, 2));
     if (want_stats) {
         hipLaunchKernelGGL(mesh_sum_kernel, dim3(1), dim3(kMeshThreads), 0, h->stream, nb, d_part, d_stats);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->mesh_ev[5], h->stream));
-    h->mesh_deform_timed = true;
+    RCCHK(h->mesh_deform_timer.mark(h, 3));
+    h->mesh_deform_timer.done();
     r->nQ = nQ; r->quads = m.quads; r->t0 = m.t0; r->p1 = d_p1;
     r->out = want_out ? d_out : nullptr; r->status = want_status ? d_status : nullptr; r->stats = want_stats ? d_stats : nullptr;
     return SITRK_OK;
@@ -362,14 +327,13 @@ SITRK_API int sitrk_mesh_kernel_ms(sitrk_t *h, float *build_ms, float *points_ms
 {
     NEED(h, "null handle");
     if (build_ms) {
-        NEED(h->mesh_build_timed, "sitrk_mesh_kernel_ms: no sitrk_mesh_build has run to its end yet");
-        HIPCHK(hipEventElapsedTime(build_ms, h->mesh_ev[0], h->mesh_ev[1]));
+        NEED(h->mesh_build_timer.complete, "sitrk_mesh_kernel_ms: no sitrk_mesh_build has run to its end yet");
+        RCCHK(h->mesh_build_timer.elapsed(h, 0, build_ms));
     }
     if (points_ms || cells_ms || stats_ms) {
-        NEED(h->mesh_deform_timed, "sitrk_mesh_kernel_ms: no sitrk_mesh_deform has run its kernels yet");
-        if (points_ms) HIPCHK(hipEventElapsedTime(points_ms, h->mesh_ev[2], h->mesh_ev[3]));
-        if (cells_ms) HIPCHK(hipEventElapsedTime(cells_ms, h->mesh_ev[3], h->mesh_ev[4]));
-        if (stats_ms) HIPCHK(hipEventElapsedTime(stats_ms, h->mesh_ev[4], h->mesh_ev[5]));
+        NEED(h->mesh_deform_timer.complete, "sitrk_mesh_kernel_ms: no sitrk_mesh_deform has run its kernels yet");
+        float *out[3] = {points_ms, cells_ms, stats_ms};
+        for (int k = 0; k < 3; k++) RCCHK(h->mesh_deform_timer.elapsed(h, k, out[k]));
     }
     return SITRK_OK;
 }

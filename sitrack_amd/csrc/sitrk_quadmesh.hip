@@ -306,18 +306,7 @@ __global__ __launch_bounds__(kQmBlock) void quad_emit_kernel(int64_t nT, int64_t
     ((int4 *)quads)[o] = row;
 }
 
-inline unsigned nblk(int64_t n, int bs = kQmThreads) { return (unsigned)((n + bs - 1) / bs); }
-
 }  // namespace
-
-void quadmesh_release(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->quad_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->quad_timed = false;
-}
 
 }  // namespace sitrk
 
@@ -368,37 +357,35 @@ void sitrk::quad_carve(Carver &c, QuadBuffers &b, int64_t nT)
 int sitrk::quad_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, int64_t nT, const int32_t *d_tris, const QuadBuffers &b,
                      const QuadParams &c, int64_t *nQ, int *rounds)
 {
-    h->quad_timed = false;
-    for (hipEvent_t &e : h->quad_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    RCCHK(h->quad_timer.begin(h));
     const uint64_t slots = quad_slots(nT);
     if (slots > b.slots) return fail(h, SITRK_EINVAL, "%s: %lld triangles do not fit the buffers", fn, (long long)nT);
     EdgeTable tab = b.tab;
     tab.mask = slots - 1;
     HIPCHK(hipMemsetAsync(h->counter, 0, 2 * sizeof(unsigned long long), h->stream));
-    HIPCHK(hipEventRecord(h->quad_ev[0], h->stream));
+    RCCHK(h->quad_timer.mark(h, 0));
     HIPCHK(hipMemsetAsync(tab.key, 0xff, slots * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(tab.val, 0, slots * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(b.mate, 0xff, (size_t)nT * sizeof(int32_t), h->stream));                  // -1: unmatched
-    hipLaunchKernelGGL(quad_tri_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, nP, d_tris, d_pts, tab, b.live, h->counter);
+    hipLaunchKernelGGL(quad_tri_kernel, dim3(nblk(nT, kQmThreads)), dim3(kQmThreads), 0, h->stream, nT, nP, d_tris, d_pts, tab, b.live, h->counter);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->quad_ev[1], h->stream));
+    RCCHK(h->quad_timer.mark(h, 1));
     unsigned long long cnt[2] = {0, 0};
     HIPCHK(download(h, cnt, h->counter, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (cnt[0])                                                                                     // before any kernel follows an index
         return fail(h, SITRK_EINDEX, "%s: %llu triangle(s) have a vertex index outside [0, %lld)", fn, cnt[0], (long long)nP);
-    hipLaunchKernelGGL(quad_score_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, d_tris, d_pts, tab, b.live, c, b.score, b.nbr);
+    hipLaunchKernelGGL(quad_score_kernel, dim3(nblk(nT, kQmThreads)), dim3(kQmThreads), 0, h->stream, nT, d_tris, d_pts, tab, b.live, c, b.score, b.nbr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->quad_ev[2], h->stream));
+    RCCHK(h->quad_timer.mark(h, 2));
     const int64_t max_rounds = nT / 2 + 1;
     int64_t nround = 0;
     unsigned long long before = 0;
     for (;;) {
         if (nround == max_rounds)
             return fail(h, SITRK_EINVAL, "%s: the matching has not come to rest after %lld rounds (%llu pairs)", fn, (long long)nround, before);
-        hipLaunchKernelGGL(quad_pick_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, d_tris, b.score, b.nbr, b.mate, b.pick);
-        hipLaunchKernelGGL(quad_match_kernel, dim3(nblk(nT)), dim3(kQmThreads), 0, h->stream, nT, b.pick, b.mate, h->counter + 1);
+        hipLaunchKernelGGL(quad_pick_kernel, dim3(nblk(nT, kQmThreads)), dim3(kQmThreads), 0, h->stream, nT, d_tris, b.score, b.nbr, b.mate, b.pick);
+        hipLaunchKernelGGL(quad_match_kernel, dim3(nblk(nT, kQmThreads)), dim3(kQmThreads), 0, h->stream, nT, b.pick, b.mate, h->counter + 1);
         HIPCHK(hipGetLastError());
         HIPCHK(download(h, cnt + 1, h->counter + 1, 1));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -406,15 +393,15 @@ int sitrk::quad_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, 
         if (cnt[1] == before) break;
         before = cnt[1];
     }
-    HIPCHK(hipEventRecord(h->quad_ev[3], h->stream));
+    RCCHK(h->quad_timer.mark(h, 3));
     const int64_t nb = nblk(nT, kQmBlock);
     hipLaunchKernelGGL(quad_count_kernel, dim3((unsigned)nb), dim3(kQmBlock), 0, h->stream, nT, b.mate, b.block_count);
     hipLaunchKernelGGL(quad_scan_kernel, dim3(1), dim3(kQmBlock), 0, h->stream, nb, b.block_count, b.block_off, h->counter);
     hipLaunchKernelGGL(quad_emit_kernel, dim3((unsigned)nb), dim3(kQmBlock), 0, h->stream, nT, nT / 2, d_tris, d_pts, b.live, b.mate, b.block_off,
                        b.quads, b.tri_quad);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->quad_ev[4], h->stream));
-    h->quad_timed = true;
+    RCCHK(h->quad_timer.mark(h, 4));
+    h->quad_timer.done();
     HIPCHK(download(h, cnt, h->counter, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (cnt[0] != cnt[1] || cnt[0] > (unsigned long long)(nT / 2))
@@ -469,7 +456,7 @@ SITRK_API int sitrk_tri2quad(sitrk_t *h, int64_t nP, const double *yx, const int
     HIPCHK(upload(h, d_pts, yx, nP));
     if (mask) {
         HIPCHK(upload(h, d_mask, mask, nP));
-        hipLaunchKernelGGL(quad_mask_kernel, dim3(nblk(nP)), dim3(kQmThreads), 0, h->stream, nP, d_mask, d_pts);
+        hipLaunchKernelGGL(quad_mask_kernel, dim3(nblk(nP, kQmThreads)), dim3(kQmThreads), 0, h->stream, nP, d_mask, d_pts);
         HIPCHK(hipGetLastError());
     }
     RCCHK(quad_run(h, fn, nP, d_pts, nT, tris, b, quad_params(cos_lo, cos_hi, ratio_min, area_min, area_max), quads, tri_quad, &nq, &nr));
@@ -506,10 +493,8 @@ SITRK_API int sitrk_tri2quad_buoys(sitrk_t *h, int64_t nT, const int32_t *tris, 
 SITRK_API int sitrk_tri2quad_kernel_ms(sitrk_t *h, float *adjacency_ms, float *score_ms, float *rounds_ms, float *compact_ms)
 {
     NEED(h, "null handle");
-    NEED(h->quad_timed, "sitrk_tri2quad_kernel_ms: no tri2quad call has run all its kernels yet");
-    if (adjacency_ms) HIPCHK(hipEventElapsedTime(adjacency_ms, h->quad_ev[0], h->quad_ev[1]));
-    if (score_ms) HIPCHK(hipEventElapsedTime(score_ms, h->quad_ev[1], h->quad_ev[2]));
-    if (rounds_ms) HIPCHK(hipEventElapsedTime(rounds_ms, h->quad_ev[2], h->quad_ev[3]));
-    if (compact_ms) HIPCHK(hipEventElapsedTime(compact_ms, h->quad_ev[3], h->quad_ev[4]));
+    NEED(h->quad_timer.complete, "sitrk_tri2quad_kernel_ms: no tri2quad call has run all its kernels yet");
+    float *out[4] = {adjacency_ms, score_ms, rounds_ms, compact_ms};
+    for (int k = 0; k < 4; k++) RCCHK(h->quad_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }

@@ -35,6 +35,7 @@ namespace {
 
 constexpr int kRasThreads = 256;
 constexpr int64_t kRasMaxPixels = (int64_t)1 << 28;
+constexpr int kRasMaxSide = 32768;                 // of a raster that is labelled, kept or thinned (check_raster_shape)
 constexpr int32_t kRasNone = INT32_MAX;
 constexpr unsigned kRasGatherBlocks = 2048;        // 256 CUs x 8 resident workgroups
 
@@ -222,12 +223,10 @@ int raster_finish(sitrk_ctx *h, const unsigned long long *d_cnt, unsigned long l
 int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
 {
     const int64_t npix = (int64_t)g.ny * g.nx;
-    for (hipEvent_t &e : h->raster_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    h->raster_timed = false;
+    RCCHK(h->raster_timer.begin(h));
     h->raster_counted = false;
     HIPCHK(hipMemsetAsync(j.cnt, 0, 3 * sizeof(unsigned long long), h->stream));
-    HIPCHK(hipEventRecord(h->raster_ev[0], h->stream));
+    RCCHK(h->raster_timer.mark(h, 0));
     hipLaunchKernelGGL(raster_fill_kernel, dim3(nblk(npix)), dim3(kRasThreads), 0, h->stream, npix, j.owner);
     HIPCHK(hipGetLastError());
     if (j.nC > 0) {
@@ -236,15 +235,15 @@ int raster_run(sitrk_ctx *h, const RasterJob &j, const RasterGrid &g)
         else launch_cells<4, 0>(h, j, g);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->raster_ev[1], h->stream));
+    RCCHK(h->raster_timer.mark(h, 1));
     // at most kRasGatherBlocks workgroups, each lane `trips` pixels a grid apart: the atomics on the one counter serialise at the
     // memory side, and one per 256 pixels took longer than the pixels themselves (profiles/raster_bench.md)
-    const unsigned gblocks = nblk(npix) < kRasGatherBlocks ? nblk(npix) : kRasGatherBlocks;
-    const int trips = (int)((npix + (int64_t)gblocks * kRasThreads - 1) / ((int64_t)gblocks * kRasThreads));
-    hipLaunchKernelGGL(raster_gather_kernel, dim3(gblocks), dim3(kRasThreads), 0, h->stream, npix, trips, j.nC, j.owner, j.out, j.fields, j.cnt);
+    const Strided gs(npix, kRasThreads, kRasGatherBlocks);
+    hipLaunchKernelGGL(raster_gather_kernel, dim3(gs.blocks), dim3(kRasThreads), 0, h->stream, npix, gs.trips, j.nC, j.owner, j.out, j.fields,
+                       j.cnt);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->raster_ev[2], h->stream));
-    h->raster_timed = true;
+    RCCHK(h->raster_timer.mark(h, 2));
+    h->raster_timer.done();
     return SITRK_OK;
 }
 
@@ -257,13 +256,12 @@ int raster_check_grid(sitrk_ctx *h, const char *fn, double y0, double x0, double
     return SITRK_OK;
 }
 
-void raster_release(sitrk_ctx *h)
+int check_raster_shape(sitrk_ctx *h, const char *fn, int ny, int nx)
 {
-    for (hipEvent_t &e : h->raster_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->raster_timed = false;
+    if (ny < 1 || nx < 1 || ny > kRasMaxSide || nx > kRasMaxSide)
+        return fail(h, SITRK_EINVAL, "%s: ny and nx must be in 1..%d (got %d, %d)", fn, kRasMaxSide, ny, nx);
+    if ((int64_t)ny * nx > kRasMaxPixels) return fail(h, SITRK_EINVAL, "%s: ny*nx = %lld exceeds 2^28 pixels", fn, (long long)ny * nx);
+    return SITRK_OK;
 }
 
 }  // namespace sitrk
@@ -319,13 +317,8 @@ SITRK_API int sitrk_mesh_raster(sitrk_t *h, int mesh, int jrec1, int at_t1, doub
     const int64_t npix = (int64_t)ny * nx;
     int32_t *d_owner; double *d_fields; unsigned long long *d_cnt;
     auto layout = [&](Carver &c) { c.take(d_owner, npix); c.take(d_fields, fields ? (size_t)5 * npix : 0); c.take(d_cnt, 3); };
-    Carver size;
-    layout(size);
     MeshDeformDev m;
-    RCCHK(mesh_deform_core(h, mesh, jrec1, fields != nullptr, true, false, size.off, &m));
-    Carver place;
-    place.base = m.extra;
-    layout(place);
+    RCCHK(carve_behind_mesh(h, mesh, jrec1, fields != nullptr, true, false, layout, &m));
     RasterJob j;
     j.nC = m.nQ; j.nP = h->nP; j.nv = 4; j.flag = m.status; j.out = m.out; j.owner = d_owner; j.fields = fields ? d_fields : nullptr; j.cnt = d_cnt;
     if (at_t1) { j.cells = m.quads; j.pts = m.p1; j.only_status1 = true; }
@@ -343,10 +336,9 @@ SITRK_API int sitrk_mesh_raster(sitrk_t *h, int mesh, int jrec1, int at_t1, doub
 SITRK_API int sitrk_raster_kernel_ms(sitrk_t *h, float *cells_ms, float *gather_ms)
 {
     NEED(h, "null handle");
-    NEED(h->raster_timed, "sitrk_raster_kernel_ms: no raster call has run its kernels yet");
-    if (cells_ms) HIPCHK(hipEventElapsedTime(cells_ms, h->raster_ev[0], h->raster_ev[1]));
-    if (gather_ms) HIPCHK(hipEventElapsedTime(gather_ms, h->raster_ev[1], h->raster_ev[2]));
-    return SITRK_OK;
+    NEED(h->raster_timer.complete, "sitrk_raster_kernel_ms: no raster call has run its kernels yet");
+    RCCHK(h->raster_timer.elapsed(h, 0, cells_ms));
+    return h->raster_timer.elapsed(h, 1, gather_ms);
 }
 
 SITRK_API int sitrk_raster_stats(sitrk_t *h, int64_t *claims)

@@ -46,8 +46,6 @@ constexpr int kSkBatch = 8;                        // sub-iterations per launch 
 constexpr int kSkSide = kSkTile + 2 * kSkHalo;     // side of the patch in LDS
 constexpr int kSkPitch = (kSkSide + 2 + 3) / 4 * 4;    // ... with a ring of zeros around it, rows of whole words
 constexpr int kSkCols = SITRK_SKEL_NCOLS;
-constexpr int kSkMaxSide = 32768;
-constexpr int64_t kSkMaxPixels = (int64_t)1 << 28;
 constexpr int kSkMaxSub = 1 << 20;
 constexpr unsigned kSkBlocks = 2048;               // 256 CUs x 8 resident workgroups
 constexpr int64_t kSkSpanWaves = 4 * 2048;         // ... and their waves, each with a span of pixels of its own
@@ -57,20 +55,6 @@ static_assert(kSkSide * kSkSide % kSkThreads == 0 && kSkTile * kSkTile % kSkThre
 
 // counters of one call on the device
 enum { kSkFeat = 0, kSkNode = 1, kSkSkel = 2, kSkBad = 3, kSkN = 4 };
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + kSkThreads - 1) / kSkThreads); }
-
-// the launch of a kernel whose lanes step a grid at a time: at most kSkBlocks workgroups and the trips that cover n
-struct Strided {
-    unsigned blocks;
-    int trips;
-    explicit Strided(int64_t n)
-    {
-        blocks = nblk(n) < kSkBlocks ? nblk(n) : kSkBlocks;
-        if (blocks < 1) blocks = 1;
-        trips = (int)((n + (int64_t)blocks * kSkThreads - 1) / ((int64_t)blocks * kSkThreads));
-    }
-};
 
 // the count n of the waves of a workgroup (the same in all lanes of a wave) into a counter, one atomic
 __device__ __forceinline__ void block_add(long long n, unsigned long long *c)
@@ -362,9 +346,7 @@ struct SkelBuf {
 
 int skel_check(sitrk_ctx *h, const char *fn, int ny, int nx, const SkelArgs &a)
 {
-    if (ny < 1 || nx < 1 || ny > kSkMaxSide || nx > kSkMaxSide)
-        return fail(h, SITRK_EINVAL, "%s: ny and nx must be in 1..%d (got %d, %d)", fn, kSkMaxSide, ny, nx);
-    if ((int64_t)ny * nx > kSkMaxPixels) return fail(h, SITRK_EINVAL, "%s: ny*nx = %lld exceeds 2^28 pixels", fn, (long long)ny * nx);
+    RCCHK(check_raster_shape(h, fn, ny, nx));
     if (a.max_sub < 1 || a.max_sub > kSkMaxSub) return fail(h, SITRK_EINVAL, "%s: max_sub must be in 1..%d (got %d)", fn, kSkMaxSub, a.max_sub);
     if (a.maxfeat < 0) return fail(h, SITRK_EINVAL, "%s: maxfeat must be >= 0 (got %lld)", fn, (long long)a.maxfeat);
     if (a.maxnode < 0) return fail(h, SITRK_EINVAL, "%s: maxnode must be >= 0 (got %lld)", fn, (long long)a.maxnode);
@@ -386,19 +368,14 @@ int skel_core(sitrk_ctx *h, const char *fn, const SkelArgs &a, const int32_t *ho
     HIPCHK(hipSetDevice(h->device));
     const int64_t frows = a.maxfeat < npix ? a.maxfeat : npix, nrows = a.maxnode < npix ? a.maxnode : npix;
     SkelBuf b;
-    b.scan_bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, b.scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)npix, rocprim::plus<int32_t>(),
-                                   h->stream));
-    b.scan_bytes = align256(b.scan_bytes);
+    RCCHK(scan_i32_bytes(h, npix, &b.scan_bytes));
     RCCHK(carve_scratch(h, [&](Carver &c) {
         c.take(b.map, host_map ? (size_t)npix : 0); c.take(b.st[0], npix); c.take(b.st[1], npix); c.take(b.xc, npix);
         c.take(b.cnt, npix); c.take(b.flag, npix); c.take(b.row, npix);
         c.take(b.table, (size_t)frows * kSkCols); c.take(b.nodes, (size_t)nrows * 3); c.take(b.tot, kSkN); c.take(b.del, kSkHalo);
         c.take(b.scan_tmp, b.scan_bytes);
     }));
-    for (hipEvent_t &e : h->skel_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    h->skel_timed = false;
+    RCCHK(h->skel_timer.begin(h));
     const int32_t *map = dev_map;
     if (host_map) {
         HIPCHK(upload(h, b.map, host_map, (size_t)npix));
@@ -406,7 +383,7 @@ int skel_core(sitrk_ctx *h, const char *fn, const SkelArgs &a, const int32_t *ho
     }
     HIPCHK(hipMemsetAsync(b.tot, 0, kSkN * sizeof(unsigned long long), h->stream));
     HIPCHK(hipMemsetAsync(b.cnt, 0, (size_t)npix * sizeof(int32_t), h->stream));
-    const Strided sp(npix);
+    const Strided sp(npix, kSkThreads, kSkBlocks);
     hipLaunchKernelGGL(skel_init_kernel, dim3(sp.blocks), dim3(kSkThreads), 0, h->stream, npix, sp.trips, map, b.st[0], b.tot);
     HIPCHK(hipGetLastError());
     unsigned long long tot[kSkN] = {0, 0, 0, 0};
@@ -418,7 +395,7 @@ int skel_core(sitrk_ctx *h, const char *fn, const SkelArgs &a, const int32_t *ho
 
     // the thinning: batches of `batch` sub-iterations, the last one cut to what max_sub leaves; a batch's counters are the only
     // download in the loop, which stops behind two sub-iterations in a row that removed nothing
-    HIPCHK(hipEventRecord(h->skel_ev[0], h->stream));
+    RCCHK(h->skel_timer.mark(h, 0));
     const dim3 tiles((unsigned)((nx + kSkTile - 1) / kSkTile), (unsigned)((ny + kSkTile - 1) / kSkTile));
     const int batch = h->skeleton_batch > 0 ? h->skeleton_batch : kSkBatch;
     int cur = 0, done = 0, nsub = 0, quiet = 0;
@@ -438,40 +415,37 @@ int skel_core(sitrk_ctx *h, const char *fn, const SkelArgs &a, const int32_t *ho
         done += nb;
     }
     const int8_t *K = b.st[cur];
-    HIPCHK(hipEventRecord(h->skel_ev[1], h->stream));
+    RCCHK(h->skel_timer.mark(h, 1));
 
     // the table
     hipLaunchKernelGGL(skel_class_kernel, dim3(sp.blocks), dim3(kSkThreads), 0, h->stream, npix, sp.trips, ny, nx, K, b.xc, b.tot);
     HIPCHK(hipGetLastError());
-    const int64_t pieces = (npix + 63) / 64;
-    const int64_t want = (pieces + kSkSpanWaves - 1) / kSkSpanWaves;
-    const int wtrips = (int)(want > kSkMinTrips ? want : kSkMinTrips);
-    const unsigned wblocks = (unsigned)(((pieces + wtrips - 1) / wtrips + kSkThreads / 64 - 1) / (kSkThreads / 64));
-    hipLaunchKernelGGL(skel_count_kernel, dim3(wblocks), dim3(kSkThreads), 0, h->stream, (int32_t)npix, wtrips, map, b.cnt);
+    const WaveSpans ws(npix, kSkThreads, kSkSpanWaves, kSkMinTrips);
+    hipLaunchKernelGGL(skel_count_kernel, dim3(ws.blocks), dim3(kSkThreads), 0, h->stream, (int32_t)npix, ws.trips, map, b.cnt);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(skel_flag_kernel, dim3(nblk(npix)), dim3(kSkThreads), 0, h->stream, npix, b.cnt, b.flag);
+    hipLaunchKernelGGL(skel_flag_kernel, dim3(nblk(npix, kSkThreads)), dim3(kSkThreads), 0, h->stream, npix, b.cnt, b.flag);
     HIPCHK(hipGetLastError());
     size_t tb = b.scan_bytes;
     HIPCHK(rocprim::exclusive_scan(b.scan_tmp, tb, b.flag, b.row, 0, (size_t)npix, rocprim::plus<int32_t>(), h->stream));
-    hipLaunchKernelGGL(skel_rows_kernel, dim3(nblk(npix)), dim3(kSkThreads), 0, h->stream, npix, frows, b.cnt, b.row, b.table, b.tot);
+    hipLaunchKernelGGL(skel_rows_kernel, dim3(nblk(npix, kSkThreads)), dim3(kSkThreads), 0, h->stream, npix, frows, b.cnt, b.row, b.table, b.tot);
     HIPCHK(hipGetLastError());
     if (frows > 0) {
-        hipLaunchKernelGGL(skel_table_kernel, dim3(wblocks), dim3(kSkThreads), 0, h->stream, (int32_t)npix, wtrips, ny, nx, frows, map, b.xc, b.row,
-                           b.table);
+        hipLaunchKernelGGL(skel_table_kernel, dim3(ws.blocks), dim3(kSkThreads), 0, h->stream, (int32_t)npix, ws.trips, ny, nx, frows, map, b.xc,
+                           b.row, b.table);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->skel_ev[2], h->stream));
+    RCCHK(h->skel_timer.mark(h, 2));
 
     // the nodes: their flags lie over the counters and their rows over the values' flags, both dead by now
     int32_t *nflag = b.cnt, *nrow = b.flag;
-    hipLaunchKernelGGL(skel_nodeflag_kernel, dim3(nblk(npix)), dim3(kSkThreads), 0, h->stream, npix, b.xc, nflag);
+    hipLaunchKernelGGL(skel_nodeflag_kernel, dim3(nblk(npix, kSkThreads)), dim3(kSkThreads), 0, h->stream, npix, b.xc, nflag);
     HIPCHK(hipGetLastError());
     tb = b.scan_bytes;
     HIPCHK(rocprim::exclusive_scan(b.scan_tmp, tb, nflag, nrow, 0, (size_t)npix, rocprim::plus<int32_t>(), h->stream));
-    hipLaunchKernelGGL(skel_nodes_kernel, dim3(nblk(npix)), dim3(kSkThreads), 0, h->stream, npix, nrows, map, b.xc, nflag, nrow, b.nodes, b.tot);
+    hipLaunchKernelGGL(skel_nodes_kernel, dim3(nblk(npix, kSkThreads)), dim3(kSkThreads), 0, h->stream, npix, nrows, map, b.xc, nflag, nrow, b.nodes, b.tot);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->skel_ev[3], h->stream));
-    h->skel_timed = true;
+    RCCHK(h->skel_timer.mark(h, 3));
+    h->skel_timer.done();
 
     HIPCHK(download(h, tot, b.tot, kSkN));
     if (a.skel) HIPCHK(download(h, a.skel, K, (size_t)npix));
@@ -490,15 +464,6 @@ int skel_core(sitrk_ctx *h, const char *fn, const SkelArgs &a, const int32_t *ho
 }
 
 }  // namespace
-
-void skeleton_release(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->skel_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->skel_timed = false;
-}
 
 int skeleton_set_batch(sitrk_ctx *h, int value)
 {
@@ -539,9 +504,8 @@ SITRK_API int sitrk_keep_skeleton(sitrk_t *h, int keep, int max_sub, int64_t max
 SITRK_API int sitrk_skeleton_kernel_ms(sitrk_t *h, float *thin_ms, float *table_ms, float *nodes_ms)
 {
     NEED(h, "null handle");
-    NEED(h->skel_timed, "sitrk_skeleton_kernel_ms: no skeleton call has run its kernels yet");
+    NEED(h->skel_timer.complete, "sitrk_skeleton_kernel_ms: no skeleton call has run its kernels yet");
     float *out[3] = {thin_ms, table_ms, nodes_ms};
-    for (int k = 0; k < 3; k++)
-        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], h->skel_ev[k], h->skel_ev[k + 1]));
+    for (int k = 0; k < 3; k++) RCCHK(h->skel_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }

@@ -38,28 +38,12 @@ namespace {
 
 constexpr int kTrThreads = 256;
 constexpr unsigned kTrBlocks = 2048;               // 256 CUs x 8 resident workgroups
-constexpr int kTrMaxSide = 32768;
-constexpr int64_t kTrMaxPixels = (int64_t)1 << 28;
 constexpr int32_t kTrNone = INT32_MAX;
 constexpr int64_t kTrMaxKeys = ((int64_t)1 << 31) - 1;
 constexpr int kTrMaxShift = 32768;
 
 // counters of one call on the device
 enum { kTrE = 0, kTrHit = 1, kTrPair = 2, kTrBad = 3, kTrN = 4 };
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + kTrThreads - 1) / kTrThreads); }
-
-// the launch of a kernel whose lanes step a grid at a time: at most kTrBlocks workgroups and the trips that cover n
-struct Strided {
-    unsigned blocks;
-    int trips;
-    explicit Strided(int64_t n)
-    {
-        blocks = nblk(n) < kTrBlocks ? nblk(n) : kTrBlocks;
-        if (blocks < 1) blocks = 1;
-        trips = (int)((n + (int64_t)blocks * kTrThreads - 1) / ((int64_t)blocks * kTrThreads));
-    }
-};
 
 // the counts a, b of the waves of a workgroup (the same in all lanes of a wave) into two counters, one atomic each
 __device__ __forceinline__ void block_add2(long long a, long long b, unsigned long long *ca, unsigned long long *cb)
@@ -251,9 +235,7 @@ int keep_check_slot(sitrk_ctx *h, const char *fn, const char *name, int keep, bo
 
 int keep_check_shape(sitrk_ctx *h, const char *fn, int ny, int nx, int conn, int64_t min_pix)
 {
-    if (ny < 1 || nx < 1 || ny > kTrMaxSide || nx > kTrMaxSide)
-        return fail(h, SITRK_EINVAL, "%s: ny and nx must be in 1..%d (got %d, %d)", fn, kTrMaxSide, ny, nx);
-    if ((int64_t)ny * nx > kTrMaxPixels) return fail(h, SITRK_EINVAL, "%s: ny*nx = %lld exceeds 2^28 pixels", fn, (long long)ny * nx);
+    RCCHK(check_raster_shape(h, fn, ny, nx));
     if (conn != 4 && conn != 8) return fail(h, SITRK_EINVAL, "%s: conn must be 4 (edge neighbours) or 8 (edge and corner neighbours), got %d", fn, conn);
     if (min_pix < 1) return fail(h, SITRK_EINVAL, "%s: min_pix must be >= 1 (got %lld)", fn, (long long)min_pix);
     return SITRK_OK;
@@ -291,18 +273,11 @@ void keep_commit(sitrk_ctx *h, int keep, int32_t *map, size_t cap, int ny, int n
     keep_give(h, old, old_cap);
 }
 
-int track_events(sitrk_ctx *h)
-{
-    for (hipEvent_t &e : h->track_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    return SITRK_OK;
-}
-
 template <bool EMIT>
 int launch_scan(sitrk_ctx *h, int reach, int ny, int nx, int dj, int di, int nb, const int32_t *A, const int32_t *B, int32_t *cnt,
                 const int32_t *off, unsigned long long *keys, unsigned long long *tot)
 {
-    const Strided s((int64_t)ny * nx);
+    const Strided s((int64_t)ny * nx, kTrThreads, kTrBlocks);
     if (reach == 0)
         hipLaunchKernelGGL((match_scan_kernel<0, EMIT>), dim3(s.blocks), dim3(kTrThreads), 0, h->stream, ny, nx, dj, di, s.trips, nb, A, B, cnt, off, keys, tot);
     else if (reach == 1)
@@ -317,7 +292,7 @@ int launch_scan(sitrk_ctx *h, int reach, int ny, int nx, int dj, int di, int nb,
 
 int keep_from_labels(sitrk_ctx *h, int64_t npix, const int32_t *labels, const int32_t *flag, int32_t *keep_map)
 {
-    hipLaunchKernelGGL(keep_labels_kernel, dim3(nblk(npix)), dim3(kTrThreads), 0, h->stream, npix, labels, flag, keep_map);
+    hipLaunchKernelGGL(keep_labels_kernel, dim3(nblk(npix, kTrThreads)), dim3(kTrThreads), 0, h->stream, npix, labels, flag, keep_map);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return SITRK_OK;
@@ -331,11 +306,8 @@ void track_release(sitrk_ctx *h)
     }
     if (h->keep_spare) (void)hipFree(h->keep_spare);
     h->keep_spare = nullptr; h->keep_spare_cap = 0;
-    for (hipEvent_t &e : h->track_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    h->match_timed = h->advect_timed = false;
+    h->match_timer.release();
+    h->advect_timer.release();
 }
 
 }  // namespace sitrk
@@ -349,8 +321,9 @@ SITRK_API int sitrk_mesh_features_keep(sitrk_t *h, int keep, int mesh, int jrec1
     const char *fn = "sitrk_mesh_features_keep";
     NEED(h, "null handle");
     RCCHK(keep_check_slot(h, fn, "keep", keep, false));
-    // the body refuses a bad raster before any device work; the allocation is sized from a checked shape only
-    if (ny < 1 || nx < 1 || ny > kTrMaxSide || nx > kTrMaxSide || (int64_t)ny * nx > kTrMaxPixels)
+    // the body refuses a bad raster before any device work, with the message of its first failing check; the allocation is sized
+    // from a checked shape only
+    if (check_raster_shape(h, fn, ny, nx))
         return mesh_features_body(h, fn, mesh, jrec1, at_t1, y0_km, x0_km, d_km, ny, nx, what, sgn, thr, conn, min_pix, maxfeat, labels, table,
                                   nfeat, ncomp, nactive, nullptr);
     HIPCHK(hipSetDevice(h->device));
@@ -377,7 +350,7 @@ SITRK_API int sitrk_keep_put(sitrk_t *h, int keep, int ny, int nx, const int32_t
     int32_t *d_map; size_t cap;
     RCCHK(keep_take(h, (size_t)npix, &d_map, &cap));
     unsigned long long tot[kTrN] = {0, 0, 0, 0};
-    const Strided s(npix);
+    const Strided s(npix, kTrThreads, kTrBlocks);
     hipError_t e = hipMemsetAsync(d_tot, 0, kTrN * sizeof(unsigned long long), h->stream);
     if (e == hipSuccess) e = upload(h, d_map, map, (size_t)npix);
     if (e == hipSuccess) {
@@ -452,19 +425,14 @@ SITRK_API int sitrk_mesh_features_advect(sitrk_t *h, int keep_from, int keep_to,
     auto layout = [&](Carver &c) {
         c.take(d_o0, npix); c.take(d_o1, npix); c.take(d_cellfeat, nQ > 0 ? nQ : 1); c.take(d_cnt0, 3); c.take(d_cnt1, 3); c.take(d_tot, 2);
     };
-    Carver size;
-    layout(size);
     int32_t *d_map; size_t cap;
     RCCHK(keep_take(h, (size_t)npix, &d_map, &cap));
     unsigned long long cnt0[3] = {0, 0, 0}, cnt1[3] = {0, 0, 0}, tot[2] = {0, 0};
     // everything that can fail behind the allocation: the slot stays what it was
     auto run = [&]() -> int {
         MeshDeformDev m;
-        RCCHK(mesh_deform_core(h, mesh, jrec1, false, true, false, size.off, &m));
+        RCCHK(carve_behind_mesh(h, mesh, jrec1, false, true, false, layout, &m));
         if (m.nQ != nQ) return fail(h, SITRK_EHIP, "%s: the mesh changed under the call", fn);
-        Carver place;
-        place.base = m.extra;
-        layout(place);
         const RasterGrid g = {y0_km, x0_km, d_km, ny, nx};
         RasterJob r0;                                                  // the two draws of sitrk_mesh_raster
         r0.nC = m.nQ; r0.nP = h->nP; r0.nv = 4; r0.flag = m.status; r0.owner = d_o0; r0.cnt = d_cnt0;
@@ -474,24 +442,23 @@ SITRK_API int sitrk_mesh_features_advect(sitrk_t *h, int keep_from, int keep_to,
         r1.nC = m.nQ; r1.nP = h->nP; r1.nv = 4; r1.flag = m.status; r1.owner = d_o1; r1.cnt = d_cnt1;
         r1.cells = m.quads; r1.pts = m.p1; r1.only_status1 = true;
         RCCHK(raster_run(h, r1, g));
-        RCCHK(track_events(h));
-        h->advect_timed = false;
+        RCCHK(h->advect_timer.begin(h));
         HIPCHK(hipMemsetAsync(d_tot, 0, 2 * sizeof(unsigned long long), h->stream));
-        HIPCHK(hipEventRecord(h->track_ev[4], h->stream));
+        RCCHK(h->advect_timer.mark(h, 0));
         if (nQ > 0) {
-            hipLaunchKernelGGL(advect_fill_kernel, dim3(nblk(nQ)), dim3(kTrThreads), 0, h->stream, nQ, d_cellfeat);
+            hipLaunchKernelGGL(advect_fill_kernel, dim3(nblk(nQ, kTrThreads)), dim3(kTrThreads), 0, h->stream, nQ, d_cellfeat);
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(advect_min_kernel, dim3(nblk(npix)), dim3(kTrThreads), 0, h->stream, npix, nQ, d_o0, from.map, d_cellfeat);
+            hipLaunchKernelGGL(advect_min_kernel, dim3(nblk(npix, kTrThreads)), dim3(kTrThreads), 0, h->stream, npix, nQ, d_o0, from.map, d_cellfeat);
             HIPCHK(hipGetLastError());
-            const Strided sc(nQ);
+            const Strided sc(nQ, kTrThreads, kTrBlocks);
             hipLaunchKernelGGL(advect_cells_kernel, dim3(sc.blocks), dim3(kTrThreads), 0, h->stream, nQ, sc.trips, d_cellfeat, d_tot);
             HIPCHK(hipGetLastError());
         }
-        const Strided sp(npix);
+        const Strided sp(npix, kTrThreads, kTrBlocks);
         hipLaunchKernelGGL(advect_gather_kernel, dim3(sp.blocks), dim3(kTrThreads), 0, h->stream, npix, sp.trips, nQ, d_o1, d_cellfeat, d_map, d_tot);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->track_ev[5], h->stream));
-        h->advect_timed = true;
+        RCCHK(h->advect_timer.mark(h, 1));
+        h->advect_timer.done();
         HIPCHK(download(h, cnt0, d_cnt0, 3));
         HIPCHK(download(h, cnt1, d_cnt1, 3));
         HIPCHK(download(h, tot, d_tot, 2));
@@ -537,8 +504,7 @@ SITRK_API int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int
     // E, the number of keys, first: nothing is sized from it before it is known to fit
     unsigned long long *d_tot;
     RCCHK(carve_scratch(h, [&](Carver &c) { c.take(d_tot, kTrN); }));
-    RCCHK(track_events(h));
-    h->match_timed = false;
+    RCCHK(h->match_timer.begin(h));
     HIPCHK(hipMemsetAsync(d_tot, 0, kTrN * sizeof(unsigned long long), h->stream));
     RCCHK(launch_scan<false>(h, reach, ny, nx, dj, di, nb, A.map, B.map, nullptr, nullptr, nullptr, d_tot));
     unsigned long long tot[kTrN] = {0, 0, 0, 0};
@@ -552,9 +518,9 @@ SITRK_API int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int
 
     int32_t *d_cnt, *d_off; unsigned long long *d_keys, *d_sorted; long long *d_pairs; char *d_scan, *d_sort;
     size_t scan_bytes = 0, scan2 = 0, sort_bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)npix, rocprim::plus<int32_t>(), h->stream));
+    RCCHK(scan_i32_bytes(h, npix, &scan_bytes));
     if (E > 0) {
-        HIPCHK(rocprim::exclusive_scan(nullptr, scan2, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)E, rocprim::plus<int32_t>(), h->stream));
+        RCCHK(scan_i32_bytes(h, E, &scan2));
         HIPCHK(sort_keys_u64(nullptr, &sort_bytes, nullptr, nullptr, (size_t)E, (unsigned)(2 * nb), h->stream));
     }
     if (scan2 > scan_bytes) scan_bytes = scan2;
@@ -564,31 +530,32 @@ SITRK_API int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int
     }));
     // (the scratch may have moved: the counters are set again)
     HIPCHK(hipMemsetAsync(d_tot, 0, kTrN * sizeof(unsigned long long), h->stream));
-    HIPCHK(hipEventRecord(h->track_ev[0], h->stream));
+    RCCHK(h->match_timer.mark(h, 0));
     if (E > 0) {
         RCCHK(launch_scan<false>(h, reach, ny, nx, dj, di, nb, A.map, B.map, d_cnt, nullptr, nullptr, d_tot));
         size_t tb = scan_bytes;
         HIPCHK(rocprim::exclusive_scan(d_scan, tb, d_cnt, d_off, 0, (size_t)npix, rocprim::plus<int32_t>(), h->stream));
         RCCHK(launch_scan<true>(h, reach, ny, nx, dj, di, nb, A.map, B.map, nullptr, d_off, d_keys, d_tot));
     }
-    HIPCHK(hipEventRecord(h->track_ev[1], h->stream));
+    RCCHK(h->match_timer.mark(h, 1));
     if (E > 0) {
         size_t sb = sort_bytes;
         HIPCHK(sort_keys_u64(d_sort, &sb, (const uint64_t *)d_keys, (uint64_t *)d_sorted, (size_t)E, (unsigned)(2 * nb), h->stream));
     }
-    HIPCHK(hipEventRecord(h->track_ev[2], h->stream));
+    RCCHK(h->match_timer.mark(h, 2));
     if (E > 0) {
         int32_t *d_flag = (int32_t *)d_keys, *d_row = d_flag + E;      // over the unsorted keys, which are dead
-        hipLaunchKernelGGL(match_bounds_kernel, dim3(nblk(E)), dim3(kTrThreads), 0, h->stream, E, d_sorted, d_flag);
+        hipLaunchKernelGGL(match_bounds_kernel, dim3(nblk(E, kTrThreads)), dim3(kTrThreads), 0, h->stream, E, d_sorted, d_flag);
         HIPCHK(hipGetLastError());
         size_t tb = scan_bytes;
         HIPCHK(rocprim::exclusive_scan(d_scan, tb, d_flag, d_row, 0, (size_t)E, rocprim::plus<int32_t>(), h->stream));
         if (rows_cap > 0) HIPCHK(hipMemsetAsync(d_pairs, 0, (size_t)rows_cap * 3 * sizeof(long long), h->stream));
-        hipLaunchKernelGGL(match_rows_kernel, dim3(nblk(E)), dim3(kTrThreads), 0, h->stream, E, rows_cap, nb, d_sorted, d_flag, d_row, d_pairs, d_tot);
+        hipLaunchKernelGGL(match_rows_kernel, dim3(nblk(E, kTrThreads)), dim3(kTrThreads), 0, h->stream, E, rows_cap, nb, d_sorted, d_flag, d_row, d_pairs,
+                           d_tot);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->track_ev[3], h->stream));
-    h->match_timed = true;
+    RCCHK(h->match_timer.mark(h, 3));
+    h->match_timer.done();
     unsigned long long end[kTrN] = {0, 0, 0, 0};
     HIPCHK(download(h, end, d_tot, kTrN));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -606,17 +573,15 @@ SITRK_API int sitrk_features_match(sitrk_t *h, int keepA, int keepB, int dj, int
 SITRK_API int sitrk_match_kernel_ms(sitrk_t *h, float *emit_ms, float *sort_ms, float *rows_ms)
 {
     NEED(h, "null handle");
-    NEED(h->match_timed, "sitrk_match_kernel_ms: no sitrk_features_match has run its kernels yet");
+    NEED(h->match_timer.complete, "sitrk_match_kernel_ms: no sitrk_features_match has run its kernels yet");
     float *out[3] = {emit_ms, sort_ms, rows_ms};
-    for (int k = 0; k < 3; k++)
-        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], h->track_ev[k], h->track_ev[k + 1]));
+    for (int k = 0; k < 3; k++) RCCHK(h->match_timer.elapsed(h, k, out[k]));
     return SITRK_OK;
 }
 
 SITRK_API int sitrk_advect_kernel_ms(sitrk_t *h, float *advect_ms)
 {
     NEED(h, "null handle");
-    NEED(h->advect_timed, "sitrk_advect_kernel_ms: no sitrk_mesh_features_advect has run its kernels yet");
-    if (advect_ms) HIPCHK(hipEventElapsedTime(advect_ms, h->track_ev[4], h->track_ev[5]));
-    return SITRK_OK;
+    NEED(h->advect_timer.complete, "sitrk_advect_kernel_ms: no sitrk_mesh_features_advect has run its kernels yet");
+    return h->advect_timer.elapsed(h, 0, advect_ms);
 }

@@ -5,6 +5,7 @@ known, and the parser of --deform-features."""
 import math
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -423,6 +424,46 @@ def test_the_large_shapes_reach_the_paths_they_are_for():
         assert s["SPAN5"] == {"npix": 2131599, "flag": (5, 34447), "strided": (5, 34447), "wtrips": 5, "waves": 6662, "last_wave_pieces": 2,
                               "last_piece_pixels": 15, "merge_j": (5, 6), "merge_i": (5, 6), "nb": 22}
         assert (s["DEEP"]["npix"], s["DEEP"]["wtrips"], s["DEEP"]["merge_j"][0], s["DEEP"]["merge_i"][0], s["DEEP"]["nb"]) == (17219899, 33, 7, 7, 25)
+
+
+def test_launch_shape_is_what_the_library_computes(tmp_path):
+    """launch_shape() is a restatement; the launches are sized by Strided and WaveSpans of sitrk_launch.h.  That header is plain
+    C++: a small program built from it prints what it derives, for the three large shapes and at the edges of both formulas, and
+    the restatement has to give the same."""
+    c = kernel_constants()
+    exe = str(tmp_path / "launch_shape_check")
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "sitrack_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "c", "launch_shape_check.cpp")], check=True)
+    up = lambda a, b: -(-a // b)
+    capped = (("flag", c["kLbThreads"], c["kLbFlagBlocks"]), ("strided", c["kTrThreads"], c["kTrBlocks"]))
+    counts = [ny * nx for ny, nx in (TRIP2, SPAN5, DEEP)] + [0, 1, 256, 256 * 2048, 256 * 2048 + 1]
+    spans = [ny * nx for ny, nx in (TRIP2, SPAN5, DEEP)] + [1, 64, 65, 64 * 4 * 8192, 64 * 4 * 8192 + 1]
+    args = []
+    for n in counts:
+        for _, threads, cap in capped:
+            args += ["s", n, threads, cap]
+    for n in spans:
+        args += ["w", n, c["kLbThreads"], c["kLbSpanWaves"], c["kLbMinTrips"]]
+    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = [tuple(int(x) for x in ln.split()) for ln in r.stdout.splitlines()]
+    assert len(got) == 2 * len(counts) + len(spans)
+    it = iter(got)
+    for n in counts:
+        v = launch_shape(1, n, c)
+        for key, threads, cap in capped:
+            blocks, trips = next(it)
+            want_trips, last = v[key]
+            assert trips == want_trips and blocks == max(1, min(up(n, threads), cap)), (key, n, blocks, trips, v[key])
+            assert n - (trips - 1) * blocks * threads == last, (key, n, blocks, trips, v[key])
+    for n in spans:
+        v = launch_shape(1, n, c)
+        blocks, trips = next(it)
+        assert trips == v["wtrips"] and blocks == up(v["waves"], c["kLbThreads"] // 64), (n, blocks, trips, v)
+    # the second trip and the longer span start exactly where the formulas say
+    if (c["kLbFlagBlocks"], c["kLbSpanWaves"], c["kLbMinTrips"], c["kLbThreads"], c["kTrBlocks"], c["kTrThreads"]) == (2048, 8192, 4, 256, 2048, 256):
+        assert got[2 * 3:2 * 8:2] == [(1, 0), (1, 1), (1, 1), (2048, 1), (2048, 2)]
+        assert got[2 * len(counts) + 3:] == [(1, 4), (1, 4), (1, 4), (2048, 4), (1639, 5)]
 
 
 # ------------------------------------------------------------------------------------------------ feature_table
