@@ -17,7 +17,8 @@ from sitrack_amd import _lib
 from sitrack_amd import coarse as co
 from sitrack_amd import driver as drv
 from test_mesh import ccw_quads, exact_lattice
-from test_raster import JITTER_GRIDS, JITTER_INNER, jitter_case, lattice_case
+from test_raster import JITTER_GRIDS, JITTER_INNER, jitter_case, lattice_case, split_quads
+from test_tri2quad import chain_constants, up
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("sitrk_coarse_cells", "sitrk_mesh_coarse", "sitrk_coarse_kernel_ms")
@@ -171,6 +172,69 @@ def jitter_perm():
     return np.random.default_rng(11).permutation(1225)
 
 
+# The case that takes the rows-of-partials reductions of sitrk_coarse.hip into a second trip (tests/test_gpu_coarse.py): a
+# jittered lattice of 301 x 291 points 8 km apart, 87 000 quadrangles in a fixed random order, on 300 x 290 pixels of 7.6 km whose
+# origin lies inside the mesh, so that cells fall outside on all four sides.
+BIG_LATTICE = (301, 291)
+BIG_GRID = (-1469.7, 2025.7, 7.6, 300, 290)
+BIG_NLEV = 4
+
+
+def big_case():
+    """(yx, yx1, quads): the lattice moved by smooth_move, its quadrangles in a fixed random order"""
+    if "big" not in _CASES:
+        ny, nx = BIG_LATTICE
+        yx = exact_lattice(ny, nx, 8.0) + np.random.default_rng(1).uniform(-2., 2., (ny * nx, 2))
+        quads = ccw_quads(ny, nx)
+        _CASES["big"] = (yx, smooth_move(yx), np.ascontiguousarray(quads[np.random.default_rng(11).permutation(len(quads))]))
+    return _CASES["big"]
+
+
+def big_use():
+    """a `use` mask over the quadrangles of big_case() that switches off one contributing cell inside the grid in every trip
+    of coarse_count_kernel's loop over the rows of counts, and one outside the grid in the last trip: (use (nC,) int8, the
+    cells switched off, their trips)"""
+    T = chain_constants()["kCoThreads"]
+    yx, yx1, quads = big_case()
+    _, ok = cell_terms(yx, yx1, quads, DAY)
+    inside = centroid_pixels(yx, quads, BIG_GRID)[0]
+    trip = np.arange(len(quads)) // (T * T)                               # row = cell // T, trip = row // T
+    off = [int(np.flatnonzero(ok & inside & (trip == k))[7]) for k in range(trip.max() + 1)]
+    off.append(int(np.flatnonzero(ok & ~inside & (trip == trip.max()))[3]))
+    use = np.ones(len(quads), dtype=np.int8)
+    use[off] = 0
+    return use, off, trip[off].tolist()
+
+
+def big_coarse(key):
+    """coarse_ref of big_case(), computed once and left unchanged: key = "quads" | "tris" (split_quads: twice the cells) | "use"
+    (the quadrangles under big_use())"""
+    if "big " + key not in _CASES:
+        yx, yx1, quads = big_case()
+        cells = split_quads(quads) if key == "tris" else quads
+        _CASES["big " + key] = coarse_ref(yx, yx1, cells, DAY, BIG_GRID, BIG_NLEV, use=big_use()[0] if key == "use" else None)
+    return _CASES["big " + key]
+
+
+def sort_end_bit(npix):
+    """the number of key bits coarse_run sorts on: the keys run 0 .. npix"""
+    end_bit = 1
+    while end_bit < 32 and (1 << end_bit) <= npix:
+        end_bit += 1
+    return end_bit
+
+
+def late_share(lev, side, fmin, first_pixel):
+    """Of one level of a pyramid: [(|exactly rounded sum of the column's terms over the filled boxes of index >= first_pixel|,
+    the bound (n + 16) 2^-53 fsum|t| of tests/test_gpu_coarse.py over all filled boxes)] for the six moments, and the number of
+    such boxes with a cell and filled."""
+    some, filled, t = box_terms(lev, side, fmin)
+    late = np.flatnonzero(filled.ravel()) >= first_pixel                  # box_terms keeps the filled boxes in ascending index
+    n = int(filled.sum())
+    return ([(abs(math.fsum(row[late])), (n + 16) * 2. ** -53 * math.fsum(np.abs(row))) for row in t],
+            int(some.ravel()[first_pixel:].sum()), int(late.sum()))
+
+
 # ------------------------------------------------------------------------------------------------ the restatement's self-checks
 def test_centroids_on_pixel_corners_go_to_the_upper_pixel():
     yx, quads, _, _ = lattice_case()
@@ -269,6 +333,64 @@ def test_masks_use_and_degenerate_cells_do_not_contribute():
     assert coarse_ref(yx, yx1, flat, STRAIN_T, TIE_GRID, 1)["nin"] == 142
     empty = coarse_ref(yx, yx1, quads[:0], STRAIN_T, TIE_GRID, 3)
     assert (empty["nin"], empty["nout"]) == (0, 0) and (empty["table"] == 0.).all() and all((lev == 0.).all() for lev in empty["levels"])
+
+
+def big_sizes():
+    """what the kernels of sitrk_coarse.hip see of big_case(), from the constants of the source: rows of partials per level, rows
+    of counts for the quadrangles and the triangles, and the trips of the loops over them"""
+    T = chain_constants()["kCoThreads"]
+    shp = _lib.Context.coarse_level_shapes(BIG_GRID[3], BIG_GRID[4], BIG_NLEV)
+    rows = [up(a * b, T) for a, b in shp]
+    nQ = (BIG_LATTICE[0] - 1) * (BIG_LATTICE[1] - 1)
+    return {"T": T, "shapes": shp, "rows": rows, "trips": [up(r, T) for r in rows], "count_rows": (up(nQ, T), up(2 * nQ, T)),
+            "count_trips": (up(up(nQ, T), T), up(up(2 * nQ, T), T)), "end_bit": sort_end_bit(BIG_GRID[3] * BIG_GRID[4])}
+
+
+def check_big_sizes(s):
+    """the size conditions of the case, asserted before a device is asked anything"""
+    T = s["T"]
+    assert s["rows"][0] > T + 64 and s["trips"][0] == 2                   # level 0: a second trip, of more than one wave of lanes
+    assert s["rows"][1] > 64 and s["trips"][1] == 1                       # level 1: block_sum gets sums from more than one wave
+    assert min(s["count_rows"]) > T + 64 and s["count_trips"] == (2, 3)
+    assert s["end_bit"] >= 17 and BIG_NLEV >= 3 and BIG_GRID[3] * BIG_GRID[4] > T * T
+
+
+def test_big_case_takes_every_reduction_loop_of_the_chain_into_a_second_trip():
+    """The size conditions of tests/test_gpu_coarse.py's case of more than 256 rows, from coarse_ref and the constants read from
+    sitrk_coarse.hip, without a device.  coarse_ref's loop over the cells is linear: 0.36 s for the 87 000 quadrangles, 0.84 s for
+    the 174 000 triangles, measured on the CPU of the development machine; the three pyramids of the case are computed once."""
+    s = big_sizes()
+    T = s["T"]
+    print(s)
+    check_big_sizes(s)
+    assert s["shapes"] == [(300, 290), (150, 145), (75, 73), (38, 37)] and s["rows"] == [340, 85, 22, 6] and s["end_bit"] == 17
+    yx, yx1, quads = big_case()
+    assert len(quads) == 87000 and s["count_rows"] == (340, 680)
+    r = big_coarse("quads")
+    assert r["nin"] + r["nout"] == 87000 and r["nout"] > 1000 and r["nin"] > 70000
+    n0 = r["levels"][0][0]
+    print("nin %d, nout %d, cells per pixel up to %d, %d empty pixels" % (r["nin"], r["nout"], n0.max(), (n0 == 0).sum()))
+    assert n0.max() >= 3 and (n0 == 0).sum() > 1000
+    # a pixel's run is not contiguous before the sort: the keys of the cells, in the order given, fall as often as they rise
+    inside, j, i, _, _ = centroid_pixels(yx, quads, BIG_GRID)
+    key = np.where(inside, j * BIG_GRID[4] + i, BIG_GRID[3] * BIG_GRID[4])
+    assert (np.diff(key) < 0).sum() > 40000 and key[inside].max() >= 1 << 16      # keys that need the 17th bit
+    # rows of the second trip (level 0: pixels from T*T on) and lanes of the second wave (level 1: boxes from 64 T on) carry
+    # boxes with cells, filled boxes, and a share of every moment far above the bound the device's sum is held to
+    for l, first in ((0, T * T), (1, 64 * T)):
+        share, nsome, nfilled = late_share(r["levels"][l], BIG_GRID[2] * 2. ** l, 0.5, first)
+        print("level %d, boxes from %d on: %d with a cell, %d filled; share / bound of the six moments: %s" %
+              (l, first, nsome, nfilled, ", ".join("%.3g" % (a / b) for a, b in share)))
+        assert nsome > 1000 and nfilled > 1000 and all(a > 1e3 * b for a, b in share)
+    assert r["table"][0, 0] == (n0 >= 1.).sum() and r["table"][0, 1] < r["table"][0, 0]
+    # the triangles: twice the cells, each with a centroid of its own
+    t = big_coarse("tris")
+    assert t["nin"] + t["nout"] == 174000 and t["nout"] > 2000 and t["levels"][0][0].sum() == t["nin"]
+    # the use mask: one contributing cell less in every trip of the loop over the rows of counts
+    use, off, trips = big_use()
+    assert trips == [0, 1, 1] and (use == 0).sum() == 3
+    u = big_coarse("use")
+    assert (u["nin"], u["nout"]) == (r["nin"] - 2, r["nout"] - 1) and u["levels"][0][0].sum() == r["nin"] - 2
 
 
 # ------------------------------------------------------------------------------------------------ the binding

@@ -20,8 +20,8 @@ import pytest
 import sitrack_amd as sit
 from sitrack_amd import _lib, ncio
 from sitrack_amd import driver as drv
-from test_coarse import (DAY, ONE_PIXEL, STRAIN_T, TIE_GRID, bits, box_terms, coarse_ref, jitter_coarse, jitter_perm, smooth_move,
-                         strain_move)
+from test_coarse import (BIG_GRID, BIG_NLEV, DAY, ONE_PIXEL, STRAIN_T, TIE_GRID, big_case, big_coarse, big_sizes, big_use, bits, box_terms,
+                         check_big_sizes, coarse_ref, jitter_coarse, jitter_perm, late_share, smooth_move, strain_move)
 from test_driver import make_case
 from test_gpu_mesh import JREC0, K, RDT, advance, start
 from test_raster import JITTER_GRIDS, JITTER_INNER, jitter_case, lattice_case, split_quads
@@ -113,6 +113,44 @@ def test_jittered_mesh_in_order_permuted_twice_and_as_triangles(ctx):
     want_t = coarse_ref(yx, yx1, tris, DAY, grid, 6)
     assert want_t["nin"] == 2450
     same_bits(ctx.coarse_cells(yx, yx1, tris, DAY, grid, 6, boxes=True), want_t, "triangles", d=18.4)
+
+
+# ------------------------------------------------------------------------------------------------ 2b. more than 256 rows of partials
+def test_more_than_256_rows_of_partials_and_of_counts(ctx):
+    """The loops of coarse_table_kernel and coarse_count_kernel -- lane i takes the rows i, i + kCoThreads, ... -- past their
+    first trip, and sort_pairs_u32 on 17 key bits: big_case() of tests/test_coarse.py, 87 000 quadrangles of a 301 x 291 jittered
+    lattice in a fixed random order on 300 x 290 pixels of 7.6 km and four levels.  Level 0 has 340 rows of partials (two trips, 84
+    lanes in the second), level 1 has 85 (lanes of two waves hold sums when block_sum starts), the terms kernel writes 340 rows
+    of counts for the quadrangles and 680 for the triangles (two and three trips).  tests/test_coarse.py proves these sizes, and
+    that the boxes behind the first trip are filled, from the restatement alone; it also gives the restatement's CPU times.
+
+    What a wrong second trip breaks.  coarse_table_kernel: a dropped trip loses the 19 117 pixels with a cell from number
+    kCoThreads^2 on -- the two counting columns of level 0, compared as integers, are short by that, and each moment by a share
+    of more than 1e9 times its bound; a wrong stride takes rows twice or not at all, the same two assertions.  coarse_count_kernel:
+    nin and nout are exact against the restatement, and the `use` mask takes one contributing cell out of every trip, so a trip
+    that is dropped or counted twice cannot cancel against it.  The sort: a key bit above the 16th left out merges the runs of
+    pixels p and p + 65536 -- `boxes` then differ in bits at level 0."""
+    s = big_sizes()
+    check_big_sizes(s)                                                    # before the device is asked anything
+    yx, yx1, quads = big_case()
+    d = BIG_GRID[2]
+    want = big_coarse("quads")
+    assert want["nout"] > 0 and s["end_bit"] >= 17
+    for l, first in ((0, s["T"] ** 2), (1, 64 * s["T"])):                 # rows of the second trip, lanes of the second wave
+        share, nsome, nfilled = late_share(want["levels"][l], d * 2. ** l, 0.5, first)
+        assert nsome > 0 and nfilled > 0 and all(a > 1e3 * b for a, b in share), l
+    got =ctx.coarse_cells(yx, yx1, quads, DAY, BIG_GRID, BIG_NLEV, boxes=True)
+    same_bits(got, want, "87000 quadrangles", d=d)
+    # without `boxes`: the same launches, the same table
+    assert np.array_equal(bits(ctx.coarse_cells(yx, yx1, quads, DAY, BIG_GRID, BIG_NLEV)["table"]), bits(got["table"]))
+    # the same cells as 174 000 triangles: three trips over the rows of counts
+    same_bits(ctx.coarse_cells(yx, yx1, split_quads(quads), DAY, BIG_GRID, BIG_NLEV, boxes=True), big_coarse("tris"), "174000 triangles", d=d)
+    # one contributing cell switched off in every trip of the count loop
+    use, off, trips = big_use()
+    assert trips == [0, 1, 1]
+    masked = ctx.coarse_cells(yx, yx1, quads, DAY, BIG_GRID, BIG_NLEV, use=use, boxes=True)
+    same_bits(masked, big_coarse("use"), "87000 quadrangles, three switched off", d=d)
+    assert (masked["nin"], masked["nout"]) == (got["nin"] - 2, got["nout"] - 1)
 
 
 # ------------------------------------------------------------------------------------------------ 3., 4. one long run; clipping

@@ -26,7 +26,8 @@ from test_deform import FILL
 from test_driver import make_case
 from test_gpu_deform import bits, same_as, tracked_case
 from test_mesh import mesh_deform_ref, stat_terms
-from test_tri2quad import tri2quad_ref, tri2quad_rounds
+from test_coarse import coarse_ref
+from test_tri2quad import chain_constants, tri2quad_ref, tri2quad_rounds, up
 
 pytestmark = pytest.mark.gpu
 K, KSTRT, RDT = 8, 3, 3600.
@@ -44,9 +45,23 @@ def cloud(ny=25, nx=24):
     return grid, u, v, sic, yx, ji
 
 
-def start(ny=25, nx=24, first=None, last=None):
+DENSE_N, DENSE_KM = 340, 0.5
+
+
+def dense_cloud(n=DENSE_N, spacing=DENSE_KM):
+    """cloud()'s make at another scale: n x n points `spacing` km apart about the same centre, jittered by the same fraction of
+    the spacing.  The mesh is then built with rmax_km = spacing.  340 x 340 at 0.5 km are 115 600 buoys on 170 km of the 256-km
+    domain, some 10 000 of them on the block of land."""
+    grid, u, v, sic, _, _ = tracked_case()
+    j, i = np.meshgrid(np.arange(n) - 0.5 * (n - 1), np.arange(n) - 0.5 * (n - 1), indexing="ij")
+    jit = 0.8 / 3.5 * spacing
+    yx = np.stack([-20. + spacing * j.ravel(), spacing * i.ravel()], axis=1) + np.random.default_rng(3).uniform(-jit, jit, (n * n, 2))
+    return grid, u, v, sic, yx, syn.regular_host_cell(grid, yx)
+
+
+def start(ny=25, nx=24, first=None, last=None, case=None):
     """a tracker on the case, two records stepped from KSTRT: the next record is JREC0"""
-    grid, u, v, sic, yx, ji = cloud(ny, nx)
+    grid, u, v, sic, yx, ji = case or cloud(ny, nx)
     trk = sit.IceTracker(grid["Yf"], grid["Xf"], grid["Yu"], grid["Xu"], grid["Yv"], grid["Xv"], grid["tmask"], rdt=RDT, nslots=K)
     for k in range(K):
         trk.load_record(k, u[k], v[k], sic[k])
@@ -262,6 +277,79 @@ def test_a_mesh_of_more_than_1024_quadrangles():
         s1 = ctx.fetch()
         _, rs, _ = mesh_deform_ref(s["yx"], s1["yx"], cells, (jrec1 - JREC0 + 1) * RDT, s["alive"], s1["alive"])
         assert np.array_equal(res["status"], rs)
+    finally:
+        trk.close()
+
+
+def late_terms(terms, index, first, n):
+    """[(|exactly rounded sum of the terms of the cells of index >= first|, the bound (n + 16) 2^-53 fsum|t| over all terms)] of
+    the rows of `terms`, whose columns belong to the cells `index`"""
+    late = np.asarray(index) >= first
+    return [(abs(math.fsum(t[late])), (n + 16) * 2. ** -53 * math.fsum(np.abs(t))) for t in terms]
+
+
+def test_a_mesh_of_more_than_256_rows_of_partial_sums():
+    """mesh_sum_kernel -- lane l takes the rows l, l + kMeshThreads, ... of mesh_cells_kernel's partial sums -- past its first
+    trip, and with it the SRC = 1 path of coarse_terms_kernel and coarse_count_kernel past 256 rows of counts: dense_cloud(), 340 x
+    340 buoys 0.5 km apart, gives a mesh of more than 70 000 quadrangles, more than 273 rows.  The cells are held to the
+    host-array chain on the same handle (the numpy Delaunay restatement is pinned past its caps by tests/test_cloud_trips.py),
+    status, counts and rates to mesh_deform_ref on the fetched positions (0.1 s at this size), the sums to check_stats' bound.
+
+    What a wrong second trip breaks: a dropped trip loses the cells from number kMeshThreads^2 on -- n0, n1 and n2, compared as
+    integers, are short by them, and each of the seven sums by a share that is asserted to be more than 1000 times its bound; a
+    wrong stride takes rows twice or not at all, the same assertions.  For sitrk_mesh_coarse nin + nout must equal n1."""
+    from test_gpu_coarse import same_bits                             # that module imports this one
+    c = chain_constants()
+    T = c["kMeshThreads"]
+    assert 70000 >= T * T + 16 * T and up(up(70001, T), T) == 2 and c["kCoThreads"] * (c["kCoThreads"] + 16) <= 70000
+    trk = start(case=dense_cloud())
+    try:
+        ctx = trk.ctx
+        s0 = ctx.fetch()
+        trk.deform_mark(JREC0)
+        r = trk.mesh(DENSE_KM, JREC0)
+        assert r["nQ"] > 70000, r                                     # the device's count: more than kMeshThreads + 16 rows
+        cells = trk.mesh_cells()
+        tris, quads, rounds = host_chain(ctx, s0, DENSE_KM)
+        assert r == {"nT": len(tris), "nQ": len(quads), "rounds": rounds} and np.array_equal(cells, quads)
+        jrec1 = advance(trk, JREC0, 3, 3)
+        s1 = ctx.fetch()
+        Tsec = (jrec1 - JREC0 + 1) * RDT
+        ro, rs, rstats = mesh_deform_ref(s0["yx"], s1["yx"], cells, Tsec, s0["alive"], s1["alive"])
+        counts = [int((rs == k).sum()) for k in range(3)]
+        late = [int((rs[T * T:] == k).sum()) for k in range(3)]
+        print("nQ %d in %d rows; status 0/1/2: %r, of the cells from %d on: %r" % (len(cells), up(len(cells), T), counts, T * T, late))
+        assert min(counts) >= 5 and late[1] >= 100                       # all three statuses; status 1 in the second trip
+        n1 = counts[1]
+        share = late_terms(stat_terms(ro, rs), np.flatnonzero(rs == 1), T * T, n1)
+        assert all(a > 1e3 * b for a, b in share), share
+        res = trk.mesh_deform(jrec1)
+        assert res["status"].dtype == np.int8 and np.array_equal(res["status"], rs)
+        assert [res["stats"][n] for n in ("n0", "n1", "n2")] == rstats[:3].tolist() == counts
+        same_as((np.stack([res[n] for n in RATES]), res["status"] != 0), (ro, rs != 0), "dense mesh")
+        check_stats(res, "dense mesh")
+        o2, v2, _ = ctx.deform_since_mark(jrec1, cells)
+        same_rates(res, o2, v2, "dense mesh")
+        # two calls in a row and the stats alone: the same bits
+        as_bits = lambda d: [np.float64(d[n]).view(np.uint64) for n in _lib.MESH_STATS]      # noqa: E731
+        again = trk.mesh_deform(jrec1)
+        assert np.array_equal(again["status"], res["status"]) and all(np.array_equal(bits(again[n]), bits(res[n])) for n in RATES)
+        assert as_bits(again["stats"]) == as_bits(res["stats"])
+        only = trk.mesh_deform(jrec1, full=False)
+        assert sorted(only) == sorted(_lib.MESH_STATS) and as_bits(only) == as_bits(res["stats"])
+        # sitrk_mesh_coarse on this mesh = sitrk_coarse_cells on the fetched positions = the restatement
+        lo, hi = s0["yx"].min(axis=0), s0["yx"].max(axis=0)
+        grid = sit.raster_grid(lo[0] + 9., hi[0] + 3., lo[1] - 2., hi[1] - 11., 0.45)        # the mesh reaches beyond it on two sides
+        nlev = 4
+        assert grid[3] * grid[4] > c["kCoThreads"] ** 2
+        raw = ctx.mesh_coarse(0, jrec1, grid, nlev, boxes=True)
+        host = ctx.coarse_cells(s0["yx"], s1["yx"], cells, Tsec, grid, nlev, mask0=s0["alive"], mask1=s1["alive"], use=(rs == 1), boxes=True)
+        want = coarse_ref(s0["yx"], s1["yx"], cells, Tsec, grid, nlev, mask0=s0["alive"], mask1=s1["alive"], use=(rs == 1))
+        same_bits(raw, host, "dense mesh against coarse_cells")
+        assert np.array_equal(bits(raw["table"]), bits(host["table"]))                         # the same launches: the same sums
+        same_bits(raw, want, "dense mesh against the restatement", d=grid[2])
+        assert raw["nout"] > 0 and raw["nin"] > 100 and raw["nin"] + raw["nout"] == n1 and up(len(cells), c["kCoThreads"]) > c["kCoThreads"]
+        assert np.array_equal(bits(ctx.mesh_coarse(0, jrec1, grid, nlev)["table"]), bits(raw["table"]))
     finally:
         trk.close()
 

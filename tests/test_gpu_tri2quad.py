@@ -8,8 +8,8 @@ import sitrack_amd as sit
 from sitrack_amd import _lib
 from test_deform import DAY3, check_linear_field, jittered_lattice, linear_move
 from test_gpu_deform import tracked_case
-from test_tri2quad import (INF, _shoelace, as_set, candidates, chain_case, check_shape, defect_case, params, tri2quad_ref,
-                           tri2quad_rounds)
+from test_tri2quad import (INF, _shoelace, as_set, big_case, big_ref, candidates, chain_case, chain_constants, check_shape,
+                           check_shape_fast, defect_case, params, scan_shape, tri2quad_ref, tri2quad_rounds, up)
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +78,40 @@ def test_many_workgroups_and_a_contended_table(ctx):
     assert len(quads) > 50000
     ms = ctx.tri2quad_kernel_ms()
     print("257 x 257: %d quadrangles in %d rounds; adjacency %.3f, scores %.3f, rounds %.3f, compaction %.3f ms" % ((len(quads), rounds) + ms))
+    assert all(m >= 0. for m in ms)
+
+
+def test_more_than_one_chunk_of_block_counts(ctx):
+    """quad_scan_kernel scans the counts of the compaction's blocks (kQmBlock triangles each) in chunks of kQmBlock blocks, with a
+    carry in LDS from chunk to chunk: a second chunk needs more than kQmBlock^2 = 1 048 576 triangles.  The 726 x 726 jittered
+    lattice has 1 051 250: 1 027 blocks, two chunks, the second of three blocks, all three with leaders.
+
+    The comparison is the full one, against tri2quad_ref: 2.7 s on the CPU at this size, computed once (tests/test_tri2quad.py,
+    which also proves the sizes without a device).  The round form, 3.0 s more, is left to the cases below 2^20 triangles: the
+    rounds are over before the scan starts.  What a wrong second trip breaks: a carry that is dropped, or not added, makes the rows
+    of the blocks from kQmBlock on start again at 0 -- tri_quad differs from the restatement's in every matched triangle from
+    number kQmBlock^2 on (more than 100 leaders, asserted), the rows of `quads` from late_offset on are overwritten or never
+    written, and the total, hence the length of `quads`, is short by late_offset; a chunk read at a wrong stride moves every
+    offset behind it.  check_shape_fast pins the same from the device's output alone: the leaders in ascending triangle id hold
+    0, 1, 2, ..., nQ - 1, and every row is the canonical quadrangle of its two triangles."""
+    c = chain_constants()
+    B = c["kQmBlock"]
+    yx, tris = big_case()
+    nT = len(tris)
+    assert nT == 1051250 and (up(nT, B), up(up(nT, B), B)) == (1027, 2)                 # before the device is asked anything
+    rq, rtq = big_ref()
+    quads, tri_quad, rounds = ctx.tri2quad(yx, tris)
+    assert quads.dtype == np.int32 and tri_quad.dtype == np.int32
+    assert len(quads) == len(rq), (len(quads), len(rq))
+    assert np.array_equal(tri_quad, rtq), np.flatnonzero(tri_quad != rtq)[:8]
+    assert np.array_equal(quads, rq), np.flatnonzero((quads != rq).any(axis=1))[:8]
+    lead, second = check_shape_fast(yx, tris, quads, tri_quad)
+    s = scan_shape(nT, lead, c)
+    print("726 x 726: %d quadrangles in %d rounds, %r" % (len(quads), rounds, s))
+    assert s["chunks"] == 2 and s["late_blocks_with_leaders"] == 3 and s["late_leaders"] >= 100 and s["late_offset"] > 0
+    assert tri_quad[lead[lead >= B * B][0]] == s["late_offset"] and s["late_offset"] + s["late_leaders"] == len(quads)
+    assert rounds == 3                                                      # what tri2quad_rounds gives on this case, recorded
+    ms = ctx.tri2quad_kernel_ms()
     assert all(m >= 0. for m in ms)
 
 

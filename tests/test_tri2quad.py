@@ -4,6 +4,7 @@ the number of rounds the device must report -- held against each other on every 
 and repeated triangles, three-fold edges, the binding and sit.Tri2Quad's argument errors."""
 import math
 import os
+import re
 import sys
 
 import numpy as np
@@ -175,8 +176,77 @@ def check_shape(yx, tris, quads, tri_quad):
         assert (_shoelace(np.asarray(yx, dtype=np.float64)[quads]) > 0).all()
 
 
+def check_shape_fast(yx, tris, quads, tri_quad):
+    """check_shape() without a Python loop over the rows, for results of a million triangles.  The leaders -- the first
+    triangle of every row, in ascending triangle id -- hold exactly 0, 1, 2, ..., nQ - 1, every row occurs exactly twice, and
+    every row is made of its two triangles' vertices, counter-clockwise from its smallest index.  Returns (leaders, seconds),
+    the triangle ids of the two halves of every row."""
+    tris = np.asarray(tris).reshape(-1, 3)
+    assert quads.dtype == np.int32 and tri_quad.dtype == np.int32 and tri_quad.shape == (len(tris),)
+    tid = np.flatnonzero(tri_quad >= 0)
+    val = tri_quad[tid]
+    assert len(tid) == 2 * len(quads)
+    order = np.argsort(val, kind="stable")                          # equal values stay in ascending triangle id
+    val, tid = val[order], tid[order]
+    assert np.array_equal(val, np.repeat(np.arange(len(quads)), 2))
+    lead, second = tid[0::2], tid[1::2]
+    assert (lead < second).all() and (np.diff(lead) > 0).all()
+    six = np.concatenate([tris[lead], tris[second]], axis=1)
+    assert (quads[:, :, None] == six[:, None, :]).any(axis=2).all() and (six[:, :, None] == quads[:, None, :]).any(axis=2).all()
+    assert (np.diff(np.sort(quads, axis=1), axis=1) > 0).all() and (quads[:, 0] == quads.min(axis=1)).all()
+    if len(quads):
+        assert (_shoelace(np.asarray(yx, dtype=np.float64)[quads]) > 0).all()
+    return lead, second
+
+
+def chain_constants():
+    """the launch constants of the deformation chain (tri2quad, mesh, coarse), read from the text of its sources: name -> int"""
+    out = {}
+    for fn, names in (("sitrk_quadmesh.hip", ("kQmThreads", "kQmBlock")), ("sitrk_mesh.hip", ("kMeshThreads",)),
+                      ("sitrk_coarse.hip", ("kCoThreads",))):
+        src = open(os.path.join(ROOT, "sitrack_amd", "csrc", fn)).read()
+        for name in names:
+            found = re.findall(r"constexpr\s+[\w\s]+?\b%s\s*=\s*(\d+(?:\s*\*\s*\d+)*)\s*;" % name, src)
+            assert len(found) == 1, (fn, name, found)
+            out[name] = math.prod(int(f) for f in found[0].split("*"))
+    return out
+
+
+def up(a, b):
+    """ceil(a / b) of two integers"""
+    return -(-a // b)
+
+
 def as_set(quads):
     return set(map(tuple, np.asarray(quads).tolist()))
+
+
+# the case of tests/test_gpu_tri2quad.py that takes quad_scan_kernel into a second chunk: a jittered lattice of BIG_N x BIG_N points
+BIG_N = 726
+
+
+def big_case():
+    """(yx, tris) of the BIG_N x BIG_N jittered lattice, 2 (BIG_N - 1)^2 triangles"""
+    return jittered_lattice(BIG_N, BIG_N, -2000., 1500., seed=31), sit.lattice_cells(BIG_N, BIG_N, "tri")
+
+
+_BIG = {}
+
+
+def big_ref():
+    """tri2quad_ref of big_case(), computed once and left unchanged: (quads, tri_quad)"""
+    if not _BIG:
+        _BIG["ref"] = tri2quad_ref(*big_case())
+    return _BIG["ref"]
+
+
+def scan_shape(nT, lead, c):
+    """what quad_count_kernel / quad_scan_kernel / quad_emit_kernel see of nT triangles whose leaders are `lead`: a dict with the
+    blocks, the chunks of the scan, the leaders in blocks of the second and later chunks and the offset of the first such block"""
+    B = c["kQmBlock"]
+    blocks = up(nT, B)
+    return {"blocks": blocks, "chunks": up(blocks, B), "late_leaders": int((lead // B >= B).sum()), "late_offset": int((lead < B * B).sum()),
+            "late_blocks_with_leaders": len(np.unique(lead[lead // B >= B] // B))}
 
 
 def defect_case():
@@ -317,6 +387,48 @@ def test_parameter_edges():
     sq = 10. * np.stack([j.ravel(), i.ravel()], axis=1)
     q, _, _ = both_forms(sq, sit.lattice_cells(4, 4, "tri"), **params(angles=(90., 90.), ratio_min=1.))
     assert len(q) == 9
+
+
+def test_check_shape_fast_holds_what_check_shape_holds():
+    yx, mask, tris = defect_case()
+    quads, tri_quad = tri2quad_ref(yx, tris, mask)
+    check_shape(yx, tris, quads, tri_quad)
+    lead, second = check_shape_fast(yx, tris, quads, tri_quad)
+    assert np.array_equal(tri_quad[lead], np.arange(len(quads))) and np.array_equal(tri_quad[second], np.arange(len(quads)))
+    r = len(quads) // 2
+    spoiled = []
+    tq = tri_quad.copy(); tq[tq >= r] -= r; spoiled.append((quads, tq))                   # the rows start again at 0, a lost carry
+    tq = tri_quad.copy(); tq[tq >= r] += 1; spoiled.append((quads, tq))                    # a row number left out
+    tq = tri_quad.copy(); tq[lead[5]] = -1; spoiled.append((quads, tq))                    # a row that occurs once
+    tq = tri_quad.copy(); tq[lead[[5, 6]]] = tq[lead[[6, 5]]]; tq[second[[5, 6]]] = tq[second[[6, 5]]]; spoiled.append((quads, tq))
+    q = quads.copy(); q[7] = q[7, [1, 2, 3, 0]]; spoiled.append((q, tri_quad))              # not started at its smallest index
+    q = quads.copy(); q[7] = q[7, [0, 3, 2, 1]]; spoiled.append((q, tri_quad))              # clockwise
+    q = quads.copy(); q[7] = q[8]; spoiled.append((q, tri_quad))                            # another pair's row
+    for q, tq in spoiled:
+        with pytest.raises(AssertionError):
+            check_shape_fast(yx, tris, q, tq)
+        with pytest.raises(AssertionError):
+            check_shape(yx, tris, q, tq)
+
+
+def test_big_case_takes_the_block_scan_into_a_second_chunk():
+    """The size conditions of tests/test_gpu_tri2quad.py's case of more than one chunk, from the restatement and the constants
+    read from sitrk_quadmesh.hip, without a device.  tri2quad_ref takes 2.7 s on this case (1 051 250 triangles, 477 010
+    quadrangles; 2.0 s of it are `candidates`), tri2quad_rounds 3.0 s more, measured on the CPU of the development machine."""
+    c = chain_constants()
+    B = c["kQmBlock"]
+    yx, tris = big_case()
+    nT = len(tris)
+    assert nT == 2 * (BIG_N - 1) ** 2 == 1051250 and nT > B * B
+    quads, tri_quad = big_ref()
+    lead, second = check_shape_fast(yx, tris, quads, tri_quad)
+    s = scan_shape(nT, lead, c)
+    print("%d triangles, %d quadrangles: %r" % (nT, len(quads), s))
+    assert (s["blocks"], s["chunks"]) == (1027, 2) and s["blocks"] > B
+    # blocks of the second chunk hold leaders, and their offsets are the carry: not zero, and not what a chunk scanned alone gives
+    assert s["late_blocks_with_leaders"] == s["blocks"] - B and s["late_leaders"] >= 100 and s["late_offset"] > 0
+    assert s["late_offset"] + s["late_leaders"] == len(quads)
+    assert tri_quad[lead[lead >= B * B][0]] == s["late_offset"]
 
 
 # ------------------------------------------------------------------------------------------------ the interfaces
