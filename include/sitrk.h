@@ -800,6 +800,61 @@ int sitrk_keep_skeleton(sitrk_t *h, int keep, int max_sub, int64_t maxfeat, int6
                         int *nsub, int *converged);
 int sitrk_skeleton_kernel_ms(sitrk_t *h, float *thin_ms, float *table_ms, float *nodes_ms);
 
+/* ---- dispersion of buoy pairs: strain moments by separation class ----------------------
+ * An EXTRA the reference does not have: for every pair of points that lie r0 apart at t0, how much their separation has changed
+ * at t1, and per class of r0 the moments of that strain -- the buoy-dispersion analysis of sea-ice deformation (Rampal et al.
+ * 2008).  It needs no triangulation, no quadrangle test and no grid.  No parity claim is made against any other
+ * code; the contract below is this library's own.  Everything in fp64, one rounded operation per symbol in the order written, no
+ * fused multiply-add.
+ * POINTS: yx0, yx1 are (nP,2) [y,x] in km, in the tracker's polar-stereographic plane, at t0 and t1.  A point is VALID iff its
+ * mask0 and mask1 bytes are not 0 (NULL: all) and its four coordinates are finite.
+ * PAIRS: a pair is an unordered i < j of valid points; each pair counts once.
+ *     dy = y_j - y_i ; dx = x_j - x_i ; q0 = dy*dy + dx*dx      on the t0 positions;  q1 the same on the t1 positions
+ * CLASSES: edges_km holds nc + 1 finite, strictly increasing values with edges[0] >= 0, 1 <= nc <= SITRK_PAIRS_MAXCLASS.
+ *     E_c = edges[c]*edges[c]   (one rounded product)
+ * A pair is in class c iff E_c <= q0 && q0 < E_{c+1}, compared in fp64, and it CONTRIBUTES iff it is in a class and q0 > 0.
+ * Only + - * and comparisons decide this: the class of every pair, and so every count, is pinned bit for bit.
+ * A PAIR'S TERMS:
+ *     r0 = sqrt(q0) ; r1 = sqrt(q1) ; d = (q1 - q0)/(r0 + r1) ; e = d/r0
+ * d is r1 - r0 formed without cancelling two square roots: q1 - q0 is pinned, the only unpinned operations are the device's two
+ * sqrt.  e is the pair's strain over the interval.  The elapsed time does not enter: rates are e/T on the host.
+ * THE TABLE is (nc, SITRK_PAIRS_NCOLS) fp64, one row per class: [0] n, the number of contributing pairs (exact, below 2^53);
+ * [1] sum r0; [2] sum e; [3] sum |e|; [4] sum e*e; [5] sum (e*e)*|e|; [6] sum d*d.  The order of the sums is the
+ * implementation's but fixed by the points and the edges alone: no floating-point atomics, two calls on the same state return
+ * the same bits.  *npts (may be NULL) = the number of valid points.
+ *
+ * sitrk_pairs_points: host arrays; mask0 / mask1 (nP) int8 or NULL.  Synchronous on the handle's stream.  Uses the context's
+ * transient scratch only: the grid, buoys, records, meshes and marks of a tracker on the same handle are left as they were.
+ * nP of 0 or 1 is valid: zeros.  SITRK_EINVAL, before any device work, for nc out of range, edges that are not finite, not
+ * strictly increasing or start below 0, and missing pointers.
+ * COST: the work is the number of pairs within edges[nc] of each other, about nP * rho * pi * edges[nc]^2 / 2 for a cloud of rho
+ * points per km^2, and nothing caps it: it is the caller's to bound, through the mask or a coarsened cloud.
+ * sitrk_pairs_mark is queued on the compute stream behind the stepping already queued and snapshots the current fp64 positions
+ * of all buoys, in the caller's order, with a validity byte each -- alive now and, with a mask (nP, caller's order, may be
+ * NULL), its byte not 0 -- into a device buffer of 17 bytes per buoy that belongs to the context: allocated at the first mark,
+ * overwritten by the next one, freed by sitrk_pairs_free, sitrk_set_buoys and sitrk_destroy, which all cancel the mark.  It is
+ * independent of sitrk_deform_mark and of the meshes.  jrec0 = the model record that will be stepped next.
+ * sitrk_pairs_since_mark is valid right after the step of jrec1 >= jrec0: t0 = the snapshot, t1 = the current positions.  A buoy
+ * is valid iff it was valid at the mark and is a valid vertex under the rule of sitrk_deform_since_mark: alive now and, in sets
+ * with record windows, rec_first <= jrec0 && rec_last >= jrec1.  The table has the bits of sitrk_pairs_points on (the snapshot,
+ * the current positions, those two validities); the snapshot is in the caller's order, so a re-sort between the calls changes
+ * nothing.  It may be called any number of times after one mark, each later jrec1 one more interval from the same t0.  Only
+ * edges_km goes up and 56 bytes per class come down.  SITRK_EINVAL without a mark, for jrec1 < jrec0, without buoys, and as
+ * sitrk_pairs_points for nc, the edges and the pointers.
+ * sitrk_pairs_free: frees the snapshot and cancels the mark; valid at any time.
+ * sitrk_pairs_kernel_ms: GPU time [ms] of the phases of the last table on this handle, from HIP events -- the binning (box, keys,
+ * sort, gather, bin starts), the pairs kernel, the table; any pointer may be NULL, SITRK_EINVAL before any such call.
+ * sitrk_pairs_stats: *tests = the pairs that last table's pairs kernel formed q0 for, all class passes together. */
+#define SITRK_PAIRS_MAXCLASS 16
+#define SITRK_PAIRS_NCOLS 7
+int sitrk_pairs_points(sitrk_t *h, int64_t nP, const double *yx0, const double *yx1, const int8_t *mask0, const int8_t *mask1,
+                       int nc, const double *edges_km, double *table, int64_t *npts);
+int sitrk_pairs_mark(sitrk_t *h, int jrec0, const int8_t *mask);
+int sitrk_pairs_since_mark(sitrk_t *h, int jrec1, int nc, const double *edges_km, double *table, int64_t *npts);
+int sitrk_pairs_free(sitrk_t *h);
+int sitrk_pairs_kernel_ms(sitrk_t *h, float *bin_ms, float *pairs_ms, float *table_ms);
+int sitrk_pairs_stats(sitrk_t *h, int64_t *tests);
+
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,
  * util.Dist2Coast) reads a rasterised dist2coast file.  Here the coast is the model's own: the edges between a sea T-cell

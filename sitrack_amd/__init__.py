@@ -18,6 +18,7 @@ from .quadmesh import Tri2Quad                                                # 
 from .delaunay import DelaunayTris                                           # noqa: F401
 from .raster import RasterCells, raster_grid                                  # noqa: F401
 from .coarse import CoarseCells, scaling_exponents                            # noqa: F401
+from .dispersion import PairDispersion, dispersion_curve, dispersion_exponents, pair_edges, pairs_arg   # noqa: F401
 from .features import SkeletonRaster, node_yx, skeleton_table                                                            # noqa: F401
 from .features import LabelRaster, MatchLabels, feature_table, feature_tracks, link_features                              # noqa: F401
 from ._lib import FEAT_COLS, FEAT_WHAT                                        # noqa: F401

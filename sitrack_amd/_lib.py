@@ -37,6 +37,9 @@ MATCH_MAXSHIFT = 32768                       # |dj|, |di| of sitrk_features_matc
 SKEL_NCOLS = 7                               # SITRK_SKEL_NCOLS, in this order:
 SKEL_COLS = ("label", "npix", "nskel", "nend", "njunc", "north", "ndiag")
 SKEL_MAXSUB = 1 << 20                        # max_sub of the skeleton calls
+PAIRS_MAXCLASS = 16                          # SITRK_PAIRS_MAXCLASS
+PAIRS_NCOLS = 7                              # SITRK_PAIRS_NCOLS, in this order:
+PAIRS_COLS = ("n", "sum_r0", "sum_e", "sum_abs_e", "sum_e2", "sum_abs_e3", "sum_d2")
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -132,6 +135,12 @@ _SIGNATURES = {
     "sitrk_keep_skeleton": (_int, [_vp, _int, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
                                    C.POINTER(_int), C.POINTER(_int)]),
     "sitrk_skeleton_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_pairs_points": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_pairs_mark": (_int, [_vp, _int, _vp]),
+    "sitrk_pairs_since_mark": (_int, [_vp, _int, _int, _vp, _vp, C.POINTER(_i64)]),
+    "sitrk_pairs_free": (_int, [_vp]),
+    "sitrk_pairs_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_pairs_stats": (_int, [_vp, C.POINTER(_i64)]),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -1093,6 +1102,65 @@ class Context:
         v = [C.c_float(0) for _ in range(3)]
         self._chk(self._L.sitrk_skeleton_kernel_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # -- dispersion of buoy pairs (sitrk_pairs_*)
+    @staticmethod
+    def _edges_arg(edges_km):
+        """(nc + 1,) float64, C-contiguous; the library checks the values"""
+        e = as_c(edges_km, np.float64)
+        if e.ndim != 1 or e.shape[0] < 2:
+            raise ValueError("edges_km: expected a 1-D array of at least two values, got shape %s" % (e.shape,))
+        return e
+
+    def pairs_points(self, yx0, yx1, edges_km, mask0=None, mask1=None):
+        """sitrk_pairs_points: every unordered pair of valid points of yx0, yx1 (nP,2) km whose t0 separation lies in a class
+        [edges_km[c], edges_km[c+1]).  A dict with table (nc, 7) fp64 under the names PAIRS_COLS and npts, the valid points.
+        mask0 / mask1 (nP): 0 = not valid."""
+        yx0 = as_c(yx0, np.float64)
+        nP = yx0.shape[0]
+        yx0 = as_c(yx0, np.float64, (nP, 2), "yx0")
+        yx1 = as_c(yx1, np.float64, (nP, 2), "yx1")
+        m0 = None if mask0 is None else as_c(np.asarray(mask0) != 0, np.int8, (nP,), "mask0")
+        m1 = None if mask1 is None else as_c(np.asarray(mask1) != 0, np.int8, (nP,), "mask1")
+        e = self._edges_arg(edges_km)
+        nc = e.shape[0] - 1
+        table = np.zeros((nc, PAIRS_NCOLS), dtype=np.float64)
+        npts = _i64(0)
+        self._chk(self._L.sitrk_pairs_points(self._h, nP, _ptr(yx0), _ptr(yx1), _ptr(m0), _ptr(m1), nc, _ptr(e), _ptr(table),
+                                             C.byref(npts)))
+        return {"table": table, "npts": npts.value}
+
+    def pairs_mark(self, jrec0, mask=None):
+        """sitrk_pairs_mark: snapshot every buoy's position and validity (alive now, mask byte not 0) on the device; jrec0 = the
+        model record stepped next"""
+        m = None if mask is None else as_c(np.asarray(mask) != 0, np.int8, (self.nP,), "mask")
+        self._chk(self._L.sitrk_pairs_mark(self._h, int(jrec0), _ptr(m)))
+
+    def pairs_since_mark(self, jrec1, edges_km):
+        """sitrk_pairs_since_mark, right after the step of jrec1: like pairs_points() between the mark and now, no position
+        leaving the device"""
+        e = self._edges_arg(edges_km)
+        nc = e.shape[0] - 1
+        table = np.zeros((nc, PAIRS_NCOLS), dtype=np.float64)
+        npts = _i64(0)
+        self._chk(self._L.sitrk_pairs_since_mark(self._h, int(jrec1), nc, _ptr(e), _ptr(table), C.byref(npts)))
+        return {"table": table, "npts": npts.value}
+
+    def pairs_free(self):
+        """sitrk_pairs_free: drop the snapshot of pairs_mark()"""
+        self._chk(self._L.sitrk_pairs_free(self._h))
+
+    def pairs_kernel_ms(self):
+        """(bin_ms, pairs_ms, table_ms): GPU time of the phases of the last pair-dispersion table (sitrk_pairs_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_pairs_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def pairs_stats(self):
+        """the pairs whose t0 separation the last table's pairs kernel formed, all class passes together (sitrk_pairs_stats)"""
+        a = _i64(0)
+        self._chk(self._L.sitrk_pairs_stats(self._h, C.byref(a)))
+        return a.value
 
     # -- distance to the model coastline (sitrk_coast_*)
     def coast_build(self, Yf=None, Xf=None, tmask=None):

@@ -69,6 +69,7 @@ static void free_buoys(sitrk_ctx *h)
     h->nP = 0;
     deform_release(h, false);           // the snapshot of sitrk_deform_mark belongs to these buoys
     mesh_release(h, false);             // ... and so do the indices of every mesh
+    pairs_release(h, false);            // ... and the snapshot of sitrk_pairs_mark
 }
 
 static void free_records(sitrk_ctx *h);
@@ -128,6 +129,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     deform_release(h, true);
     coast_release(h, false, true);
     mesh_release(h, true);
+    pairs_release(h, true);
     track_release(h);
     h->quad_timer.release();            // the modules whose timer is all they hold
     h->dl_timer.release();

@@ -258,6 +258,16 @@ struct sitrk_ctx {
     int deform_jrec0 = 0;
     sitrk::PhaseTimer<3> deform_timer;  // around the scatter pass and the cell kernel of the last deform call
 
+    // pair dispersion (sitrk_pairs.hip): the positions of all buoys at sitrk_pairs_mark and a validity byte each, caller order, 17 B
+    // per buoy.  Allocated at the first mark, freed -- and the mark cancelled -- by sitrk_pairs_free and with the buoys.  Events
+    // around the three phases of the last call -- binning, pairs, table --, and its candidate tests
+    sitrk::pt *pairs_t0 = nullptr;
+    int8_t *pairs_v0 = nullptr;
+    bool pairs_marked = false;
+    int pairs_jrec0 = 0;
+    sitrk::PhaseTimer<4> pairs_timer;
+    unsigned long long pairs_tests = 0;
+
     sitrk::CoastState coast;            // distance to the coastline (sitrk_coast.hip)
 
     // quadrangles from triangles (sitrk_quadmesh.hip): events around the phases of the last call -- adjacency, scores, rounds, compaction
@@ -325,6 +335,8 @@ void deform_release(sitrk_ctx *h, bool destroy);
 int deform_points_now(sitrk_ctx *h, pt *out);
 // ... and the pass of sitrk_deform_since_mark: NaN in y also for a buoy whose record window does not cover [jrec0, jrec1] (sitrk_mesh.hip)
 int deform_points_span(sitrk_ctx *h, int jrec0, int jrec1, pt *out);
+// sitrk_pairs.hip: frees the snapshot of sitrk_pairs_mark and cancels the mark (free_buoys of sitrk.hip); destroy = the timer too
+void pairs_release(sitrk_ctx *h, bool destroy);
 // sitrk_mesh.hip: frees every mesh (free_buoys of sitrk.hip); destroy = the timers too
 void mesh_release(sitrk_ctx *h, bool destroy);
 // ... and the body of sitrk_mesh_deform behind its argument checks (mesh_deform_check), everything left in the transient scratch:

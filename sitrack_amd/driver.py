@@ -18,9 +18,10 @@ record only, and the always-written 2-record file keeps records 0 and Nt.
 `main()` is the run itself: open_run, read_mesh / sample_vars, init_seeds / seed_windows, open_tracker, then the record loop
 over plan_batches.  What the loop keeps between batches lives in one object per concern -- Partition (who owns which buoys,
 re-balancing), BoxIngest (which hyperslab of a record is read), Outputs (the series and the two-record file) and, where the
-run asks for them, Sampler (--sample) and DeformSeries (--deform), None otherwise.
+run asks for them, Sampler (--sample), DeformSeries (--deform) and PairSeries (--pairs), None otherwise.
 """
 import argparse
+import math
 import os
 from datetime import datetime, timezone
 from os import path
@@ -28,7 +29,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib, coarse, features, ncio, raster
+from . import _lib, coarse, dispersion, features, ncio, raster
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
@@ -141,7 +142,25 @@ def parse_args(argv=None):
                          '(rows, 3) int64 -- pixel, label, X of every end (X = 1), junction (X >= 3) and isolated pixel (X = 0) -- with '
                          'm<k>_w<k>_skeleton_counts = (nfeat, nnode, nskel, nsub, converged), next to `skeleton` = (max_sub,); the '
                          'feature count and the longest skeleton are logged')
+    ap.add_argument('--pairs', type=_pairs_arg, default=None, metavar='R_LO:R_HI:NC|e0,e1,...[@RD_KM]',
+                    help='dispersion of buoy pairs (extra; default none): for every pair of buoys r0 apart at the start of a window the '
+                         'strain (r1 - r0)/r0 of their separation, summed on the GPU per class of r0 -- NC geometric classes from R_LO '
+                         'to R_HI km, or the explicit edges e0,e1,... (at most 16 classes) -- from the positions that live there: '
+                         'per class the pairs and the sums of r0, e, |e|, e^2, |e|^3 and (r1 - r0)^2.  @RD_KM first coarsens the alive '
+                         'cloud to that spacing; the work grows with the pairs within the last edge.  Written to '
+                         './npz/<...>_pairs_<...>.npz as w<k>_pairs (ntau, nc, 7) with w<k>_jrec1, w<k>_T and w<k>_npts, next to '
+                         '`edges`, `windows` and `time0`; the pairs per class and the scaling exponents are logged.  One rank only')
+    ap.add_argument('--pairs-window', type=_pairs_count_arg('--pairs-window'), default=None,
+                    help='with --pairs: model records per window (extra; default 0 = the whole run is one window).  The t0 positions are '
+                         'taken in front of each window; a last, shorter window is kept')
+    ap.add_argument('--pairs-every', type=_pairs_count_arg('--pairs-every'), default=None,
+                    help='with --pairs: a table after every so many records of a window and at its end, all from the window\'s own t0 '
+                         '(extra; default 0 = at the window\'s end only)')
     a = ap.parse_args(argv)
+    for flag, v in (('--pairs-window', a.pairs_window), ('--pairs-every', a.pairs_every)):
+        if v is not None and a.pairs is None:
+            ap.error("%s: there is no table to take without --pairs" % flag)
+    a.pairs_window, a.pairs_every = a.pairs_window or 0, a.pairs_every or 0
     refusal = deform_track_refusal(a.deform_track, a.deform_features, a.deform_grid, len(a.deform))
     if refusal:
         ap.error(refusal)
@@ -281,6 +300,54 @@ def _deform_window_arg(text):
     return n
 
 
+def _pairs_arg(text):
+    """--pairs: (edges, rd_km or 0.) of R_LO:R_HI:NC[@RD_KM] or e0,e1,...[@RD_KM], RD_KM finite > 0"""
+    err = argparse.ArgumentTypeError
+    tok = text.split('@')
+    if len(tok) not in (1, 2):
+        raise err("--pairs: expected R_LO:R_HI:NC or e0,e1,..., with @RD_KM or without, got %r" % text)
+    try:
+        edges = dispersion.pairs_arg(tok[0], '--pairs')
+    except ValueError as e:
+        raise err(str(e))
+    rd = 0.
+    if len(tok) == 2:
+        try:
+            rd = float(tok[1])
+        except ValueError:
+            rd = math.nan
+        if not (math.isfinite(rd) and rd > 0.):
+            raise err("--pairs: RD_KM must be finite and > 0, got %r" % text)
+    return (edges, rd)
+
+
+def _pairs_count_arg(flag):
+    def parse(text):
+        try:
+            n = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError("%s: expected an integer, got %r" % (flag, text))
+        if n < 0:
+            raise argparse.ArgumentTypeError("%s: must be >= 0 records, got %d" % (flag, n))
+        return n
+    return parse
+
+
+def pair_windows(Nt, kstrt, nwin, every):
+    """--pairs-window, --pairs-every: [(jrec0, [jrec1, ...])]: the windows of deform_windows and, per window, the model records
+    behind which a table is taken -- every `every`-th of the window (0: none) and its last"""
+    out = []
+    for j0, j1 in deform_windows(Nt, kstrt, nwin):
+        at = list(range(j0 + every - 1, j1, every)) if every > 0 else []
+        out.append((j0, at + [j1]))
+    return out
+
+
+def pair_cuts(windows):
+    """the model records behind which a batch must end for --pairs"""
+    return sorted({j for _, js in windows for j in js})
+
+
 def deform_windows(Nt, kstrt, nwin):
     """--deform-window: the windows [(jrec0, jrec1)] of model records, nwin records each (0: the whole run), the last one
     shorter where nwin does not divide Nt"""
@@ -298,7 +365,8 @@ def plan_batches(Nt, kstrt, K, lFull, stride=1, ends=(), firsts=None, cuts=None)
     """The record loop's batches [(jt, m)]: consecutive records go into one sitrk_run of up to K // 2 records, cut after every
     record whose output is due (output_due) and -- only when fields are sampled (`firsts` = the distinct first records of the
     buoys' windows) -- in front of every record some buoy starts in, where its seed is sampled before the step.  `cuts`: model
-    records after each of which a batch ends as well (--deform: the last record of every window)."""
+    records after each of which a batch ends as well (--deform: the last record of every window; --pairs: the records it takes a
+    table behind)."""
     firsts = set(firsts) if firsts is not None else set()
     cuts = set(cuts) if cuts is not None else set()
     batches, jt = [], 0
@@ -1020,6 +1088,55 @@ class DeformSeries:
                        **({"skeleton": np.array([self.skel], dtype=np.int64)} if self.skel is not None else {}))
 
 
+class PairSeries:
+    """--pairs: the dispersion of buoy pairs from the positions that live on the GPU: a mark in front of every window of model
+    records, a table behind each record the window asks for, all from the window's own t0.
+      win      [(jrec0, [jrec1, ...])];  first: model record -> the window it opens;  at: model record -> the window it belongs to"""
+
+    def __init__(self, spec, window, every, Nt, kstrt, ctx, trk, nP, say, clk):
+        self.edges, self.rd = spec
+        self.ctx, self.trk, self.nP, self.say, self.clk = ctx, trk, nP, say, clk
+        self.win = pair_windows(Nt, kstrt, window, every)
+        self.first = {w[0]: k for k, w in enumerate(self.win)}
+        self.at = {j: k for k, w in enumerate(self.win) for j in w[1]}
+        self.out = {k: [] for k in range(len(self.win))}
+
+    def mark(self, kw):
+        """in front of the first record of window kw: the t0 of its pairs, the cloud as it is now"""
+        t_d = self.clk.now()
+        msk = None
+        if self.rd > 0.:                                 # the alive cloud, coarsened to spacing rd on the positions as they are now
+            st = self.ctx.fetch()
+            al = np.asarray(st["alive"]) != 0
+            msk = np.zeros(self.nP, dtype=np.int8)
+            if al.any():
+                msk[np.where(al)[0][self.ctx.subsample_cloud(st["yx"][al], self.rd)[0]]] = 1
+        self.trk.pairs_mark(self.win[kw][0], msk)
+        self.clk.add("pairs_s", t_d)
+
+    def take(self, jrec1):
+        """behind the step of jrec1: the table since the start of its window"""
+        t_d = self.clk.now()
+        kw = self.at[jrec1]
+        r = self.trk.pairs(jrec1, self.edges)
+        self.out[kw].append((jrec1, r["T"], r["table"], r["npts"]))
+        beta = dispersion.dispersion_exponents(r["table"], r["T"])["beta"]
+        self.say(' *** --pairs window %d record %d (T = %g s): %d points, pairs per class %s, beta(1..3) = %s'
+                 % (kw, jrec1, r["T"], r["npts"], ' '.join('%d' % n for n in r["table"][:, 0]), ' '.join('%.3f' % b for b in beta)))
+        self.clk.add("pairs_s", t_d)
+
+    def write(self, fname, vTime, kstrt):
+        members = {}
+        for kw, rows in self.out.items():
+            members["w%d_jrec1" % kw] = np.array([r[0] for r in rows], dtype=np.int64)
+            members["w%d_T" % kw] = np.array([r[1] for r in rows], dtype=np.float64)
+            members["w%d_pairs" % kw] = np.array([r[2] for r in rows], dtype=np.float64).reshape(len(rows), len(self.edges) - 1, _lib.PAIRS_NCOLS)
+            members["w%d_npts" % kw] = np.array([r[3] for r in rows], dtype=np.int64)
+        _savez_deflate(fname, edges=np.asarray(self.edges, dtype=np.float64),
+                       windows=np.array([(w[0], w[1][-1]) for w in self.win], dtype=np.int64).reshape(-1, 2),
+                       time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64), **members)
+
+
 class Outputs:
     """The files of positions.  The reference allocates the whole series -- xPosC, xPosG (Nt+1,nP,2) f8, xmask -- and writes it
     at the end (:324-330,515-519).  Here, with -F, the series file is opened at once and every record is appended when it is
@@ -1136,6 +1253,9 @@ def main(argv=None):
     if a.deform and comm.multi:
         comm.close()
         raise ValueError('--deform: the cells of a mesh would span the ranks\' buoy ranges; run it on one rank (%d ranks here)' % comm.world)
+    if a.pairs is not None and comm.multi:
+        comm.close()
+        raise ValueError('--pairs: the pairs would span the ranks\' buoy ranges; run it on one rank (%d ranks here)' % comm.world)
     say = print if comm.root else (lambda *args, **kw: None)
     say('\n *** SITRACK ice particule tracker, GPU build; NetCDF backend = ' + ncio.backend()
         + ('; %d ranks (%s)' % (comm.world, comm.backend) if comm.multi else ''))
@@ -1170,6 +1290,7 @@ def main(argv=None):
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
                        say, clk, coarse=a.deform_coarse, feat=a.deform_features, track=a.deform_track,
                        skel=a.deform_skeleton) if a.deform else None
+    prs = PairSeries(a.pairs, a.pairs_window, a.pairs_every, Nt, kstrt, ctx, trk, nP, say, clk) if a.pairs is not None else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE
     #      fused launch (sitrk_run: every buoy still takes every step, only the loop nest is interchanged) whenever no
@@ -1177,7 +1298,7 @@ def main(argv=None):
     #      only (:565-571).  Records are read straight into the library's pinned staging and uploaded on its copy stream
     #      while the previous batch is stepped with; `-F` / `-p` need every record's positions: batches of one.
     batches = plan_batches(Nt, kstrt, K_plan, out.lFull, out.stride, out.ends, smp.firsts if smp and run.lUse2DTime else None,
-                           cuts=set(dfm.last) if dfm else None)
+                           cuts=(set(dfm.last) if dfm else set()) | (set(prs.at) if prs else set()) if dfm or prs else None)
     tplan = plan_tinterp(batches, Nt, K) if tphase is not None else None
     due = rebalance_due(batches, a.rebalance, comm.multi)
     tk = clk.add("setup_s", tk)
@@ -1204,6 +1325,9 @@ def main(argv=None):
         if dfm and jrec0 in dfm.first:
             dfm.build(dfm.first[jrec0])
             t_q = clk.now()
+        if prs and jrec0 in prs.first:
+            prs.mark(prs.first[jrec0])
+            t_q = clk.now()
         if tplan is None:
             trk.run(jrec0, jt0 % K, m)
         else:
@@ -1224,6 +1348,8 @@ def main(argv=None):
                 ingest.upload_recs(batches[ib + 1][0], tplan[ib]["behind"])
         if dfm and jrecN in dfm.last:
             dfm.take(dfm.last[jrecN])
+        if prs and jrecN in prs.at:
+            prs.take(jrecN)
         t_f = clk.now()
         if out.need(jrecN):
             rec = out.fetch(trk, part, jrecN)
@@ -1267,6 +1393,9 @@ def main(argv=None):
     if dfm:
         outs.append(out_file(run, 'deformation', out.vTime[0], out.vTime[Nt], ext='npz'))
         dfm.write(outs[-1], out.vTime, kstrt)
+    if prs:
+        outs.append(out_file(run, 'pairs', out.vTime[0], out.vTime[Nt], ext='npz'))
+        prs.write(outs[-1], out.vTime, kstrt)
     if a.plot > 0:
         try:
             import mojito as mjt          # noqa: F401  optional, as in the reference (:20,587-600)

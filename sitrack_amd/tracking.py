@@ -170,9 +170,12 @@ class IceTracker:
         self.ctx.set_params(rdt, iUVstrategy, rmin)
         self.ctx.set_substeps(nsub)
         self.ctx.alloc_records(nslots, field_dtype)
+        self._rdt = float(rdt)
+        self._pairs_jrec0 = None
 
     def set_buoys(self, xPosC0, vJIt, z1stModelRec=None, zLstModelRec=None, sort=True):
         self.ctx.set_buoys(xPosC0, vJIt, z1stModelRec, zLstModelRec, sort=sort)
+        self._pairs_jrec0 = None                            # the library cancels the mark of pairs_mark()
 
     def _check_exact(self, xUu, xVv, xIC):
         dt = self.ctx.field_dtype
@@ -257,6 +260,47 @@ class IceTracker:
         from .deformation import _as_dict
         out, valid, _ = self.ctx.deform_since_mark(jrec1, cells)
         return _as_dict(out, valid)
+
+    def pairs_mark(self, jrec0, mask=None):
+        """Snapshot every buoy's fp64 position and validity on the device as the t0 of pairs() (an extra the reference does not
+        have; sitrk_pairs_mark); `jrec0` = the model record that will be stepped next; mask (nP): 0 = the buoy takes no part.
+        Independent of deform_mark() and of the meshes."""
+        cerr = 'ERROR [IceTracker.pairs_mark()]: '
+        try:
+            bad = int(jrec0) != jrec0
+        except (TypeError, ValueError):
+            bad = True
+        if bad:
+            raise ValueError(cerr + '`jrec0` must be an integer, got %r' % (jrec0,))
+        if mask is not None and np.shape(mask) != (self.ctx.nP,):
+            raise ValueError(cerr + '`mask` must be (%d,), got %s' % (self.ctx.nP, np.shape(mask)))
+        self.ctx.pairs_mark(int(jrec0), mask)
+        self._pairs_jrec0 = int(jrec0)
+
+    def pairs(self, jrec1, edges_km):
+        """Right after the step of `jrec1`: the pair-dispersion table between the mark and now for the classes `edges_km`, from
+        the device-resident positions (sitrk_pairs_since_mark).  Same dict as sit.PairDispersion plus "T" = (jrec1 - jrec0 + 1)*rdt
+        seconds; a buoy takes part where it was valid at the mark, is alive and was stepped at every record of the span.  May be
+        called again and again after one mark."""
+        from .dispersion import check_edges
+        cerr = 'ERROR [IceTracker.pairs()]: '
+        e = check_edges(edges_km, cerr)
+        if self._pairs_jrec0 is None:
+            raise ValueError(cerr + 'no mark: call pairs_mark() first (set_buoys() and pairs_free() cancel it)')
+        try:
+            bad = int(jrec1) != jrec1
+        except (TypeError, ValueError):
+            bad = True
+        if bad or int(jrec1) < self._pairs_jrec0:
+            raise ValueError(cerr + '`jrec1` must be an integer >= the mark\'s record %d, got %r' % (self._pairs_jrec0, jrec1))
+        r = self.ctx.pairs_since_mark(int(jrec1), e)
+        r["T"] = float(int(jrec1) - self._pairs_jrec0 + 1) * self._rdt
+        return r
+
+    def pairs_free(self):
+        """Drop the snapshot of pairs_mark() (sitrk_pairs_free)"""
+        self.ctx.pairs_free()
+        self._pairs_jrec0 = None
 
     def quads(self, tris, angles=(60., 120.), ratio_min=0.5, area=(0., float("inf"))):
         """Quadrangles (nQ,4) of buoy indices and tri_quad (nT,) from the triangles `tris` (nT,3) of buoy indices, at the buoys'
