@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_cellmath.h"
 #include "sitrk_internal.h"
 #include "sitrk_reduce.h"
@@ -372,10 +373,8 @@ int coarse_run(sitrk_ctx *h, const char *fn, const CoarseJob &j, const CoarseGri
     }
     RCCHK(h->coarse_timer.mark(h, 1));
     if (j.nC > 0) {
-        unsigned end_bit = 1;                                          // the keys run 0 .. npix, npix <= 2^24
-        while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)npix) end_bit++;
-        size_t tb = b.sort_bytes;
-        HIPCHK(sort_pairs_u32(b.sort_tmp, &tb, b.k0, b.k1, b.v0, b.v1, (size_t)j.nC, end_bit, h->stream));
+        size_t tb = b.sort_bytes;                                      // the keys run 0 .. npix, npix <= 2^24
+        HIPCHK(sort_pairs_u32(b.sort_tmp, &tb, b.k0, b.k1, b.v0, b.v1, (size_t)j.nC, key_bits((uint64_t)npix), h->stream));
     }
     RCCHK(h->coarse_timer.mark(h, 2));
     if (j.nC > 0) {

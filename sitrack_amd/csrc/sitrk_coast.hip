@@ -9,7 +9,8 @@
 //   rocPRIM exclusive scan of the flags, coast_compact_kernel: ids and endpoints in id order
 //   coast_stats_kernel    bounding box of the segments' midpoints, the longest segment, the largest coordinate
 //   coast_key_kernel      square bins over that box, key = bin of the midpoint (row-major), the radix sort of sitrk_sort.hip
-//                         (stable: id order inside a bin), coast_gather_kernel, coast_start_kernel (first segment of every bin)
+//                         (stable: id order inside a bin), coast_gather_kernel, bin_start_kernel of sitrk_bins.h (first segment
+//                         of every bin)
 // Query (coast_query_kernel, one query per lane, no LDS, no cross-lane work).  With pad >= half the longest segment, a segment
 // at distance <= d from p has its midpoint within d + pad of p, and the bin of a coordinate is a monotone function of it, so all
 // such segments lie in bin rows bin(py - R) .. bin(py + R) and, in each row, in ONE run of the bin-sorted segments, bins
@@ -27,6 +28,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -40,13 +42,6 @@ constexpr int kCoastThreads = 256;
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 __device__ __forceinline__ double plus_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
 __device__ __forceinline__ bool finite64(double a) { return fabs(a) < plus_inf(); }
-
-// order-preserving map of a double to an unsigned 64-bit key (min/max by integer atomics); subsample_key_to_double inverts it
-__device__ __forceinline__ unsigned long long dkey(double d)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // F-points as two strided arrays: (Yf, Xf, 1) for the caller's arrays, (&geoF->y, &geoF->x, 2) for the context's grid
 struct FPoints {
@@ -114,31 +109,23 @@ __global__ __launch_bounds__(kCoastThreads) void coast_stats_kernel(int64_t nseg
     for (int64_t s = (int64_t)blockIdx.x * kCoastThreads + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * kCoastThreads) {
         const pt a = ab[2 * s], b = ab[2 * s + 1], m = midpoint(a, b);
         const double ey = b.y - a.y, ex = b.x - a.x;
-        const unsigned long long ky = dkey(m.y), kx = dkey(m.x);
+        const unsigned long long ky = order_key(m.y), kx = order_key(m.x);
         r[0] = min(r[0], ky); r[1] = min(r[1], kx); r[2] = max(r[2], ky); r[3] = max(r[3], kx);
-        r[4] = max(r[4], dkey(ey * ey + ex * ex));
-        r[5] = max(r[5], dkey(fmax(fmax(fabs(a.y), fabs(a.x)), fmax(fabs(b.y), fabs(b.x)))));
+        r[4] = max(r[4], order_key(ey * ey + ex * ex));
+        r[5] = max(r[5], order_key(fmax(fmax(fabs(a.y), fabs(a.x)), fmax(fabs(b.y), fabs(b.x)))));
     }
     __shared__ unsigned long long sm[6][kCoastThreads];
 #pragma unroll
     for (int q = 0; q < 6; q++) sm[q][threadIdx.x] = r[q];
     __syncthreads();
-    for (int s = kCoastThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int q = 0; q < 6; q++) {
-                const unsigned long long u = sm[q][threadIdx.x], v = sm[q][threadIdx.x + s];
-                sm[q][threadIdx.x] = q < 2 ? min(u, v) : max(u, v);
-            }
-        }
-        __syncthreads();
-    }
+    block_reduce<kCoastThreads, Red::Min, Red::Min, Red::Max, Red::Max, Red::Max, Red::Max>(sm);
     if (threadIdx.x < 6) {
         if (threadIdx.x < 2) atomicMin(&red[threadIdx.x], sm[threadIdx.x][0]);
         else atomicMax(&red[threadIdx.x], sm[threadIdx.x][0]);
     }
 }
 
+// Deliberately not cell_coord of sitrk_bins.h: truncation by (int)t, not floor, and NaN / -inf go to bin 0, +inf to the last.
 // THE bin of a coordinate: a monotone (non-decreasing) function of v, which is all the query relies on.  Coordinates outside the
 // bins' extent, +-inf included, go to the first / last bin.
 __device__ __forceinline__ int bin_of(double v, double v0, double inv_h, int n)
@@ -169,21 +156,6 @@ __global__ __launch_bounds__(kCoastThreads) void coast_gather_kernel(int64_t nse
     seg[2 * s] = ab[2 * o];
     seg[2 * s + 1] = ab[2 * o + 1];
     sid[s] = ids[o];
-}
-
-// start[b] = number of sorted keys below b, b = 0 .. nbins (start[nbins] = nseg)
-__global__ __launch_bounds__(kCoastThreads) void coast_start_kernel(int64_t nbins, int64_t nseg, const uint32_t *__restrict__ key,
-                                                                    int32_t *__restrict__ start)
-{
-    const int64_t b = (int64_t)blockIdx.x * kCoastThreads + threadIdx.x;
-    if (b > nbins) return;
-    int64_t lo = 0, hi = nseg;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)key[mid] < b) lo = mid + 1;
-        else hi = mid;
-    }
-    start[b] = (int32_t)lo;
 }
 
 // the contract's squared distance of p to segment (a, b): one rounded operation per symbol, no FMA
@@ -375,9 +347,9 @@ SITRK_API int sitrk_coast_build(sitrk_t *h, int Nj, int Ni, const double *Yf, co
     HIPCHK(hipStreamSynchronize(st));                           // the scratch of this stage is free from here on
 
     // ---- the bins
-    const double lo[2] = {subsample_key_to_double(r[0]), subsample_key_to_double(r[1])};
-    const double hi[2] = {subsample_key_to_double(r[2]), subsample_key_to_double(r[3])};
-    const double longest = std::sqrt(subsample_key_to_double(r[4])), cmax = subsample_key_to_double(r[5]);
+    const double lo[2] = {order_value(r[0]), order_value(r[1])};
+    const double hi[2] = {order_value(r[2]), order_value(r[3])};
+    const double longest = std::sqrt(order_value(r[4])), cmax = order_value(r[5]);
     // side: coast_bin quarters of the spacing n segments would have if they filled the midpoints' bounding box evenly -- about
     // one segment per bin at the default, whatever the mesh; a coast on a line, or a single segment, gets the longest segment
     double side = 0.25 * h->coast_bin * std::sqrt((hi[0] - lo[0]) * (hi[1] - lo[1]) / (double)n);
@@ -393,8 +365,7 @@ SITRK_API int sitrk_coast_build(sitrk_t *h, int Nj, int Ni, const double *Yf, co
     // half the longest segment (rounded up), and what the bins' own arithmetic can be off by
     ix.pad = 0.5 * longest * (1.0 + 0x1p-20) + (ix.h + cmax) * 0x1p-30;
     const int64_t nbins = nb[0] * nb[1];
-    unsigned end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)nbins) end_bit++;
+    const unsigned end_bit = key_bits((uint64_t)nbins - 1);
     size_t b_sort = 0;
     HIPCHK(sort_pairs_u32(nullptr, &b_sort, nullptr, nullptr, nullptr, nullptr, (size_t)n, 32, st));
     uint32_t *k0, *k1; int32_t *v0, *v1; char *sort_tmp;
@@ -409,7 +380,8 @@ SITRK_API int sitrk_coast_build(sitrk_t *h, int Nj, int Ni, const double *Yf, co
     tb = align256(b_sort);
     HIPCHK(sort_pairs_u32(sort_tmp, &tb, k0, k1, v0, v1, (size_t)n, end_bit, st));
     hipLaunchKernelGGL(coast_gather_kernel, dim3(nblk(n)), dim3(kCoastThreads), 0, st, n, v1, cs.ids, cs.ab, cs.seg, cs.sid);
-    hipLaunchKernelGGL(coast_start_kernel, dim3(nblk(nbins + 1)), dim3(kCoastThreads), 0, st, nbins, n, k1, cs.start);
+    hipLaunchKernelGGL(bin_start_kernel<kCoastThreads>, dim3(nblk(nbins + 1)), dim3(kCoastThreads), 0, st, nbins, (int32_t)n,
+                       lower_bound_steps(n), k1, cs.start);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     ix.seg = cs.seg; ix.sid = cs.sid; ix.start = cs.start;

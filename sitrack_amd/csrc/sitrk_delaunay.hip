@@ -25,6 +25,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -87,17 +88,7 @@ __global__ __launch_bounds__(kDlThreads) void dl_quant_kernel(int64_t n, const p
     sm[2][threadIdx.x] = hi[0]; sm[3][threadIdx.x] = hi[1];
     sm[4][threadIdx.x] = bad;   sm[5][threadIdx.x] = cnt;
     __syncthreads();
-    for (int s = kDlThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            for (int c = 0; c < 2; c++) {
-                sm[c][threadIdx.x] = min(sm[c][threadIdx.x], sm[c][threadIdx.x + s]);
-                sm[2 + c][threadIdx.x] = max(sm[2 + c][threadIdx.x], sm[2 + c][threadIdx.x + s]);
-            }
-            sm[4][threadIdx.x] = min(sm[4][threadIdx.x], sm[4][threadIdx.x + s]);
-            sm[5][threadIdx.x] += sm[5][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    block_reduce<kDlThreads, Red::Min, Red::Min, Red::Max, Red::Max, Red::Min, Red::Add>(sm);
     if (threadIdx.x == 0) {
         if (sm[5][0]) {
             for (int c = 0; c < 2; c++) { atomicMin(&red[c], sm[c][0]); atomicMax(&red[2 + c], sm[2 + c][0]); }
@@ -115,6 +106,7 @@ __global__ __launch_bounds__(kDlThreads) void dl_key_kernel(DlGrid g, int64_t n,
     const ipt a = xy[i];
     uint32_t k = g.ncells;
     if (a.y != kDlGone) {
+        // deliberately not cell_coord of sitrk_bins.h: the coordinates are integers and the cell is their quotient by the side
         int64_t cy = (a.y - g.y0) / g.side, cx = (a.x - g.x0) / g.side;       // both differences are >= 0
         cy = cy < 0 ? 0 : (cy >= g.ny ? g.ny - 1 : cy);
         cx = cx < 0 ? 0 : (cx >= g.nx ? g.nx - 1 : cx);
@@ -436,8 +428,7 @@ int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, co
         }
         g.ny = (int)ny; g.nx = (int)nx;
         g.ncells = (uint32_t)(ny * nx);
-        unsigned end_bit = 1;                            // keys 0..ncells (ncells: no vertex)
-        while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)g.ncells) end_bit++;
+        const unsigned end_bit = key_bits(g.ncells);     // keys 0..ncells (ncells: no vertex)
         hipLaunchKernelGGL(dl_key_kernel, dim3(nblk(nP)), dim3(kDlThreads), 0, st, g, nP, b.xy, b.k0, b.v0);
         HIPCHK(hipGetLastError());
         size_t tb = b.sort_bytes;
@@ -456,8 +447,7 @@ int sitrk::dl_core(sitrk_ctx *h, const char *fn, int64_t nP, const pt *d_pts, co
         if (cnt[0] > (unsigned long long)cap_rows)
             return fail(h, SITRK_EHIP, "%s: %llu triangles on %lld vertices", fn, cnt[0], (long long)nv);
         if (cnt[0]) {
-            unsigned pbits = 1;
-            while (pbits < 32 && ((uint64_t)1 << pbits) < (uint64_t)nP) pbits++;
+            const unsigned pbits = key_bits((uint64_t)nP - 1);    // p and q are indices below nP
             tb = b.sort_bytes;
             HIPCHK(sort_rows_u64(b.sort_tmp, &tb, b.rkey0, b.rkey1, b.rval0, b.rval1, (size_t)cnt[0], 32 + pbits, st));
             hipLaunchKernelGGL(dl_rows_kernel, dim3(nblk((int64_t)cnt[0])), dim3(kDlThreads), 0, st, (int64_t)cnt[0], b.rkey1, b.rval1, b.tris);

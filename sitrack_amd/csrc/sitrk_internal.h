@@ -48,7 +48,6 @@ struct SubResolveArgs {
     uint8_t *done = nullptr;            // per workgroup: all its points decided
     unsigned long long *undecided = nullptr;   // optional: += points still undecided at each workgroup's exit
 };
-double subsample_key_to_double(unsigned long long k);
 // cells of side `side` over the extents hi[c] - lo[c], c < dims: the side is doubled while the grid exceeds max_cells cells or 2^20
 // cells a side (a coarser grid is only slower).  false: no grid fits; else *inv_h = 1 / side and ncell[c] cells along c
 bool fit_cell_grid(int dims, const double *lo, const double *hi, double side, int64_t max_cells, double *inv_h, int64_t *ncell);

@@ -19,6 +19,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -28,12 +29,6 @@ namespace sitrk {
 namespace {
 
 constexpr int kOvThreads = 256;
-
-__device__ __forceinline__ unsigned long long dkey(double d)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ V3 unit_vec(double lat, double lon)
 {
@@ -66,13 +61,6 @@ __device__ __forceinline__ double haversine(double plat, double plon, double cos
     return 2. * R * asin(sqrt(a1 * a1 + a3 * a2 * a2));
 }
 
-__device__ __forceinline__ int cell_coord(double v, double v0, double inv_h, int nc)
-{
-    const double t = (v - v0) * inv_h;               // same expression as the host's cell count: t <= nc - 1 by monotonicity
-    int c = (int)floor(t);
-    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
-}
-
 __device__ __forceinline__ bool is_valid(const int8_t *valid, int64_t i) { return valid == nullptr || valid[i] != 0; }
 
 __global__ void bbox_init_kernel(unsigned long long *red)
@@ -95,7 +83,7 @@ __global__ __launch_bounds__(kOvThreads) void unit_bbox_kernel(int64_t n, const 
         }
         cnt++;
         const V3 v = unit_vec(la, lo_);
-        const unsigned long long k[3] = {dkey(v.x), dkey(v.y), dkey(v.z)};
+        const unsigned long long k[3] = {order_key(v.x), order_key(v.y), order_key(v.z)};
         for (int c = 0; c < 3; c++) { lo[c] = min(lo[c], k[c]); hi[c] = max(hi[c], k[c]); }
     }
     __shared__ unsigned long long sm[8][kOvThreads];
@@ -103,17 +91,7 @@ __global__ __launch_bounds__(kOvThreads) void unit_bbox_kernel(int64_t n, const 
     sm[6][threadIdx.x] = bad;
     sm[7][threadIdx.x] = cnt;
     __syncthreads();
-    for (int s = kOvThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            for (int c = 0; c < 3; c++) {
-                sm[c][threadIdx.x] = min(sm[c][threadIdx.x], sm[c][threadIdx.x + s]);
-                sm[3 + c][threadIdx.x] = max(sm[3 + c][threadIdx.x], sm[3 + c][threadIdx.x + s]);
-            }
-            sm[6][threadIdx.x] = min(sm[6][threadIdx.x], sm[6][threadIdx.x + s]);
-            sm[7][threadIdx.x] += sm[7][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    block_reduce<kOvThreads, Red::Min, Red::Min, Red::Min, Red::Max, Red::Max, Red::Max, Red::Min, Red::Add>(sm);
     if (threadIdx.x == 0) {
         for (int c = 0; c < 3; c++) { atomicMin(&red[c], sm[c][0]); atomicMax(&red[3 + c], sm[3 + c][0]); }
         atomicMin(&red[6], sm[6][0]);
@@ -139,7 +117,6 @@ __global__ __launch_bounds__(kOvThreads) void bin_key_kernel(OvGrid g, int64_t n
     val[i] = (int32_t)i;
 }
 
-// cstart/cend zeroed by the caller: empty cells keep [0,0)
 __global__ __launch_bounds__(kOvThreads) void bin_gather_kernel(OvGrid g, int64_t n, const double *__restrict__ lat,
                                                                const double *__restrict__ lon, const uint32_t *__restrict__ key,
                                                                const int32_t *__restrict__ perm, V3 *uv_s, ll *ll_s, int32_t *cstart,
@@ -154,8 +131,7 @@ __global__ __launch_bounds__(kOvThreads) void bin_gather_kernel(OvGrid g, int64_
     uv_s[s] = unit_vec(la, lo);
     ll p; p.lat = la; p.lon = lo;
     ll_s[s] = p;
-    if (s == 0 || key[s - 1] != k) cstart[k] = (int32_t)s;
-    if (s == n - 1 || key[s + 1] != k) cend[k] = (int32_t)(s + 1);
+    mark_cell_run(key, s, n, cstart, cend);
 }
 
 // Results in input order: nn = input index of the nearest other valid buoy when its distance is < rd, else -1 (dmin +inf).
@@ -289,7 +265,7 @@ static int overlap_stage1(sitrk_ctx *h, const char *fn, int64_t n, const double 
     OvGrid g;
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     if (bb[7]) {
-        for (int c = 0; c < 3; c++) { lo[c] = subsample_key_to_double(bb[c]); hi[c] = subsample_key_to_double(bb[3 + c]); }
+        for (int c = 0; c < 3; c++) { lo[c] = order_value(bb[c]); hi[c] = order_value(bb[3 + c]); }
     }
     g.x0 = lo[0]; g.y0 = lo[1]; g.z0 = lo[2];
     // chord of rd (rd <= 9999 km: half-angle <= 0.79 rad, sin increasing); side h >= that chord, padded so that neither the
@@ -302,8 +278,7 @@ static int overlap_stage1(sitrk_ctx *h, const char *fn, int64_t n, const double 
     g.nx = (int)ncell[0]; g.ny = (int)ncell[1]; g.nz = (int)ncell[2];
     const int64_t ncells = ncell[0] * ncell[1] * ncell[2];
     g.ncells = (uint32_t)ncells;
-    unsigned end_bit = 1;                               // keys 0..ncells (ncells: invalid buoys)
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)ncells) end_bit++;
+    const unsigned end_bit = key_bits((uint64_t)ncells);    // keys 0..ncells (ncells: invalid buoys)
 
     hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kOvThreads), 0, st, g, n, d_lat, d_lon, dv, k0, v0);
     HIPCHK(hipGetLastError());

@@ -11,7 +11,8 @@
 //                        for a point that is not valid; value = its index
 //   (sort_pairs_u32)     the stable radix sort of sitrk_sort.hip: the valid points in (bin, index) order
 //   pairs_gather_kernel  one sorted position per lane: the point's t0 and t1 positions as one 32-byte record
-//   pairs_start_kernel   one bin per lane: the first sorted position of the bin, a binary search of a length fixed by the host
+//   bin_start_kernel     (sitrk_bins.h) one bin per lane: the first sorted position of the bin, a binary search of a length fixed by
+//                        the host
 //   pairs_rows_kernel    one workgroup: a row of bins with n points is cut into ceil(n / kPairsTile) HOME CHUNKS of consecutive
 //                        sorted positions; the exclusive scan of those numbers over the rows
 //   pairs_kernel         one workgroup of one wave per (home chunk, class): lane i keeps home point i in registers; the rows of
@@ -29,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_internal.h"
 #include "sitrk_reduce.h"
 
@@ -59,20 +61,6 @@ struct PairsEdges {
     double e[SITRK_PAIRS_MAXCLASS + 1];
     double e2[SITRK_PAIRS_MAXCLASS + 1];            // e[c]*e[c], one rounded product
 };
-
-__device__ __forceinline__ unsigned long long order_key(double v)       // a < b  <=>  key(a) < key(b), finite a, b
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-inline double order_value(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    memcpy(&v, &b, sizeof v);
-    return v;
-}
 
 __device__ __forceinline__ bool pairs_valid(int64_t k, const pt *__restrict__ p0, const pt *__restrict__ p1, const int8_t *__restrict__ m0,
                                             const int8_t *__restrict__ m1, pt &a, pt &b)
@@ -118,6 +106,7 @@ __global__ __launch_bounds__(kPairsThreads) void pairs_key_kernel(int64_t n, con
     const bool ok = pairs_valid(k, p0, p1, m0, m1, a, b);
     uint32_t key = (uint32_t)g.ny * (uint32_t)g.nx;
     if (ok) {
+        // deliberately not cell_coord of sitrk_bins.h: (int) truncates, and the clamp compares in floating point before it converts
         int by = 0, bx = 0;
         if (g.inv_h > 0.0) {
             const double fy = (a.y - g.ymin) * g.inv_h, fx = (a.x - g.xmin) * g.inv_h;      // >= 0 and below the grid's side + 1
@@ -140,22 +129,6 @@ __global__ __launch_bounds__(kPairsThreads) void pairs_gather_kernel(int64_t nva
     P4 r;
     r.y0 = a.y; r.x0 = a.x; r.y1 = b.y; r.x1 = b.x;
     pts[s] = r;
-}
-
-// start[b], b = 0 .. nbins: the first of the nvalid sorted positions whose key is >= b
-__global__ __launch_bounds__(kPairsThreads) void pairs_start_kernel(int64_t nbins, int32_t nvalid, int steps, const uint32_t *__restrict__ keys,
-                                                                    int32_t *__restrict__ start)
-{
-    const int64_t b = (int64_t)blockIdx.x * kPairsThreads + threadIdx.x;
-    if (b > nbins) return;
-    int32_t lo = 0, hi = nvalid;                                       // keys[lo - 1] < b <= keys[hi]
-    for (int it = 0; it < steps; it++) {
-        if (lo < hi) {
-            const int32_t mid = lo + ((hi - lo) >> 1);
-            if (keys[mid] < (uint32_t)b) lo = mid + 1; else hi = mid;
-        }
-    }
-    start[b] = lo;
 }
 
 // chunk_off[r], r = 0 .. ny: the home chunks of the rows in front of row r
@@ -394,16 +367,12 @@ int pairs_run(sitrk_ctx *h, int64_t nP, const pt *p0, const pt *p1, const int8_t
         cap = max_chunks(nvalid, g.ny);
         hipLaunchKernelGGL(pairs_key_kernel, dim3(nblk(nP)), dim3(kPairsThreads), 0, h->stream, nP, p0, p1, m0, m1, g, b.k0, b.v0);
         HIPCHK(hipGetLastError());
-        unsigned end_bit = 1;                                          // the keys run 0 .. nbins, nbins <= 2^22
-        while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)nbins) end_bit++;
-        size_t tb = b.sort_bytes;
-        HIPCHK(sort_pairs_u32(b.sort_tmp, &tb, b.k0, b.k1, b.v0, b.v1, (size_t)nP, end_bit, h->stream));
+        size_t tb = b.sort_bytes;                                      // the keys run 0 .. nbins, nbins <= 2^22
+        HIPCHK(sort_pairs_u32(b.sort_tmp, &tb, b.k0, b.k1, b.v0, b.v1, (size_t)nP, key_bits((uint64_t)nbins), h->stream));
         hipLaunchKernelGGL(pairs_gather_kernel, dim3(nblk(nvalid)), dim3(kPairsThreads), 0, h->stream, nvalid, b.v1, p0, p1, b.pts);
         HIPCHK(hipGetLastError());
-        int steps = 1;
-        while (((int64_t)1 << steps) <= nvalid) steps++;
-        hipLaunchKernelGGL(pairs_start_kernel, dim3(nblk(nbins + 1)), dim3(kPairsThreads), 0, h->stream, nbins, (int32_t)nvalid, steps, b.k1,
-                           b.start);
+        hipLaunchKernelGGL(bin_start_kernel<kPairsThreads>, dim3(nblk(nbins + 1)), dim3(kPairsThreads), 0, h->stream, nbins, (int32_t)nvalid,
+                           lower_bound_steps(nvalid), b.k1, b.start);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pairs_rows_kernel, dim3(1), dim3(kPairsThreads), 0, h->stream, g.ny, g.nx, b.start, b.chunk_off);
         HIPCHK(hipGetLastError());

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sitrk_bins.h"
 #include "sitrk_internal.h"
 
 #pragma clang fp contract(off)
@@ -37,13 +38,6 @@ namespace {
 constexpr int kSubThreads = 256;      // threads per workgroup of every kernel here
 constexpr int kMaxSweeps = 256;       // bound of the in-launch re-sweeps of one workgroup
 constexpr uint8_t kUndecided = 0, kKept = 1, kDropped = 2;
-
-// order-preserving map of a double to an unsigned 64-bit key (min/max by integer atomics)
-__device__ __forceinline__ unsigned long long dkey(double d)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ uint8_t state_load(const uint8_t *p)
 {
@@ -63,13 +57,6 @@ __device__ __forceinline__ double d2of(pt a, pt b)
     return yy + xx;
 }
 
-__device__ __forceinline__ int cell_coord(double v, double v0, double inv_h, int nc)
-{
-    const double t = (v - v0) * inv_h;               // same expression as the host's cell count: t <= nc - 1 by monotonicity
-    int c = (int)floor(t);
-    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
-}
-
 __global__ void bbox_init_kernel(unsigned long long *red)
 {
     if (threadIdx.x < 5) red[threadIdx.x] = threadIdx.x < 2 || threadIdx.x == 4 ? ~0ull : 0ull;
@@ -85,7 +72,7 @@ __global__ __launch_bounds__(kSubThreads) void bbox_kernel(int64_t n, const pt *
             bad = min(bad, (unsigned long long)i);
             continue;
         }
-        const unsigned long long ky = dkey(p.y), kx = dkey(p.x);
+        const unsigned long long ky = order_key(p.y), kx = order_key(p.x);
         lo_y = min(lo_y, ky); hi_y = max(hi_y, ky);
         lo_x = min(lo_x, kx); hi_x = max(hi_x, kx);
     }
@@ -93,16 +80,7 @@ __global__ __launch_bounds__(kSubThreads) void bbox_kernel(int64_t n, const pt *
     sm[0][threadIdx.x] = lo_y; sm[1][threadIdx.x] = lo_x; sm[2][threadIdx.x] = hi_y; sm[3][threadIdx.x] = hi_x;
     sm[4][threadIdx.x] = bad;
     __syncthreads();
-    for (int s = kSubThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sm[0][threadIdx.x] = min(sm[0][threadIdx.x], sm[0][threadIdx.x + s]);
-            sm[1][threadIdx.x] = min(sm[1][threadIdx.x], sm[1][threadIdx.x + s]);
-            sm[2][threadIdx.x] = max(sm[2][threadIdx.x], sm[2][threadIdx.x + s]);
-            sm[3][threadIdx.x] = max(sm[3][threadIdx.x], sm[3][threadIdx.x + s]);
-            sm[4][threadIdx.x] = min(sm[4][threadIdx.x], sm[4][threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
+    block_reduce<kSubThreads, Red::Min, Red::Min, Red::Max, Red::Max, Red::Min>(sm);
     if (threadIdx.x == 0) {
         atomicMin(&red[0], sm[0][0]); atomicMin(&red[1], sm[1][0]);
         atomicMax(&red[2], sm[2][0]); atomicMax(&red[3], sm[3][0]);
@@ -121,7 +99,6 @@ __global__ __launch_bounds__(kSubThreads) void bin_key_kernel(SubGrid g, int64_t
     val[i] = (int32_t)i;
 }
 
-// cstart/cend zeroed by the caller: empty cells keep [0,0)
 __global__ __launch_bounds__(kSubThreads) void bin_gather_kernel(int64_t n, const pt *__restrict__ yx, const uint32_t *__restrict__ key,
                                                                 const int32_t *__restrict__ perm, pt *yx_s, int32_t *cstart,
                                                                 int32_t *cend)
@@ -129,9 +106,7 @@ __global__ __launch_bounds__(kSubThreads) void bin_gather_kernel(int64_t n, cons
     const int64_t s = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
     if (s >= n) return;
     yx_s[s] = yx[perm[s]];
-    const uint32_t k = key[s];
-    if (s == 0 || key[s - 1] != k) cstart[k] = (int32_t)s;
-    if (s == n - 1 || key[s + 1] != k) cend[k] = (int32_t)(s + 1);
+    mark_cell_run(key, s, n, cstart, cend);
 }
 
 // Pull: walk the earlier neighbours of sorted point p from its cursor (cell slot 0..8 of the 3x3 neighbourhood, sorted
@@ -242,14 +217,6 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kSubThreads - 1) / kSub
 
 }  // namespace
 
-double subsample_key_to_double(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double d;
-    memcpy(&d, &b, sizeof(d));
-    return d;
-}
-
 bool fit_cell_grid(int dims, const double *lo, const double *hi, double side, int64_t max_cells, double *inv_h, int64_t *ncell)
 {
     for (int it = 0; it < 2100; it++, side *= 2.0) {
@@ -313,8 +280,8 @@ SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, dou
     HIPCHK(hipStreamSynchronize(st));
     if (bb[4] != ~0ull)
         return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: non-finite coordinate at index %llu", bb[4]);
-    const double lo[2] = {subsample_key_to_double(bb[0]), subsample_key_to_double(bb[1])};
-    const double hi[2] = {subsample_key_to_double(bb[2]), subsample_key_to_double(bb[3])};
+    const double lo[2] = {order_value(bb[0]), order_value(bb[1])};
+    const double hi[2] = {order_value(bb[2]), order_value(bb[3])};
     // side h >= rd, padded so that the rounding of a cell coordinate ((v - v0) * inv_h, <= 2^20) can never put a pair with
     // d2 < r2 two cells apart
     SubGrid g;
@@ -324,8 +291,7 @@ SITRK_API int sitrk_subsample_cloud(sitrk_t *h, int64_t n, const double *yx, dou
         return fail(h, SITRK_EINVAL, "sitrk_subsample_cloud: no cell grid fits the cloud's extent");
     g.ny = (int)ncell[0]; g.nx = (int)ncell[1];
     const int64_t ncells = ncell[0] * ncell[1];
-    unsigned end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)ncells) end_bit++;
+    const unsigned end_bit = key_bits((uint64_t)ncells - 1);
 
     // bin: key = cell, stable radix sort (index order inside a cell), sorted coordinates, cell ranges
     hipLaunchKernelGGL(bin_key_kernel, dim3(nblk(n)), dim3(kSubThreads), 0, st, g, n, d_yx, k0, v0);
