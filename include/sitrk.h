@@ -123,6 +123,7 @@ int sitrk_set_substeps(sitrk_t *h, int nsub);
  * sitrk_subsample_cloud's resolve kernel; "coast_bin" (1..64, default 4): bin side of the next sitrk_coast_build, in quarters of
  * sqrt(bounding-box area / segments); "delaunay_bin" (1..4, default 3): cells per reach of the next sitrk_delaunay;
  * "skeleton_batch" (1..8, default 8): sub-iterations per launch of the thinning kernel of the next skeleton call;
+ * "dist_aggregate" (0/1, default 0): per-wave aggregation in the digit passes of the next distribution call;
  * "lanes" (1/2, default 2) / "lane_min_wg" (>= 1, default 7168): with lanes = 2, sitrk_run splits the cell-sorted buoys into two
  * contiguous lanes (cut at a multiple of 256 * 8 * xcd_group buoys) and queues each lane's fused launches on a stream of its own
  * -- lane 0 on the compute stream, lane 1 on the ingest stream, its first launch half as long, so that the lanes' launch
@@ -854,6 +855,61 @@ int sitrk_pairs_since_mark(sitrk_t *h, int jrec1, int nc, const double *edges_km
 int sitrk_pairs_free(sitrk_t *h);
 int sitrk_pairs_kernel_ms(sitrk_t *h, float *bin_ms, float *pairs_ms, float *table_ms);
 int sitrk_pairs_stats(sitrk_t *h, int64_t *tests);
+
+/* ---- distribution of values: counts between edges, exact order statistics ----------------------
+ * An EXTRA the reference does not have: the probability distribution of the deformation rates -- how many cells fall between
+ * explicit edges, the PDF with its power-law tail -- and their order statistics -- the percentile a feature threshold is stated
+ * as -- taken on the device, for a host array or for the cells of a device-resident mesh whose per-cell rates never move to the
+ * host.  No parity claim is made against any other code; the contract below is this library's own.  It has only
+ * comparisons in fp64, counts, and a selection on the bits of the values, so nothing is unpinned.
+ * THE SAMPLE.  sitrk_dist_values: x (n) fp64, use (n) int8 or NULL; the sample is x[i] for every i with use == NULL or
+ * use[i] != 0.  sitrk_mesh_dist: the cells of status 1 of sitrk_mesh_deform(mesh, jrec1) -- the population its ten stats are
+ * summed over --, and their value is f = div, shr or vor for what = 0, 1, 2, taken as f, -f or |f| for sgn = +1, -1, 0.  what = 3
+ * is the total deformation squared,  t2 = div*div + shr*shr  (one rounded operation per symbol, no fused multiply-add): the
+ * square, as in sitrk_mesh_features, so that no second square root enters; it needs sgn == +1.  A NaN is not part of the sample
+ * and is counted in *nnan; *m is the sample's size (either may be NULL).  -0.0 is taken as +0.0 (v + 0.0).  Infinities are
+ * ordinary values.
+ * THE HISTOGRAM.  nb in 0 .. SITRK_DIST_MAXBINS; edges (nb+1) finite and strictly ascending.  counts (nb+2) int64: counts[c] =
+ * the number of sample values v with exactly c of the edges <= v, compared in fp64.  So counts[0] lies below edges[0], counts[c]
+ * for 1 <= c <= nb in [edges[c-1], edges[c]) and counts[nb+1] at or above edges[nb]; the counts add up to m.  nb == 0 skips the
+ * histogram; edges and counts may then be NULL.
+ * ORDER STATISTICS.  nq in 0 .. SITRK_DIST_MAXQ, every q[t] in [0,1].  The rank of target t is
+ *     k_t = min(m - 1, (int64)floor(q[t] * (double)m))            (one rounded product)
+ * formed ON THE DEVICE from the counted m, so that no round trip is needed to learn m first.  qval[t] = the value at position k_t
+ * of the sample in ascending order, BIT FOR BIT ONE OF THE SAMPLE'S VALUES (after -0.0 -> +0.0); qrank[t] = k_t.  With m == 0
+ * qval[t] is NaN and qrank[t] is -1.  The order is that of the usual monotone 64-bit key of an fp64: with b its bits,
+ *     key = b ^ (b >> 63 ? ~0 : 1 << 63)
+ * which for the values of a sample is the order of <.  nq == 0 skips the selection; q, qval and qrank may then be NULL.
+ * BYTES.  Only the nb+2 counts, the nq pairs and the two integers come down; sitrk_dist_values sends x and use up, sitrk_mesh_dist
+ * sends the edges and q: nothing per cell crosses to the host in either direction.
+ * sitrk_dist_values is synchronous on the handle's stream and uses the context's transient scratch only: the grid, buoys,
+ * records, meshes, marks and kept maps of a tracker on the same handle are left as they were.  n == 0 is valid: zeros, m = 0.
+ * sitrk_mesh_dist is valid wherever sitrk_mesh_deform is, runs the same pass over the buoys and the same cell kernel, and leaves
+ * the mesh, buoys, records and kept maps as they were.  An empty mesh (nQ == 0) returns zeros, m = 0.
+ * Two calls return the same bits, and the result does not depend on the launch geometry or on the knob "dist_aggregate" (0/1,
+ * default 0; 1: in the selection a wave whose matching keys share their digit adds their number once).  Measured no faster.
+ * SITRK_EINVAL, before any device work: nb or nq out of range, edges that are not finite or not strictly ascending, a q outside
+ * [0,1] (a NaN included), missing pointers, n < 0, what or sgn out of range, what == 3 with sgn != +1, and for sitrk_mesh_dist
+ * what sitrk_mesh_deform refuses: an empty slot, jrec1 < jrec0, no buoys.
+ * sitrk_dist_kernel_ms: GPU time [ms] of the phases of the last of the two calls on this handle, from HIP events -- the keys (key
+ * kernel, the sum of m and the ranks; for the mesh form the deformation itself is under sitrk_mesh_kernel_ms), the histogram
+ * (counts, sum of the rows), the selection (eight digit passes, each a count and a pick); any pointer may be NULL, SITRK_EINVAL
+ * before any such call.
+ * sitrk_dist_stats, measurement only: *passes = the digit passes that call's selection ran (8, or 0 with nq == 0), *top_pass_ms =
+ * the GPU time of the first of them, the top digit, where the keys of one sign and exponent crowd one counter; either may be
+ * NULL. */
+#define SITRK_DIST_MAXBINS 1024
+#define SITRK_DIST_MAXQ    16
+int sitrk_dist_values(sitrk_t *h, int64_t n, const double *x, const int8_t *use,
+                      int nb, const double *edges, int64_t *counts,
+                      int nq, const double *q, double *qval, int64_t *qrank,
+                      int64_t *m, int64_t *nnan);
+int sitrk_mesh_dist(sitrk_t *h, int mesh, int jrec1, int what, int sgn,
+                    int nb, const double *edges, int64_t *counts,
+                    int nq, const double *q, double *qval, int64_t *qrank,
+                    int64_t *m, int64_t *nnan);
+int sitrk_dist_kernel_ms(sitrk_t *h, float *keys_ms, float *hist_ms, float *select_ms);
+int sitrk_dist_stats(sitrk_t *h, int *passes, float *top_pass_ms);
 
 /* ---- distance to the model coastline ------------------------------------------
  * An EXTRA the reference does not have: its coastal cleaning of a seed cloud (`ldo_coastal_clean`, mojito's MaskCoastal,

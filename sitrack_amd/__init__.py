@@ -19,6 +19,8 @@ from .delaunay import DelaunayTris                                           # n
 from .raster import RasterCells, raster_grid                                  # noqa: F401
 from .coarse import CoarseCells, scaling_exponents                            # noqa: F401
 from .dispersion import PairDispersion, dispersion_curve, dispersion_exponents, pair_edges, pairs_arg   # noqa: F401
+from .distribution import (ValueDistribution, log_edges, lin_edges, pdf_from_counts, tail_exponent,   # noqa: F401
+                           percentile_threshold, pdf_arg)
 from .features import SkeletonRaster, node_yx, skeleton_table                                                            # noqa: F401
 from .features import LabelRaster, MatchLabels, feature_table, feature_tracks, link_features                              # noqa: F401
 from ._lib import FEAT_COLS, FEAT_WHAT                                        # noqa: F401

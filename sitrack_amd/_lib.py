@@ -40,6 +40,9 @@ SKEL_MAXSUB = 1 << 20                        # max_sub of the skeleton calls
 PAIRS_MAXCLASS = 16                          # SITRK_PAIRS_MAXCLASS
 PAIRS_NCOLS = 7                              # SITRK_PAIRS_NCOLS, in this order:
 PAIRS_COLS = ("n", "sum_r0", "sum_e", "sum_abs_e", "sum_e2", "sum_abs_e3", "sum_d2")
+DIST_MAXBINS = 1024                          # SITRK_DIST_MAXBINS
+DIST_MAXQ = 16                               # SITRK_DIST_MAXQ
+DIST_WHAT = {"div": 0, "shr": 1, "vor": 2, "tot": 3}       # `what` of sitrk_mesh_dist
 MESH_STATS = ("n0", "n1", "n2", "area0", "area1", "area0_div", "area0_shr", "area0_tot", "area0_tot2", "area0_tot3")
 
 _vp = C.c_void_p
@@ -141,6 +144,10 @@ _SIGNATURES = {
     "sitrk_pairs_free": (_int, [_vp]),
     "sitrk_pairs_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
     "sitrk_pairs_stats": (_int, [_vp, C.POINTER(_i64)]),
+    "sitrk_dist_values": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_mesh_dist": (_int, [_vp, _int, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sitrk_dist_kernel_ms": (_int, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "sitrk_dist_stats": (_int, [_vp, C.POINTER(_int), C.POINTER(C.c_float)]),
     "sitrk_coast_build": (_int, [_vp, _int, _int, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sitrk_coast_segments": (_int, [_vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sitrk_coast_dist": (_int, [_vp, _i64, _vp, _dbl, _vp, _vp]),
@@ -1102,6 +1109,70 @@ class Context:
         v = [C.c_float(0) for _ in range(3)]
         self._chk(self._L.sitrk_skeleton_kernel_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # -- distribution of values (sitrk_dist_*)
+    @staticmethod
+    def _dist_args(edges, q):
+        e = None if edges is None else as_c(edges, np.float64)
+        qq = None if q is None else as_c(q, np.float64)
+        if e is not None and (e.ndim != 1 or e.shape[0] < 2):
+            raise ValueError("edges must be the (nb + 1,) edges of nb >= 1 bins or None, got shape %s" % (e.shape,))
+        if qq is not None and qq.ndim != 1:
+            raise ValueError("q must be a (nq,) array or None, got shape %s" % (qq.shape,))
+        nb = 0 if e is None else e.shape[0] - 1
+        nq = 0 if qq is None else qq.shape[0]
+        counts = np.zeros(nb + 2 if nb else 0, dtype=np.int64)
+        qval, qrank = np.full(nq, np.nan, dtype=np.float64), np.full(nq, -1, dtype=np.int64)
+        return e, qq, nb, nq, counts, qval, qrank
+
+    @staticmethod
+    def _dist_result(e, qq, nb, nq, counts, qval, qrank, m, nnan):
+        return {"counts": counts if nb else None, "edges": e, "q": qq if nq else None, "values": qval, "ranks": qrank,
+                "m": m.value, "nnan": nnan.value}
+
+    def dist_values(self, x, edges=None, q=None, use=None):
+        """sitrk_dist_values: the distribution of the values x (n,) fp64 whose `use` (n,) is not 0 (None: all), NaNs aside.  A
+        dict with counts (nb + 2,) int64 -- counts[c] = the values with exactly c of the edges (nb + 1,) <= v; None without
+        edges --, edges, q, values (nq,) -- the value at rank min(m - 1, floor(q*m)) of the ascending sample, one of its values
+        bit for bit --, ranks (nq,) int64, m the sample's size and nnan the NaNs left out."""
+        x = as_c(x, np.float64)
+        if x.ndim != 1:
+            raise ValueError("x must be a (n,) array, got shape %s" % (x.shape,))
+        n = x.shape[0]
+        u = None if use is None else as_c(np.asarray(use) != 0, np.int8, (n,), "use")
+        a = self._dist_args(edges, q)
+        e, qq, nb, nq, counts, qval, qrank = a
+        m, nnan = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_dist_values(self._h, n, _ptr(x) if n else None, _ptr(u) if n else None, nb, _ptr(e),
+                                            _ptr(counts) if nb else None, nq, _ptr(qq) if nq else None, _ptr(qval) if nq else None,
+                                            _ptr(qrank) if nq else None, C.byref(m), C.byref(nnan)))
+        return self._dist_result(*a, m, nnan)
+
+    def mesh_dist(self, mesh, jrec1, what, sgn=1, edges=None, q=None):
+        """sitrk_mesh_dist, right after the step of jrec1: like dist_values() on the status-1 cells of the mesh in slot `mesh`;
+        what = 0 div, 1 shr, 2 vor (or those names) taken as f, -f, |f| for sgn = +1, -1, 0, or 3 / "tot" = div*div + shr*shr.
+        No per-cell value leaves the device."""
+        what = DIST_WHAT.get(what, what)
+        a = self._dist_args(edges, q)
+        e, qq, nb, nq, counts, qval, qrank = a
+        m, nnan = _i64(0), _i64(0)
+        self._chk(self._L.sitrk_mesh_dist(self._h, int(mesh), int(jrec1), int(what), int(sgn), nb, _ptr(e),
+                                          _ptr(counts) if nb else None, nq, _ptr(qq) if nq else None, _ptr(qval) if nq else None,
+                                          _ptr(qrank) if nq else None, C.byref(m), C.byref(nnan)))
+        return self._dist_result(*a, m, nnan)
+
+    def dist_kernel_ms(self):
+        """(keys_ms, hist_ms, select_ms): GPU time of the phases of the last distribution call (sitrk_dist_kernel_ms)"""
+        v = [C.c_float(0) for _ in range(3)]
+        self._chk(self._L.sitrk_dist_kernel_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def dist_stats(self):
+        """(passes, top_pass_ms): the digit passes the selection of the last distribution call ran and the GPU time of the first
+        of them (sitrk_dist_stats)"""
+        n, t = _int(0), C.c_float(0)
+        self._chk(self._L.sitrk_dist_stats(self._h, C.byref(n), C.byref(t)))
+        return n.value, t.value
 
     # -- dispersion of buoy pairs (sitrk_pairs_*)
     @staticmethod

@@ -137,6 +137,7 @@ SITRK_API int sitrk_destroy(sitrk_t *h)
     h->coarse_timer.release();
     h->label_timer.release();
     h->skel_timer.release();
+    h->dist_timer.release();
     free_records(h);
     dev_free(h->geo); dev_free(h->geoF); dev_free(h->orient); dev_free(h->tmask); dev_free(h->scratch); dev_free(h->counter); dev_free(h->tlerp_theta);
     if (h->box_ev) (void)hipEventDestroy(h->box_ev);
@@ -317,6 +318,8 @@ SITRK_API int sitrk_set_tuning(sitrk_t *h, const char *knob, int value)
     }
     else if (!strcmp(knob, "skeleton_batch"))        // sub-iterations per launch of the next skeleton call
         return skeleton_set_batch(h, value);
+    else if (!strcmp(knob, "dist_aggregate"))        // per-wave aggregation in the select passes of the next distribution call
+        return dist_set_aggregate(h, value);
     else if (!strcmp(knob, "raster_count")) {        // the next raster calls count their claims and atomics (sitrk_raster_stats)
         if (value < 0 || value > 1) return fail(h, SITRK_EINVAL, "sitrk_set_tuning: raster_count must be 0 or 1");
         h->raster_count = value;

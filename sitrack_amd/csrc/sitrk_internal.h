@@ -310,6 +310,13 @@ struct sitrk_ctx {
     sitrk::PhaseTimer<4> skel_timer;
     int skeleton_batch = 0;             // knob: sub-iterations per launch of the thinning kernel, 1..8; 0 = as shipped (never changes results)
 
+    // distribution of values (sitrk_dist.hip): events around the phases of the last call -- keys, histogram, the top-digit pass
+    // of the selection, its other passes -- and the digit passes it ran
+    sitrk::PhaseTimer<5> dist_timer;
+    int dist_passes = 0;
+    int dist_aggregate = 0;             // knob: a wave whose matching keys share the digit adds their number once (measured no faster:
+                                        // DESIGN.md 3.21; never changes results)
+
     // scratch for fetch / locate
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -392,6 +399,8 @@ int keep_from_labels(sitrk_ctx *h, int64_t npix, const int32_t *labels, const in
 void track_release(sitrk_ctx *h);
 // sitrk_skeleton.hip: the knob skeleton_batch behind its range check (sitrk_set_tuning)
 int skeleton_set_batch(sitrk_ctx *h, int value);
+// sitrk_dist.hip: the knob dist_aggregate behind its range check (sitrk_set_tuning)
+int dist_set_aggregate(sitrk_ctx *h, int value);
 // sitrk_coast.hip: frees the coast index (sitrk_destroy: the timer too); grid_changed = only an index that was built from
 // the context's grid (sitrk_set_grid)
 void coast_release(sitrk_ctx *h, bool grid_changed, bool destroy);

@@ -29,7 +29,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib, coarse, dispersion, features, ncio, raster
+from . import _lib, coarse, dispersion, distribution, features, ncio, raster
 from .distributed import Comm, all_ranges
 from .tracking import GetTimeSpan, IceTracker, SeedInit, tinterp_phase
 
@@ -120,11 +120,20 @@ def parse_args(argv=None):
     ap.add_argument('--deform-features', type=_deform_features_arg, default=None, metavar='WHAT@THR[@MINPIX[@CONN]]',
                     help='with --deform and --deform-grid: after each window the map of every mesh is taken apart into its features '
                          '(extra; default none): the connected sets of pixels whose rate passes a threshold, labelled on the GPU.  WHAT '
-                         'is div (div >= THR), conv (-div >= THR), shr, vor or tot (div^2 + shr^2 >= THR^2), THR in 1/s; features of '
+                         'is div (div >= THR), conv (-div >= THR), shr, vor or tot (div^2 + shr^2 >= THR^2), THR in 1/s, or pNN: the NN-th '
+                         'percentile (0..100) of that rate over the status-1 cells of the mesh and window, taken on the GPU, logged and '
+                         'stored as m<k>_w<k>_features_thr (`features` then holds NaN for thr, `features_pct` the NN); features of '
                          'fewer than MINPIX pixels (default 1) are dropped; CONN = 4 or 8 neighbours (default 8).  Stored as '
                          'm<k>_w<k>_features (rows, 12) int64 -- label, npix, jmin, jmax, imin, imax, the sums of j, i, j^2, i^2, j*i and '
                          'the perimeter -- with m<k>_w<k>_features_counts = (nfeat, ncomp, nactive), next to `features` = (what, sgn, '
                          'thr, min_pix, conn); the feature count and the longest feature are logged.  At most 32768 pixels a side')
+    ap.add_argument('--deform-pdf', type=_deform_pdf_arg, default=None, metavar='WHAT@LO:HI:NB[@lin|log][,...]',
+                    help='with --deform: after each window the distribution of a rate over the status-1 cells of every mesh, counted '
+                         'and selected on the GPU (extra; default none).  WHAT is div, conv (-div), shr, vor, tot, adiv (|div|) or avor '
+                         '(|vor|); NB bins (1..1024) from LO to HI in 1/s, geometric (`log`, the default, LO > 0) or equidistant '
+                         '(`lin`).  Stored as m<k>_w<k>_pdf_<WHAT> (NB+2) int64 -- the cells below LO, in each bin, at or above HI -- '
+                         'and m<k>_w<k>_q_<WHAT>, the exact quantiles 0.5, 0.75, 0.85, 0.9, 0.95, 0.99 (each the rate of one cell), next '
+                         'to pdf_<WHAT>_edges and pdf_q; the median, the 95th percentile and the slope of the tail are logged')
     ap.add_argument('--deform-track', type=_deform_track_arg, nargs='?', const=1, default=None, metavar='REACH',
                     help='with --deform-features on the t0 draw: the features of every window are linked to those of the window before '
                          '(extra; default none).  The label map of a window is kept on the GPU, carried to the window\'s end by the '
@@ -169,6 +178,8 @@ def parse_args(argv=None):
         ap.error(refusal)
     if a.deform_features is not None and a.deform_grid is None:
         ap.error("--deform-features: it works on the grid of --deform-grid; give that flag too")
+    if a.deform_pdf is not None and not a.deform:
+        ap.error("--deform-pdf: there is no mesh to take a distribution of without --deform")
     if a.deform_grid is not None and not a.deform:
         ap.error("--deform-grid: there is no mesh to rasterise without --deform")
     if a.deform_coarse is not None and a.deform_grid is None:
@@ -236,6 +247,14 @@ def _deform_features_arg(text):
     """--deform-features: (what, sgn, thr, min_pix, conn) of WHAT@THR[@MINPIX[@CONN]]"""
     try:
         return features.features_arg(text, '--deform-features')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _deform_pdf_arg(text):
+    """--deform-pdf: [(WHAT, edges)] of WHAT@LO:HI:NB[@lin|log][,...]"""
+    try:
+        return distribution.pdf_arg(text, '--deform-pdf')
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -965,8 +984,9 @@ class DeformSeries:
       out      what is kept of every (mesh, window) for the file"""
 
     def __init__(self, specs, window, grid, grid_at, Nt, kstrt, ctx, trk, IDs, nP, say, clk, coarse=None, feat=None, track=None,
-                 skel=None):
+                 skel=None, pdf=None):
         self.specs, self.grid, self.grid_at, self.coarse, self.feat, self.track = specs, grid, grid_at, coarse, feat, track
+        self.pdf = pdf                                   # --deform-pdf: [(WHAT, edges)]
         self.skel = skel                                 # --deform-skeleton: max_sub
         self.links = {}                                  # --deform-track: (mesh, window) -> the links to the window before
         self.ctx, self.trk, self.IDs, self.nP, self.say, self.clk = ctx, trk, IDs, nP, say, clk
@@ -1012,6 +1032,15 @@ class DeformSeries:
             self.say(' *** --deform window %d mesh %d: nQ = %d, status 0/1/2 = %d/%d/%d, area-weighted mean total deformation = %s'
                      % (kw, km, len(r["status"]), stt["n0"], stt["n1"], stt["n2"],
                         '%.6e /s' % (stt["area0_tot"] / stt["area0"]) if stt["area0"] > 0. else 'n/a'))
+            for name, edges in self.pdf or ():           # the distribution of a rate: NB + 2 counts and six values come down
+                what, sgn = distribution.DIST_KINDS[name]
+                d = self.trk.mesh_dist(jrec1, what=what, sgn=sgn, edges=edges, q=distribution.PDF_Q, slot=km)
+                self.out[pre + "pdf_" + name], self.out[pre + "q_" + name] = d["counts"], d["values"]
+                lo = edges[0] if edges[0] > 0. else edges[edges > 0.][0] if (edges > 0.).any() else None
+                self.say(' *** --deform-pdf window %d mesh %d %s: %d cells, %d below / %d at or above the edges, median %.6e /s, '
+                         'p95 %.6e /s, tail slope %s' % (kw, km, name, d["m"], d["counts"][0], d["counts"][-1], d["values"][0], d["values"][4],
+                                                       '%.3f' % distribution.tail_exponent(d["counts"], edges, lo)["slope"]
+                                                       if lo is not None else 'n/a'))
             if self.grid is not None:                    # the map is out[:, owner] on the host: no second copy of the rates
                 self.out[pre + "owner"] = self.trk.mesh_raster(jrec1, self.grid, slot=km, at=self.grid_at, fields=False)["owner"]
             if self.coarse is not None:                  # the scaling curve of this mesh and window: 64 bytes per level come down
@@ -1022,6 +1051,9 @@ class DeformSeries:
                          % (kw, km, len(tab), self.grid[2], '/'.join('%d' % n for n in tab[:, 1]), ', '.join('%.4f' % b for b in beta)))
             if self.feat is not None:                    # the features of this mesh's map: 96 bytes per feature come down
                 what, sgn, thr, min_pix, conn = self.feat
+                if isinstance(thr, distribution.Percentile):           # WHAT@pNN: this mesh's and window's own threshold, 16 bytes down
+                    thr = self.threshold(jrec1, km, kw, what, sgn, thr.pct)
+                    self.out[pre + "features_thr"] = np.float64(thr)
                 # --deform-track: kept map 2km = this window's features, 2km + 1 = those of the window before at this window's start
                 # --deform-skeleton without it: the last kept map, for this call only
                 slot = 2 * km if self.track is not None else _lib.KEEP_MAX - 1 if self.skel is not None else None
@@ -1060,6 +1092,18 @@ class DeformSeries:
                     self.trk.features_advect(jrec1, self.grid, 2 * km, 2 * km + 1, slot=km)   # ... to the start of the next window
         self.clk.add("deform_s", t_d)
 
+    def threshold(self, jrec1, km, kw, what, sgn, pct):
+        """--deform-features WHAT@pNN: the threshold at which the cell of rank floor(NN/100 * m) among the m status-1 cells of mesh
+        km, and every cell above it, passes the test of mesh_features; no cell: the largest double, which nothing passes"""
+        d = self.trk.mesh_dist(jrec1, what=what, sgn=sgn, q=[pct / 100.], slot=km)
+        if d["m"] == 0:
+            thr = float(np.finfo(np.float64).max)
+        else:
+            thr = distribution.percentile_threshold(what, d["t2"][0] if what == "tot" else d["values"][0])
+        self.say(' *** --deform-features window %d mesh %d: percentile %g of %s over %d cells (rank %d) -> THR = %r /s'
+                 % (kw, km, pct, what, d["m"], d["ranks"][0], thr))
+        return thr
+
     def tracks(self):
         """--deform-track, behind the last window: m<k>_w<k>_track and _age of every feature, and one line per window"""
         for km in range(len(self.specs)):
@@ -1076,6 +1120,7 @@ class DeformSeries:
         """the run's .npz; vTime: the times of records 0..Nt of the series"""
         if self.track is not None:
             self.tracks()
+        pct = self.feat is not None and isinstance(self.feat[2], distribution.Percentile)
         _savez_deflate(fname, meshes=np.array(self.specs, dtype=np.float64).reshape(-1, 2),
                        windows=np.array(self.win, dtype=np.int64).reshape(-1, 2),
                        time0=np.array([vTime[w[0] - kstrt] for w in self.win], dtype=np.int64),
@@ -1083,7 +1128,11 @@ class DeformSeries:
                        **({"grid": np.array(self.grid, dtype=np.float64), "grid_at": np.array(self.grid_at)} if self.grid else {}),
                        **({"coarse": np.array(self.coarse, dtype=np.float64)} if self.coarse else {}),
                        **({"features": np.array((_lib.FEAT_WHAT[self.feat[0]],) + tuple(self.feat[1:]), dtype=np.float64)}
-                          if self.feat else {}),
+                          if self.feat and not pct else {}),
+                       **({"features": np.array((_lib.FEAT_WHAT[self.feat[0]], self.feat[1], np.nan) + tuple(self.feat[3:]), dtype=np.float64),
+                           "features_pct": np.array([self.feat[2].pct], dtype=np.float64)} if pct else {}),
+                       **({"pdf_%s_edges" % name: edges for name, edges in self.pdf} if self.pdf else {}),
+                       **({"pdf_q": np.array(distribution.PDF_Q, dtype=np.float64)} if self.pdf else {}),
                        **({"track": np.array([self.track], dtype=np.int64)} if self.track is not None else {}),
                        **({"skeleton": np.array([self.skel], dtype=np.int64)} if self.skel is not None else {}))
 
@@ -1289,7 +1338,7 @@ def main(argv=None):
     ingest = BoxIngest(ctx, records, comm, clk, kstrt, K, mesh.Nj, ctx.field_dtype.itemsize, a.full_records, tphase is not None, bcast)
     dfm = DeformSeries(a.deform, a.deform_window, mesh.dfm_grid, a.deform_grid and a.deform_grid[1], Nt, kstrt, ctx, trk, seeds.IDs, nP,
                        say, clk, coarse=a.deform_coarse, feat=a.deform_features, track=a.deform_track,
-                       skel=a.deform_skeleton) if a.deform else None
+                       skel=a.deform_skeleton, pdf=a.deform_pdf) if a.deform else None
     prs = PairSeries(a.pairs, a.pairs_window, a.pairs_every, Nt, kstrt, ctx, trk, nP, say, clk) if a.pairs is not None else None
 
     # ---- the record loop (:361-496).  The reference steps record by record; here consecutive records go through ONE

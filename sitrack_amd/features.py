@@ -18,6 +18,7 @@ import math
 
 import numpy as np
 
+from .distribution import Percentile, percentile_arg
 from ._lib import FEAT_COLS, FEAT_NCOLS, FEAT_WHAT, KEEP_MAX, MATCH_MAXREACH, MATCH_MAXSHIFT, SKEL_COLS, SKEL_MAXSUB, SKEL_NCOLS
 
 MAX_SIDE = 32768
@@ -70,24 +71,27 @@ def check_test(what, sgn, thr, cerr=''):
 
 def features_arg(text, flag='--deform-features'):
     """(what, sgn, thr, min_pix, conn) of WHAT@THR[@MINPIX[@CONN]]: WHAT one of div, conv (div with sgn -1), shr, vor, tot; THR
-    finite (tot: >= 0), in the unit of the rates; MINPIX an integer >= 1 (default 1); CONN 4 or 8 (default 8).  ValueError
-    otherwise."""
+    finite (tot: >= 0), in the unit of the rates, or pNN, which gives distribution.Percentile(NN), NN in [0, 100]; MINPIX an
+    integer >= 1 (default 1); CONN 4 or 8 (default 8).  ValueError otherwise."""
     tok = text.strip().split('@')
     if len(tok) not in (2, 3, 4):
         raise ValueError("%s: expected WHAT@THR[@MINPIX[@CONN]], got %r" % (flag, text))
     if tok[0] not in FEATURE_KINDS:
         raise ValueError("%s: WHAT must be one of %s, got %r" % (flag, ", ".join(FEATURE_KINDS), text))
     what, sgn = FEATURE_KINDS[tok[0]]
+    # pNN: the NN-th percentile of the rate over the cells, resolved on the device where the threshold is needed
+    pct = percentile_arg(tok[1], flag) if tok[1][:1] == 'p' else None
     try:
-        thr = float(tok[1])
+        thr = pct if pct is not None else float(tok[1])
         min_pix = int(tok[2]) if len(tok) > 2 else 1
         conn = int(tok[3]) if len(tok) > 3 else 8
     except ValueError:
         raise ValueError("%s: expected a number and integers in WHAT@THR[@MINPIX[@CONN]], got %r" % (flag, text)) from None
-    if not math.isfinite(thr):
-        raise ValueError("%s: THR must be finite, got %r" % (flag, text))
-    if what == "tot" and thr < 0.:
-        raise ValueError("%s: THR of tot must be >= 0, got %r" % (flag, text))
+    if not isinstance(thr, Percentile):
+        if not math.isfinite(thr):
+            raise ValueError("%s: THR must be finite, got %r" % (flag, text))
+        if what == "tot" and thr < 0.:
+            raise ValueError("%s: THR of tot must be >= 0, got %r" % (flag, text))
     if min_pix < 1:
         raise ValueError("%s: MINPIX must be >= 1, got %r" % (flag, text))
     if conn not in (4, 8):

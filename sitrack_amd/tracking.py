@@ -386,6 +386,35 @@ class IceTracker:
         g = check_levels(check_grid(grid, cerr), nlev, fmin, cerr)
         return name_levels(self.ctx.mesh_coarse(slot, jrec1, g, int(nlev), fmin=float(fmin), boxes=boxes))
 
+    def mesh_dist(self, jrec1, what="tot", sgn=+1, edges=None, q=None, slot=0):
+        """Right after the step of `jrec1`: the distribution of a deformation rate over the status-1 cells of mesh `slot` (an
+        extra the reference does not have; sitrk_mesh_dist) -- the cells the stats of mesh_deform() are summed over.  what =
+        "div", "shr" or "vor", taken as f, -f or |f| for sgn = +1, -1, 0, or "tot" (sgn +1).  The dict of sit.ValueDistribution:
+        counts (nb + 2,) int64 for the edges (nb + 1,), None without; values (nq,) and ranks (nq,) for the quantiles q, each the
+        value at rank min(m - 1, floor(q*m)) of the ascending sample, bit for bit the rate of one cell; m, nnan.  For "tot" the
+        device works on t2 = div*div + shr*shr, where no second square root enters: the edges given here are those of tot and
+        are squared on the host (they must be >= 0 and stay strictly ascending), values = math.sqrt of the selected t2, and the
+        selected t2 themselves come back as "t2" -- what sit.percentile_threshold("tot", t2) takes.  The per-cell results stay
+        on the device: only the counts, the values and two integers come down."""
+        import math
+        from .distribution import check_edges, check_q, square_edges
+        cerr = 'ERROR [IceTracker.mesh_dist()]: '
+        if what not in _lib.DIST_WHAT:
+            raise ValueError(cerr + '`what` must be one of %s, got %r' % (", ".join(sorted(_lib.DIST_WHAT)), what))
+        if sgn not in (1, -1, 0):
+            raise ValueError(cerr + '`sgn` must be +1, -1 or 0 (the absolute value), got %r' % (sgn,))
+        if what == "tot" and sgn != 1:
+            raise ValueError(cerr + 'what="tot" needs sgn = +1, got %r' % (sgn,))
+        e = None if edges is None else check_edges(edges, cerr)
+        e_dev = e if e is None or what != "tot" else square_edges(e, cerr)
+        v = None if q is None else check_q(q, cerr)
+        r = self.ctx.mesh_dist(slot, jrec1, what, sgn=int(sgn), edges=e_dev, q=v)
+        r["edges"] = e
+        if what == "tot":
+            r["t2"] = r["values"]
+            r["values"] = np.array([math.sqrt(t) if t == t else t for t in r["t2"]], dtype=np.float64)
+        return r
+
     def mesh_features(self, jrec1, grid, what="tot", thr=0., sgn=1, conn=8, min_pix=1, maxfeat=65536, slot=0, at="t0", labels=False,
                       keep=None):
         """Right after the step of `jrec1`: the features of the map of mesh `slot` on the grid (y0_km, x0_km, d_km, ny, nx) of

@@ -2,7 +2,7 @@
 """Deformation rates of buoy triangles / quadrangles between two records of a trajectory file the tracker wrote (the
 2-record file or the `-F` series), on the GPU (sitrk_deform_cells; contract in include/sitrk.h).
 
-    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]] [--track [REACH]] [--skeleton [MAXSUB]]]]
+    python tools/deformation.py -i TRACKFILE -c CELLS.npy [-k K0] [-K K1] [--pdf WHAT@LO:HI:NB[@lin|log][,...]] [--grid D_KM [--coarse NLEV[@FMIN]] [--features WHAT@THR[@MINPIX[@CONN]] [--track [REACH]] [--skeleton [MAXSUB]]]]
                                 [-o OUT.npz]
 
 CELLS.npy is an (nC, 3) or (nC, 4) integer array of `id_buoy` values, either orientation.  `-c auto` triangulates the valid
@@ -33,6 +33,12 @@ by at most MAXSUB sub-iterations (1..2^20, default 4096): OUT then holds `skelet
 pixels, ends, junctions, orthogonal and diagonal links, one row per row of `features` --, `skeleton_nodes` (rows, 3) int64 --
 pixel, label, X of every end, junction and isolated pixel --, `skeleton_counts` = (nfeat, nnode, nskel, nsub, converged) and
 `skeleton_arg` = (max_sub,).
+`--pdf WHAT@LO:HI:NB[@lin|log][,...]` takes the distribution of a rate over the valid cells on the GPU (sitrk_dist_values;
+DESIGN.md 3.21): WHAT = div, conv (-div), shr, vor, tot, adiv (|div|) or avor (|vor|), NB bins (1..1024) from LO to HI, geometric
+(`log`, the default, LO > 0) or equidistant.  OUT then holds `pdf_<WHAT>` (NB+2) int64 -- the cells below LO, in each bin, at or
+above HI --, `q_<WHAT>`, the exact quantiles `pdf_q` = 0.5, 0.75, 0.85, 0.9, 0.95, 0.99, each the rate of one cell, and
+`pdf_<WHAT>_edges`.  `--features WHAT@pNN[...]` states the threshold as the NN-th percentile of the rate over the valid cells; it
+is resolved the same way (sit.percentile_threshold) and stored as `features_thr`.
 
 Caveat: the files hold positions as f4 km.  At |x| ~ 3000 km that is 0.24 m of rounding per coordinate, 2e-5 of a 10-km
 cell -- the size of the strains of interest over a few hours.  A running tracker holds the positions in fp64 on the device:
@@ -94,6 +100,9 @@ def main(argv=None):
     ap.add_argument('--features', default=None, metavar='WHAT@THR[@MINPIX[@CONN]]',
                     help='with --grid: also label the connected features of the map where the rate WHAT (div, conv, shr, vor, tot) passes '
                          'THR [1/s] (`features`, `features_counts`, `features_arg` in the output)')
+    ap.add_argument('--pdf', default=None, metavar='WHAT@LO:HI:NB[@lin|log][,...]',
+                    help='also the distribution of the rate WHAT (div, conv, shr, vor, tot, adiv, avor) over the valid cells: NB bins from LO '
+                         'to HI [1/s] and six exact quantiles (`pdf_<WHAT>`, `q_<WHAT>`, `pdf_<WHAT>_edges`, `pdf_q` in the output)')
     ap.add_argument('--track', nargs='?', const='1', default=None, metavar='REACH',
                     help='with --features: also link the features to those of the next window of as many records, K1 -> K1 + (K1 - K0), '
                          'within REACH pixels (0..2, default 1) (`next_features`, `pairs`, `pairs_counts`, `parent`, `child`, '
@@ -128,6 +137,12 @@ def main(argv=None):
             sys.exit('ERROR: --features: it works on the grid of --grid; give that flag too')
         try:
             feat = features_arg(a.features, '--features')
+        except ValueError as e:
+            sys.exit('ERROR: %s' % e)
+    pdf = None
+    if a.pdf is not None:
+        try:
+            pdf = sit.pdf_arg(a.pdf, '--pdf')
         except ValueError as e:
             sys.exit('ERROR: %s' % e)
     coarse = None
@@ -188,6 +203,14 @@ def main(argv=None):
     ctx = sit.Context(a.device)
     try:
         r = sit.DeformCells(yx0, yx1, cols, T, mask0=ok0, mask1=ok1, ctx=ctx)
+        from sitrack_amd import distribution as dst
+        for name, edges in pdf or ():
+            d = dst.rate_distribution(r, name, edges=edges, q=dst.PDF_Q, use=r['valid'], ctx=ctx)
+            r['pdf_' + name], r['q_' + name], r['pdf_%s_edges' % name] = d['counts'], d['values'], edges
+            print(' *** --pdf %s: %d cells, %d below / %d at or above the edges, median %.6e /s, p95 %.6e /s'
+                  % (name, d['m'], d['counts'][0], d['counts'][-1], d['values'][0], d['values'][4]))
+        if pdf:
+            r['pdf_q'] = np.array(dst.PDF_Q, dtype=np.float64)
         if a.grid is not None:
             if not ok0.any():
                 sys.exit('ERROR: --grid: no valid buoy at record %d' % k0)
@@ -206,6 +229,13 @@ def main(argv=None):
                 if grid[3] > 32768 or grid[4] > 32768:
                     sys.exit('ERROR: --features: %g km over the points is %d x %d pixels, more than 32768 a side' % (a.grid, grid[3], grid[4]))
                 what, sgn, thr, min_pix, conn = feat
+                if isinstance(thr, dst.Percentile):                    # WHAT@pNN: resolved on the GPU over the valid cells
+                    pct = thr.pct
+                    d = dst.rate_distribution(r, 'conv' if (what, sgn) == ('div', -1) else what, q=[pct / 100.], use=r['valid'], ctx=ctx)
+                    thr = (dst.percentile_threshold(what, d['t2'][0] if what == 'tot' else d['values'][0]) if d['m']
+                           else float(np.finfo(np.float64).max))
+                    r['features_thr'], r['features_pct'] = np.float64(thr), np.float64(pct)
+                    print(' *** --features: percentile %g of %s over %d cells (rank %d) -> THR = %r /s' % (pct, what, d['m'], d['ranks'][0], thr))
 
                 def labelled(rates, own):
                     at = np.maximum(own, 0)
